@@ -8,16 +8,23 @@ pressure and velocity update, rtol 1e-8 / atol 1e-14.  A "step" is one Fractiona
 Synthetic data, float64 throughout.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full
+    python bench.py --gpus N --steps K --warmup W --dump-outputs DIR
 
 Other workloads: ``--workload beltrami`` (Ethier-Steinman, w != 0: SURVEY.md 8d's stronger field),
 ``--workload cavity`` (BASELINE.json configs[3]: unit cube, lid u = (1,0,0) on z = 1, nu = 1e-3,
 dt = 1/N, from rest).
 
-Prints ONE compact JSON line (<= 8000 bytes) on rank 0's stdout -- the contract's keys, `roofline`, `cpu_baseline`,
-`headline_petsc_default` -- as soon as the headline, the counter passes and the CPU baseline exist, and NOTHING after it.
-The full record (kernel tables, Krylov series, variant legs, predictions) goes to ``gpurun_out/bench_full.json``
-(``--full-out``).  The heavy legs (Beltrami / cavity / Delaunay workloads with their host cross-checks, the one-core CPU
-repetition) run only with ``--extras``, after the line is out, and land in the side file.
+A plain run sets up, warms up, times the K steps and prints ONE compact JSON line (<= 8000 bytes) on rank 0's stdout:
+the contract's keys, with `roofline` priced from the HIP events inside the timed steps (no counters) and
+`cpu_baseline` null.  ``--dump-outputs DIR`` first writes what the last timed step computed (``u.npy``, ``p.npy``:
+see ``dump_fields``).
+``--full`` adds everything else the line and its side file carry: the rocprofv3 counter passes, the variant legs, the
+256^3 past-cache SpMV and the CPU baseline; the line comes when they exist, and NOTHING on stdout after it.  The
+full record (kernel tables, Krylov series, variant legs, predictions) goes to ``bench_out/bench_full.json``
+(``--full-out``; a plain run writes it only where that is given).  The heavy legs (Beltrami / cavity / Delaunay
+workloads with their host cross-checks, the one-core CPU repetition) run only with ``--extras`` (implies ``--full``),
+after the line is out, and land in the side file.
   roofline      the pressure-Poisson CG SpMV.  `traffic` = HBM bytes per launch from two rocprofv3 --pmc passes
                 (FETCH_SIZE x 2, WRITE_SIZE) of this same command, run as child processes before this process touches
                 the GPU; `avg_launch_us` = the same kernel's duration in a third child pass (--kernel-trace);
@@ -31,6 +38,7 @@ repetition) run only with ``--extras``, after the line is out, and land in the s
                 dictionaries off (what a mesh without bit-identical cells gets)
   cpu_baseline  one step of the same workload on the host cores (oracle/ipcs_cpu.c), all cores (one core too with
                 --extras), set up from the mesh definition alone
+(roofline.traffic / past_cache / f64_values, headline_petsc_default and cpu_baseline: --full only.)
 """
 from __future__ import annotations
 
@@ -59,7 +67,54 @@ def spmv_bytes(nnz, n_rows, n_cols):
     return 12 * nnz + 4 * (n_rows + 1) + 8 * n_cols + 8 * n_rows
 
 
-def parse():
+# ---- --dump-outputs: what the timed path computed -------------------------------------------------
+DUMP_SAMPLE = 1 << 20  # dofs per field at most (128^3 P2-P1: 25 MB of u + 8 MB of p)
+DUMP_SEED = 20240611
+
+
+def coordinate_order(x):
+    """Permutation that lists the points ``x`` (n, d) in lexicographic order of their coordinates, quantised to 2^-20 of
+    the bounding box: the same points in any dof numbering (or split over any number of ranks) give the same order."""
+    import torch
+
+    lo = x.min(0).values
+    span = (x.max(0).values - lo).clamp_min(1e-300)
+    q = torch.round((x - lo) / span * (1 << 20)).to(torch.int64)  # 0 .. 2^20: 21 bits per coordinate
+    key = q[:, 0]
+    for j in range(1, x.shape[1]):
+        key = key * ((1 << 20) + 1) + q[:, j]
+    return torch.argsort(key, stable=True)
+
+
+def dump_sample(n, k=DUMP_SAMPLE, seed=DUMP_SEED):
+    """Positions (ascending) of the fixed, seeded sample of ``k`` out of ``n`` coordinate-ordered dofs; all of them if
+    ``n <= k``."""
+    import numpy as np
+
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_fields(out_dir, fields):
+    """``fields``: name -> (coordinates (n, d), values (n,) or (n, c)), torch tensors of the owned dofs.  Writes
+    ``out_dir/<name>.npy`` (float64): the values in coordinate order, sampled by ``dump_sample``.  Returns the bytes
+    written."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, (x, v) in fields.items():
+        order = coordinate_order(x)
+        pick = order[torch.from_numpy(dump_sample(int(order.numel()))).to(order.device)]
+        a = np.ascontiguousarray(v[pick].double().cpu().numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return total
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)  # the driver's command line: --steps 20 --warmup 5
@@ -72,6 +127,12 @@ def parse():
     ap.add_argument("--zero-guess", action="store_true",
                     help="PETSc default: zero the solution before every Krylov solve "
                          "(default here: -ksp_initial_guess_nonzero, the previous field is the guess)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the rocprofv3 counter passes, the variant legs, the 256^3 past-cache SpMV, "
+                         "the cpu_baseline leg and the side file (each can be left out with its --no-* flag below)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/u.npy and DIR/p.npy (float64, dofs in coordinate "
+                         "order; fields of more than %d dofs: a fixed, seeded sample of them)" % DUMP_SAMPLE)
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-cpu-one-core", action="store_true",
                     help="(kept for old command lines; the 1-core repetition of the cpu_baseline step -- about a minute at "
@@ -80,10 +141,11 @@ def parse():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the cheap variant legs (steady state, zero guess, dictionaries off) and the 256^3 past-cache SpMV")
     ap.add_argument("--extras", action="store_true",
-                    help="AFTER the JSON line is out: the Beltrami / cavity / refined-Delaunay workload legs with their host "
-                         "cross-checks and the one-core cpu_baseline repetition; results go to the --full-out side file only")
+                    help="(implies --full) AFTER the JSON line is out: the Beltrami / cavity / refined-Delaunay workload legs "
+                         "with their host cross-checks and the one-core cpu_baseline repetition; results go to the --full-out "
+                         "side file only")
     ap.add_argument("--full-out", default=None,
-                    help="path of the full record (default gpurun_out/bench_full.json under the repository root)")
+                    help="path of the full record (default with --full: bench_out/bench_full.json under the repository root)")
     ap.add_argument("--probe-transports", action="store_true",
                     help="N > 1: AFTER the JSON line is out, time both device transports' halo exchanges (brings up the "
                          "xGMI-window transport on a temporary plan); results go to stderr and the side file")
@@ -123,9 +185,13 @@ def parse():
     ap.add_argument("--profile-every", type=int, default=32,
                     help="HIP-event pair around every n-th launch of a kernel tag inside the timed region")
     ap.add_argument("--verbose", action="store_true")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.pdeg is None:
         a.pdeg = 2 if a.udeg >= 3 else 1
+    if a.extras:
+        a.full = True
+    if not a.full:  # a plain run: the headline and nothing else
+        a.no_pmc = a.no_extras = a.no_cpu = True
     return a
 
 
@@ -232,7 +298,7 @@ def rocprof_passes(child_argv, log, label, budget_s=240):
 def child_argv_of(args):
     """The flags that make a --pmc-child run the same workload as this command."""
     av = ["-N", str(args.N), "--udeg", str(args.udeg), "--pdeg", str(args.pdeg), "--workload", args.workload,
-          "--steps", "1", "--warmup", "1", "--rtol", str(args.rtol)]
+          "--steps", "1", "--warmup", "1", "--rtol", str(args.rtol), "--full"]  # (--full: the past-cache SpMV too)
     for flag, on in (("--zero-guess", args.zero_guess), ("--matrix-free", args.matrix_free),
                      ("--no-dictionary", args.no_dictionary), ("--no-extras", args.no_extras)):
         if on:
@@ -435,7 +501,10 @@ def compact_line(full, limit=COMPACT_LIMIT):
 
 
 def write_full(path, full):
-    """The full record as one JSON line in the side file (rewritten whole: a later leg replaces the earlier copy)."""
+    """The full record as one JSON line in the side file (rewritten whole: a later leg replaces the earlier copy).
+    ``path`` None: no side file (a plain run without --full-out)."""
+    if path is None:
+        return None
     try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path + ".tmp", "w") as f:
@@ -514,9 +583,10 @@ def main():
         if extras_legs and args.udeg == 2 and args.N >= 96:
             leg_passes = rocprof_passes(["-N", str(DELAUNAY_LEG[0]), "--mesh", "delaunay", "--refine", str(DELAUNAY_LEG[1]),
                                          "--workload", "beltrami", "--udeg", str(args.udeg), "--pdeg", str(args.pdeg),
-                                         "--steps", "1", "--warmup", "1", "--rtol", str(args.rtol), "--no-extras"],
+                                         "--steps", "1", "--warmup", "1", "--rtol", str(args.rtol), "--full", "--no-extras"],
                                         log, "the unstructured leg", budget_s=600)
-    full_path = args.full_out or os.path.join(ROOT, "gpurun_out", "bench_full.json")
+    # the side file: always with --full, in a plain run only where --full-out names it
+    full_path = args.full_out or (os.path.join(ROOT, "bench_out", "bench_full.json") if args.full else None)
 
     os.environ.setdefault("OMP_NUM_THREADS", str(host_cores()))  # cpu_baseline leg (oracle/ipcs_cpu.c)
     import numpy as np
@@ -818,6 +888,21 @@ def main():
         return {k: [int(np.max(i[k])) if len(i[k]) else 0 for i in its] for k in its[0]}
 
     elapsed, its = timed_run(args.steps, args.warmup, True)
+    if args.dump_outputs and not args.pmc_child:
+        # what a caller of the timed path receives after its last step: the velocity and the pressure of the owned dofs,
+        # in coordinate order (every rank's share gathered on rank 0: the same files for any rank count)
+        fields = {"u": (S._Vi[0][0].x[: S._no_u], S._U.rdev()[: S._no_u]), "p": (S._Q.x[: S._no_q], S._P.rdev()[: S._no_q, 0])}
+        if world > 1:
+            import torch.distributed as dist
+
+            parts = [None] * world
+            dist.all_gather_object(parts, {k: (x.cpu().numpy(), v.cpu().numpy()) for k, (x, v) in fields.items()})
+            fields = {k: tuple(torch.from_numpy(np.concatenate([p_[k][j] for p_ in parts])).cuda() for j in (0, 1))
+                      for k in fields}
+        if rank == 0:
+            nbytes = dump_fields(args.dump_outputs, fields)
+            log(f"--dump-outputs: {nbytes / 1e6:.1f} MB in {args.dump_outputs}")
+        del fields
     phase_ms = {k: sum(a.elapsed_time(b) for a, b in v) / args.steps for k, v in phase_events.items() if k != "_on"}
     # accuracy at the end of the timed steps: nodal error against the analytic field (rank-local dofs)
     Xd = S._Vi[0][0].x[: S._n_u].T
@@ -1169,7 +1254,7 @@ def main():
             "setup_s": t_setup,
             "hbm_gib": torch.cuda.max_memory_allocated() / 2 ** 30,
             "cpu_baseline": None,  # timed on rank 0 at N = 1 only (below)
-            "full_record": os.path.relpath(full_path, ROOT),
+            "full_record": os.path.relpath(full_path, ROOT) if full_path else None,
         }
         if variants:  # PETSc's own defaults in one place: zero initial guess, no value dictionaries
             zg = variants.get("initial_guess_nonzero=False")

@@ -117,11 +117,11 @@ def test_the_compact_line_drops_optional_blocks_before_it_breaks_the_limit():
 
 @pytest.mark.gpu
 def test_bench_runs_and_prints_one_json_line(tmp_path):
-    """The driver's own command but for the mesh size: default flags (counter child passes, variant legs, past-cache
-    SpMV, cpu_baseline), ONE stdout line within the limit, the full record in the side file."""
+    """The driver's own command but for the mesh size, with --full (counter child passes, variant legs, past-cache
+    SpMV, cpu_baseline): ONE stdout line within the limit, the full record in the side file."""
     side = str(tmp_path / "full.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "-N", "16", "--steps", "2", "--warmup", "1",
-                          "--full-out", side], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--full-out", side], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -223,7 +223,7 @@ def test_the_launcher_line_with_one_rank_is_the_plain_line():
     # (the launched run WITH the counter child passes, as the driver's SCALE series runs it at N = 1: the rocprofv3
     # children inherit the launcher's WORLD_SIZE = 1 / RANK / MASTER_* environment)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", *[t for t in tail if t != "--no-pmc"]]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", *[t for t in tail if t != "--no-pmc"]]
     launched = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert launched.returncode == 0, launched.stderr[-3000:]
     a, b = (json.loads([ln for ln in o.stdout.strip().splitlines() if ln.strip().startswith("{")][-1]) for o in (plain, launched))
@@ -239,3 +239,76 @@ def test_the_launcher_line_with_one_rank_is_the_plain_line():
     assert a["roofline"]["kernel"] == b["roofline"]["kernel"] and a["roofline"]["stored_bytes_per_launch"] == b["roofline"]["stored_bytes_per_launch"]
     assert a["roofline"]["traffic"] is None and "NO COUNTERS" in a["roofline"]["basis"]
     assert b["roofline"]["traffic"] is not None and "rocprofv3" in b["roofline"]["basis"], b["roofline"].get("counters_error")
+
+
+def test_a_plain_run_leaves_everything_but_the_headline_to_full():
+    """`bench.py --steps K --warmup W` does the headline only; --full (or --extras, which implies it) brings back the
+    counter passes, the variant legs and the CPU baseline, each still switchable off on its own."""
+    import bench
+
+    a = bench.parse(["--steps", "3", "--warmup", "1"])
+    assert not a.full and a.no_pmc and a.no_extras and a.no_cpu and a.steps == 3 and a.dump_outputs is None
+    a = bench.parse(["--full"])
+    assert a.full and not (a.no_pmc or a.no_extras or a.no_cpu)
+    a = bench.parse(["--full", "--no-cpu"])
+    assert a.full and a.no_cpu and not (a.no_pmc or a.no_extras)
+    assert bench.parse(["--extras"]).full
+    # the counter child passes of a --full run are --full runs themselves (the past-cache SpMV is in their tables)
+    assert "--full" in bench.child_argv_of(bench.parse(["--full"]))
+
+
+def test_dumped_fields_do_not_depend_on_the_dof_numbering(tmp_path):
+    """--dump-outputs lists the dofs in coordinate order: the same field in another numbering (or with coordinates that
+    differ in the last bits) gives the same file; fields beyond DUMP_SAMPLE dofs are sampled, the same dofs every time."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    rng = np.random.default_rng(3)
+    n = 17
+    ijk = np.stack(np.meshgrid(*[np.arange(n)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    x = torch.from_numpy(-1.0 + ijk * (2.0 / (n - 1)))
+    u = torch.from_numpy(rng.standard_normal((x.shape[0], 3)))
+    perm = torch.from_numpy(rng.permutation(x.shape[0]))
+    assert bench.dump_fields(str(tmp_path / "a"), {"u": (x, u), "p": (x, u[:, 0])}) == x.shape[0] * 4 * 8
+    bench.dump_fields(str(tmp_path / "b"), {"u": (x[perm] * (1 + 1e-15), u[perm]), "p": (x[perm], u[perm, 0])})
+    for name in ("u", "p"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "u.npy"), u.numpy())  # meshgrid "ij" order is coordinate order
+    s = bench.dump_sample(10 * bench.DUMP_SAMPLE)
+    assert len(s) == bench.DUMP_SAMPLE and np.all(np.diff(s) > 0) and np.array_equal(s, bench.dump_sample(10 * bench.DUMP_SAMPLE))
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path):
+    """The plain command: no counter passes, no variant legs, no CPU baseline, no side file -- the contract's keys with the
+    HIP-event roofline.  --dump-outputs writes u and p of the last timed step in coordinate order: on the 16^3 box
+    every P2 / P1 dof, whose error against the analytic field is the line's own nodal error."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    out_dir = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "-N", "16", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    _check(d, live_cpu=False, counters=False)
+    assert d["steps"] == 3 and d["warmup"] == 1 and len(d["krylov_iterations_series"]["pressure"]) == 3
+    assert d["cpu_baseline"] is None and "headline_petsc_default" not in d and "past_cache" not in d["roofline"]
+    assert "full_record" not in d
+    assert sorted(os.listdir(out_dir)) == ["p.npy", "u.npy"]
+    u, p = np.load(out_dir / "u.npy"), np.load(out_dir / "p.npy")
+    assert u.dtype == p.dtype == np.float64 and u.shape == (33 ** 3, 3) and p.shape == (17 ** 3,)
+    assert np.isfinite(u).all() and np.isfinite(p).all() and u.nbytes + p.nbytes <= 64 * 2 ** 20
+    ijk = np.stack(np.meshgrid(*[np.arange(33)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    X = (-1.0 + ijk / 16.0).T
+    W = bench.make_workload("tg", 16, np, torch)
+    err = max(np.abs(u[:, i] - f(X, d["accuracy"]["t_end"])).max() for i, f in enumerate(W["fns"]))
+    e_line = d["accuracy"]["max_nodal_error_u_vs_analytic"]  # (the line carries 6 significant digits)
+    assert abs(err - e_line) <= 1e-5 * e_line, (err, d["accuracy"])
