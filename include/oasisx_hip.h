@@ -581,6 +581,42 @@ int ox_profile_get(int tag, long long key, long long *count, double *total_ms); 
 int ox_range_push(const char *name);
 int ox_range_pop(void);
 
+/* ---- Smoothed-aggregation AMG (PETSc's pc_type gamg) for one-column CG on one GPU (ox_amg.hip) ----------------------
+ * The hierarchy is built on the host (oasisx_amd/amg.py); the library keeps copies of the level descriptions below and
+ * its own level vectors.  Level 0 is the caller's operator with all its storage levels; levels 1.. are plain-f64 SELL-64.
+ * Level l < n_levels - 1 is smoothed by `degree` Chebyshev-Jacobi steps,  r = D^-1 (b - A x);  d = c_d d + c_r r;
+ * x += d  with (c_d, c_r) = cheb[2 j], cheb[2 j + 1] (step 1: c_d = 0), the same polynomial before and after the coarse
+ * correction, which goes through P (n_l x n_{l+1}) and R = P^T (n_{l+1} x n_l).  The coarsest level (A, P, R, cheb
+ * unused) is solved with the dense row-major inverse `coarse_inv` (device [n_c * n_c]): a symmetric V-cycle. */
+#define OX_MG_MAX_DEGREE 8
+#define OX_MG_MAX_LEVELS 16
+#define OX_KSP_CG_MG 6 /* the preconditioned CG of ox_ksp_solve_mg: workspace sizing (ox_ksp_work_bytes_for) only */
+typedef struct {
+  ox_sell A;             /* level operator                                   */
+  ox_sell P;             /* prolongation to this level from the next coarser */
+  ox_sell R;             /* restriction, R = P^T                             */
+  const double *dinv;    /* device [n_rows]: 1 / diag(A)                     */
+  int64_t n_rows;
+  int32_t degree;        /* Chebyshev steps (mg_levels_ksp_max_it)           */
+  int32_t reserved;
+  double cheb[2 * OX_MG_MAX_DEGREE];
+} ox_mg_level;
+typedef struct ox_mg ox_mg;
+/* tail_rows: the levels of at most this many rows (and the coarse solve) run in ONE single-workgroup launch; <= 0: the
+ * library's default */
+int ox_mg_create(int n_levels, const ox_mg_level *levels, const double *coarse_inv, int tail_rows, ox_mg **out);
+int ox_mg_destroy(ox_mg *mg);
+/* z = B r: one V-cycle (device vectors of the fine level's rows) */
+int ox_mg_apply(const ox_mg *mg, const double *r, double *z, void *stream);
+/* kernel launches of one V-cycle (reporting) */
+int ox_mg_kernels_per_cycle(const ox_mg *mg);
+/* CG preconditioned by the V-cycle (PETSc's KSPCG + PCGAMG), one right-hand side, one GPU: same options, same state
+ * machinery and the same convergence test on the preconditioned norm |B r| <= max(rtol |B b|, atol) as ox_ksp_solve_opt;
+ * z = B r is stored.  A: the operator of the hierarchy's level 0; work: ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG) bytes;
+ * opt->dinv_code is ignored. */
+int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt, void *work,
+                    size_t work_bytes, ox_ksp_result *result, void *stream);
+
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */
 int ox_comm_create(const char *id128, int rank, int nranks, void **comm_out); /* ncclCommInitRank */

@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OX_LIB_PATH") or os.path.join(_HERE, "liboasisx_hip.so")  # override: tuning builds
 
 KSP_CG, KSP_BCGS, KSP_CG_SINGLE, KSP_BCGS_MERGED, KSP_CG_MERGED = 1, 2, 3, 4, 5
+KSP_CG_MG = 6  # OX_KSP_CG_MG: workspace sizing of ox_ksp_solve_mg
+MG_MAX_DEGREE = 8  # OX_MG_MAX_DEGREE
 ROW_BLOCK_WAVES, ROW_BLOCK_LDS = 8, 134 * 1024  # OX_ROW_BLOCK_WAVES / OX_ROW_BLOCK_LDS of include/oasisx_hip.h
 CONVERGED_RTOL, CONVERGED_ATOL, CONVERGED_ITS = 2, 3, 4
 DIVERGED_ITS, DIVERGED_DTOL, DIVERGED_BREAKDOWN, DIVERGED_NANORINF = -3, -4, -5, -9
@@ -156,6 +158,19 @@ class ox_rect_info(C.Structure):
     ]
 
 
+class ox_mg_level(C.Structure):
+    _fields_ = [
+        ("A", ox_sell),
+        ("P", ox_sell),
+        ("R", ox_sell),
+        ("dinv", C.c_void_p),
+        ("n_rows", C.c_int64),
+        ("degree", C.c_int32),
+        ("reserved", C.c_int32),
+        ("cheb", C.c_double * (2 * MG_MAX_DEGREE)),
+    ]
+
+
 class ox_ksp_result(C.Structure):
     _fields_ = [
         ("reason", C.c_int32 * 4),
@@ -265,6 +280,12 @@ SIGNATURES = {
     "ox_ksp_solve_opt": (_I, [_I, C.POINTER(ox_sell), _P, _P, _P, _I, C.POINTER(ox_ksp_options), _P, C.c_size_t,
                               C.POINTER(ox_ksp_result), _P, _P]),
     "ox_ksp_work_bytes_for": (C.c_size_t, [C.POINTER(ox_sell), _I, _I]),
+    "ox_mg_create": (_I, [_I, C.POINTER(ox_mg_level), _P, _I, C.POINTER(_P)]),
+    "ox_mg_destroy": (_I, [_P]),
+    "ox_mg_apply": (_I, [_P, _P, _P, _P]),
+    "ox_mg_kernels_per_cycle": (_I, [_P]),
+    "ox_ksp_solve_mg": (_I, [_P, C.POINTER(ox_sell), _P, _P, C.POINTER(ox_ksp_options), _P, C.c_size_t,
+                             C.POINTER(ox_ksp_result), _P]),
     "ox_profile_begin": (_I, [_I, _I]),
     "ox_profile_end": (_I, []),
     "ox_profile_get": (_I, [_I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_D)]),

@@ -139,3 +139,6 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 extern bool ox_prof_on;
 void ox_prof_start(int tag, hipStream_t st, long long key = 0);
 void ox_prof_stop(hipStream_t st);
+
+// one V-cycle of an AMG hierarchy (ox_amg.hip): z = B r; every kernel a no-op once *done (nullptr: none)
+int ox_mg_vcycle(const ox_mg *mg, const double *r, double *z, const int *done, hipStream_t st);

@@ -1731,6 +1731,149 @@ static int ksp_run(int ksp_type, const ox_sell *A, const double *dinv, const dou
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// CG preconditioned by an AMG V-cycle (PETSc's KSPCG + PCGAMG; ox_amg.hip), one column, one GPU.  z = B r is stored (the
+// preconditioner is not a diagonal the update kernels could apply on the fly); the synchronisation points, the state and
+// the run-ahead batches are those of the Jacobi CG (PH_CG_INIT, PH_CG_A, PH_CG_B): the convergence test sees |z| = |B r|.
+// Per iteration:  q = A p (+ p.q);  point A;  x += alpha p, r -= alpha q;  z = B r;  {r.z, z.z};  point B;  p = z + beta p.
+// ---------------------------------------------------------------------------------------
+// r = b - q (q = A x0) or r = b, x = 0
+__global__ __launch_bounds__(256) void k_mgcg_init(int64_t n, const double *__restrict__ b, double *x,
+                                                   const double *__restrict__ q, double *r, int guess) {
+  OX_ROW_LOOP {
+    if (guess) {
+      r[row] = b[row] - q[row];
+    } else {
+      r[row] = b[row];
+      x[row] = 0.0;
+    }
+  }
+}
+// partial = {r.z, z.z} (+ zb.zb and p = z at the start of the solve)
+template <bool INIT>
+__global__ __launch_bounds__(256) void k_mgcg_dots(int64_t n, const KspState *S, const double *__restrict__ r,
+                                                   const double *__restrict__ z, const double *__restrict__ zb, double *p,
+                                                   double *partial) {
+  constexpr int NV = INIT ? 3 : 2;
+  __shared__ double red[4 * NV];
+  if (!INIT && S->done) return;
+  double s[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) s[i] = 0.0;
+  OX_ROW_LOOP {
+    const double zz = z[row];
+    s[0] = fma(r[row], zz, s[0]);
+    s[1] = fma(zz, zz, s[1]);
+    if (INIT) {
+      const double w = zb[row];
+      s[NV - 1] = fma(w, w, s[NV - 1]);
+      p[row] = zz;
+    }
+  }
+  ksp_store_partial<NV>(s, red, partial);
+}
+// x += alpha p;  r -= alpha q
+__global__ __launch_bounds__(256) void k_mgcg_update1(int64_t n, const KspState *S, double *x, double *r,
+                                                      const double *__restrict__ p, const double *__restrict__ q) {
+  if (S->done) return;
+  const double a = S->alpha[0];
+  OX_ROW_LOOP {
+    x[row] = fma(a, p[row], x[row]);
+    r[row] = fma(-a, q[row], r[row]);
+  }
+}
+// p = z + beta p
+__global__ __launch_bounds__(256) void k_mgcg_update2(int64_t n, const KspState *S, const double *__restrict__ z, double *p) {
+  if (S->done) return;
+  const double be = S->beta[0];
+  OX_ROW_LOOP { p[row] = fma(be, p[row], z[row]); }
+}
+
+static int mgcg_iterations(const ox_mg *mg, const KspCtx &C, const KspVecs &V, const KspParams &P, int count) {
+  const int64_t n = C.A->n_rows;
+  const int *done = &C.S->done;
+  for (int k = 0; k < count; ++k) {
+    if (ox_spmv_dist(C.A, V.p, V.q, 1, OX_EPI_DOT, nullptr, nullptr, C.partial, done, nullptr, C.st)) return -1;
+    KSP_SYNC(PH_CG_A, C.partial, C.nbs, 1);
+    hipLaunchKernelGGL(k_mgcg_update1, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.x, V.r, V.p, V.q);
+    OX_LAUNCH_CHECK();
+    if (ox_mg_vcycle(mg, V.r, V.z, done, C.st)) return -1;
+    hipLaunchKernelGGL(k_mgcg_dots<false>, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.r, V.z, nullptr, nullptr, C.partial);
+    OX_LAUNCH_CHECK();
+    if (ksp_sync_point<PH_CG_B>(C.S, C.partial, C.nb, 2, C.sums, ksp_last_point(P, k, count), nullptr, C.st)) return -1;
+    hipLaunchKernelGGL(k_mgcg_update2, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.z, V.p);
+    OX_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
+                               void *work, size_t work_bytes, ox_ksp_result *result, void *stream) {
+  if (!mg || !A || !b || !x || !work || !result || !opt) OX_FAIL("ox_ksp_solve_mg: null argument");
+  if (work_bytes < ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG))
+    OX_FAIL("ox_ksp_solve_mg: workspace too small (%zu < %zu)", work_bytes, ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG));
+  if (!(opt->divtol > 0.0)) OX_FAIL("ox_ksp_solve_mg: divtol=%g (must be positive; PETSc's default is 1e4)", opt->divtol);
+  memset(result, 0, sizeof(*result));
+  KspParams P{};
+  P.rtol = opt->rtol;
+  P.atol = opt->atol;
+  P.dtol = opt->divtol;
+  P.max_it = opt->max_it < 1 ? 1 : opt->max_it;
+  P.nc = 1;
+  P.c0 = 0;
+  P.nc_total = 1;
+  const int check_every = opt->check_every < 1 ? 1 : opt->check_every;
+  const int guess = opt->nonzero_guess;
+  const bool ahead = opt->run_ahead != 0;
+  hipStream_t st = ox_stream(stream);
+  const int64_t n = A->n_rows;
+  char *work_c = static_cast<char *>(work);
+  const KspLayout L = ksp_layout(A->n_rows, A->n_cols, 1, OX_KSP_CG_MG, ksp_grid_max(A));
+  KspCtx C{};
+  C.A = A;
+  C.S = reinterpret_cast<KspState *>(work_c + L.state);
+  C.S2 = reinterpret_cast<KspState *>(work_c + L.state2);
+  C.sums = reinterpret_cast<double *>(work_c + L.sums);
+  C.partial = reinterpret_cast<double *>(work_c + L.partial);
+  C.partial2 = reinterpret_cast<double *>(work_c + L.partial2);
+  C.st = st;
+  C.nb = ox_vec_blocks(2 * (n > 0 ? n : 1));
+  C.nbs = ox_spmv_dist_nparts(A, nullptr, 1);
+  double *vec[6];
+  for (int i = 0; i < 6; ++i) vec[i] = reinterpret_cast<double *>(work_c + L.vec0 + L.vec_stride * i);
+  if (!g_state_host) OX_HIP(hipHostMalloc(&g_state_host, 3 * sizeof(KspState)));
+  KspVecs V{};
+  V.x = x, V.r = vec[0], V.z = vec[1], V.p = vec[2], V.q = vec[3];
+  double *zb = vec[4];  // B b (nonzero initial guess: the norm the relative test uses)
+  if (guess && !opt->ax0) {
+    if (ox_spmv_dist(A, x, V.q, 1, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return -1;
+  }
+  hipLaunchKernelGGL(k_mgcg_init, dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && opt->ax0) ? opt->ax0 : V.q, V.r, guess);
+  OX_LAUNCH_CHECK();
+  if (guess && ox_mg_vcycle(mg, b, zb, nullptr, st)) return -1;
+  if (ox_mg_vcycle(mg, V.r, V.z, nullptr, st)) return -1;
+  hipLaunchKernelGGL(k_mgcg_dots<true>, dim3(C.nb), dim3(256), 0, st, n, C.S, V.r, V.z, guess ? zb : V.z, V.p, C.partial);
+  OX_LAUNCH_CHECK();
+  KSP_SYNC(PH_CG_INIT, C.partial, C.nb, 3);
+  int it = 0;
+  auto it1 = [&](int count) -> int { return mgcg_iterations(mg, C, V, P, count); };
+  if (ahead) {
+    if (ksp_run_ahead(C, it1, check_every > 8 ? 8 : check_every, it, P.max_it)) return -1;
+  } else {
+    for (; it <= P.max_it; it += check_every) {
+      if (it1(check_every)) return -1;
+      if (ksp_read_state(C)) return -1;
+      if (g_state_host->done) break;
+    }
+  }
+  if (!g_state_host->done) OX_FAIL("ox_ksp_solve_mg: device state never reported completion");
+  result->reason[0] = g_state_host->reason[0];
+  result->its[0] = g_state_host->its[0];
+  result->rnorm[0] = g_state_host->rn[0];
+  result->bnorm[0] = g_state_host->bn[0];
+  return 0;
+}
+
 extern "C" int ox_ksp_options_default(ox_ksp_options *o) {
   if (!o) OX_FAIL("ox_ksp_options_default: null argument");
   memset(o, 0, sizeof(*o));

@@ -6,7 +6,11 @@ Option mapping (PETSc string keys, as the reference passes them):
             symmetric else BiCGStab;  preonly (+ pc_type lu/cholesky) -> the same Krylov
             method run to ``direct_rtol`` (there is no sparse LU on the device; the converged
             reason reported is KSP_CONVERGED_ITS = 4 as PETSc's preonly does)
-  pc_type   jacobi; none (PETSc's PCNONE: the identity -- dinv = 1 through the same kernels).  Anything else (ilu,
+  pc_type   jacobi; none (PETSc's PCNONE: the identity -- dinv = 1 through the same kernels); gamg (smoothed-aggregation
+            AMG, oasisx_amd/amg.py: a V-cycle with Chebyshev-Jacobi smoothers preconditions CG) with ksp_type cg on ONE
+            column of an operator that is not mesh-partitioned, with its options pc_gamg_threshold,
+            pc_gamg_agg_nsmooths, pc_gamg_coarse_eq_limit, pc_mg_levels and mg_levels_ksp_max_it; gamg anywhere else
+            (BiCGStab, several columns, partitioned operators, preonly) runs jacobi and says so.  Anything else (ilu,
             hypre, gamg, ...; lu/cholesky outside preonly) runs as jacobi AND SAYS SO: every option this path cannot
             honour -- another preconditioner, an unknown Krylov type, a key it does not know -- is reported once per
             solver with a warning on the ``oasisx`` logger (the reference forwards any key to PETSc, ksp.py:38-53)
@@ -85,6 +89,8 @@ HONOURED_KEYS = ("ksp_type", "pc_type", "ksp_rtol", "ksp_atol", "ksp_divtol", "k
 # keys the reference itself sets next to a direct solver (fracstep.py:565-570): they configure MUMPS, which the Krylov
 # stand-in has no use for -- accepted silently with ksp_type=preonly
 DIRECT_ONLY_KEYS = ("pc_factor_mat_solver_type", "mat_mumps_icntl_24", "mat_mumps_icntl_25")
+# options of pc_type gamg (oasisx_amd/amg.py): accepted silently next to it
+GAMG_KEYS = ("pc_gamg_threshold", "pc_gamg_agg_nsmooths", "pc_gamg_coarse_eq_limit", "pc_mg_levels", "mg_levels_ksp_max_it")
 
 
 class KSPSolver:
@@ -101,6 +107,8 @@ class KSPSolver:
         self._every = {}
         self._env_fold = _env_int("OX_CG_FOLD_BLOCKS", -1)
         self._env_ahead = _env_int("OX_KSP_RUN_AHEAD", -1)
+        self._mg = None  # amg.Hierarchy of pc_type gamg, cached on the operator's values (see _hierarchy)
+        self._mg_key = None
         self.updateOptions({} if petsc_options is None else petsc_options)
 
     # -- reference surface --------------------------------------------------------------
@@ -108,7 +116,7 @@ class KSPSolver:
         """Update options (reference ksp.py:38-53)."""
         self._options.update({str(k): v for k, v in options.items()})
 
-    def _audit_options(self):
+    def _audit_options(self, nc: int = 1):
         """Warn -- once per solver and (key, value) -- about every option that is remapped or ignored."""
         log = logging.getLogger("oasisx")
         seen = self.__dict__.setdefault("_warned", set())
@@ -135,14 +143,42 @@ class KSPSolver:
         if pc == "":
             if not direct:
                 warn("pc_type", "pc_type unset (PETSc's default: ilu / bjacobi): runs jacobi", logging.INFO)
-        elif pc not in ("jacobi", "none") and not (direct and pc in ("lu", "cholesky")):
+        elif pc == "gamg" and not self._gamg(nc):
+            warn("pc_type", f"pc_type=gamg is available with ksp_type=cg on one column of an operator that is not "
+                            f"mesh-partitioned only (here: ksp_type={kt or 'unset'}, {nc} column(s)"
+                            f"{', partitioned' if self._A is not None and self._A.pattern.dist is not None else ''}): "
+                            f"runs jacobi")
+        elif pc not in ("jacobi", "none", "gamg") and not (direct and pc in ("lu", "cholesky")):
             warn("pc_type", f"pc_type={pc} is not available on the device: runs jacobi")
         elif pc == "none" and direct:
             warn("pc_type", "pc_type=none with ksp_type=preonly solves nothing in PETSc; runs the Krylov stand-in")
         for k in o:
-            if k in HONOURED_KEYS or (direct and k in DIRECT_ONLY_KEYS):
+            if k in HONOURED_KEYS or (direct and k in DIRECT_ONLY_KEYS) or (pc == "gamg" and k in GAMG_KEYS):
                 continue
             warn(k, f"option {k}={o[k]!r} is not known to this path and is ignored")
+
+    def _gamg(self, nc: int = 1) -> bool:
+        """pc_type gamg honoured: ksp_type cg, one column, one GPU (everything else runs jacobi, with a warning)."""
+        o = self._options
+        return (str(o.get("pc_type", "")).lower() == "gamg" and str(o.get("ksp_type", "")).lower() == "cg" and nc == 1
+                and self._A is not None and self._A.pattern.dist is None)
+
+    def _hierarchy(self):
+        """The AMG hierarchy of the current operator, built once per set of values (A.version, as the Jacobi diagonal)
+        and per storage of the fine level (its ox_sell is copied into the hierarchy)."""
+        from .amg import Hierarchy
+
+        A = self._A
+        A.ref()  # (drops value codes that no longer describe the values: the hierarchy copies the storage as it is)
+        gopts = {k: self._options[k] for k in GAMG_KEYS if k in self._options}
+        key = (id(A), A.version, bytes(A.struct), tuple(sorted((k, str(v)) for k, v in gopts.items())))
+        if self._mg is None or self._mg_key != key:
+            self._mg = None
+            self._mg = Hierarchy(A, gopts)
+            self._mg_key = key
+            logging.getLogger("oasisx").info("KSPSolver[%s]: gamg hierarchy %s rows, set-up %.2f s", self._prefix,
+                                             self._mg.rows, self._mg.setup_s)
+        return self._mg
 
     def _pc_none(self) -> bool:
         return str(self._options.get("pc_type", "")).lower() == "none" and \
@@ -255,6 +291,8 @@ class KSPSolver:
         if self._A is None:
             return 5
         meth = self._method()[0]
+        if self._gamg(1):
+            return int(self._hierarchy().kernels_per_cycle()) + 6
         if meth in (_lib.KSP_CG, _lib.KSP_CG_SINGLE) and self._cg_merged():
             meth = _lib.KSP_CG_MERGED
         every = self.check_every or self._every.get((1, meth)) or self._interval_for(1, meth)
@@ -271,6 +309,8 @@ class KSPSolver:
         lib = _lib.load()
         A = self._A
         nc = X.nc
+        if self._gamg(nc):
+            return self._solve_gamg(B, X, ax0)
         meth, rtol, atol, max_it, direct = self._method()
         if meth in (_lib.KSP_CG, _lib.KSP_CG_SINGLE) and nc == 1 and self._cg_merged():
             meth = _lib.KSP_CG_MERGED
@@ -280,7 +320,7 @@ class KSPSolver:
         if self._dinv is None or self._dinv.shape[0] != A.pattern.n_rows:
             self._dinv = torch.empty(A.pattern.n_rows, dtype=torch.float64, device=dev)
             self._dinv_version = -1
-        self._audit_options()
+        self._audit_options(nc)
         pc_key = (A.version, self._pc_none())
         if self._dinv_version != pc_key:
             if pc_key[1]:  # pc_type none: the identity through the same kernels
@@ -339,12 +379,49 @@ class KSPSolver:
             raise KSPConvergenceError(self._prefix, reasons, [int(res.its[c]) for c in range(nc)])
         return reasons
 
+    def _solve_gamg(self, B: FieldStorage, X: FieldStorage, ax0):
+        """One-column CG preconditioned by the AMG V-cycle (ox_ksp_solve_mg)."""
+        lib = _lib.load()
+        A = self._A
+        self._audit_options(1)
+        mg = self._hierarchy()
+        o = self._options
+        rtol, atol, max_it = float(o.get("ksp_rtol", 1e-5)), float(o.get("ksp_atol", 1e-50)), int(o.get("ksp_max_it", 10000))
+        guess = bool(o.get("ksp_initial_guess_nonzero", False))
+        need = lib.ox_ksp_work_bytes_for(A.ref(), 1, _lib.KSP_CG_MG)
+        if self._work is None or self._work.shape[0] < need:
+            self._work = torch.empty(int(need), dtype=torch.uint8, device=X.dev().device)
+        key = (1, _lib.KSP_CG_MG)
+        if key not in self._every:
+            self._every[key] = self._interval_for(1, _lib.KSP_CG_MG)
+        every = self.check_every or self._every[key]
+        opt = _lib.ox_ksp_options()
+        _lib.check(lib.ox_ksp_options_default(C.byref(opt)), "ox_ksp_options_default")
+        opt.rtol, opt.atol, opt.max_it = rtol, atol, max_it
+        opt.divtol = float(o.get("ksp_divtol", 1e4))
+        opt.nonzero_guess, opt.check_every = int(guess), int(every)
+        opt.run_ahead = self._run_ahead()
+        opt.ax0 = ax0.ptr() if (ax0 is not None and guess) else None
+        res = _lib.ox_ksp_result()
+        _lib.check(lib.ox_ksp_solve_mg(mg.handle, A.ref(), B.ptr(), X.ptr(), C.byref(opt), _lib.ptr(self._work),
+                                       int(self._work.shape[0]), C.byref(res), _lib.current_stream()), "ox_ksp_solve_mg")
+        self.last_result = res
+        reasons = [int(res.reason[0])]
+        if _truthy(o.get("ksp_error_if_not_converged", False)) and reasons[0] <= 0:
+            raise KSPConvergenceError(self._prefix, reasons, [int(res.its[0])])
+        return reasons
+
     def _interval_for(self, nc: int, meth: int) -> int:
         # from the matrix size alone (bytes per iteration at ~4 TB/s + launch latencies), NOT from a measured time:
         # with several columns the interval decides at which iteration a solve narrows to its last live column,
         # the 1-column kernels sum their dot products in another order than the NC-column ones, and a schedule
         # that followed timing noise made the last bits of a step differ from run to run (round 4: seen as 1e-15
         # differences between identical runs at sizes where an iteration takes about the 60 us of the threshold)
+        if meth == _lib.KSP_CG_MG:
+            # from the cycle itself: its bytes at ~4 TB/s, ~4 us per launch, plus the CG part of the iteration
+            mg = self._hierarchy()
+            t_iter = mg.cycle_bytes() / 4.0e12 + 4e-6 * mg.kernels_per_cycle() + 10.0 * self._A.pattern.nnz / 4.0e12 + 25e-6
+            return self._check_interval(nc, t_iter)
         t_iter = (2 if meth in (_lib.KSP_BCGS, _lib.KSP_BCGS_MERGED) else 1) * 10.0 * self._A.pattern.nnz / 4.0e12 + 25e-6
         return self._check_interval(nc, t_iter)
 
