@@ -616,6 +616,13 @@ int ox_mg_kernels_per_cycle(const ox_mg *mg);
  * opt->dinv_code is ignored. */
 int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt, void *work,
                     size_t work_bytes, ox_ksp_result *result, void *stream);
+/* The same CG on a mesh-partitioned operator (PETSc's pc_type bjacobi + sub_pc_type gamg, one block per rank): `mg` is the
+ * hierarchy of the rank's owned-by-owned block (n_owned rows, ghost columns dropped; nullptr on a rank that owns no rows),
+ * applied without communication; A (n_owned x n_local) is the partitioned operator.  Per iteration one halo exchange (the
+ * mat-vec refreshes the ghosts of p) and two all-reduces; dot products over the owned rows.  x's ghosts are NOT refreshed
+ * at the end (ox_halo_forward).  A timed-out peer fails the solve (ox_dist_status). */
+int ox_ksp_solve_mg_dist(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
+                         void *work, size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, void *stream);
 
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */

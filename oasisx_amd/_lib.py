@@ -286,6 +286,8 @@ SIGNATURES = {
     "ox_mg_kernels_per_cycle": (_I, [_P]),
     "ox_ksp_solve_mg": (_I, [_P, C.POINTER(ox_sell), _P, _P, C.POINTER(ox_ksp_options), _P, C.c_size_t,
                              C.POINTER(ox_ksp_result), _P]),
+    "ox_ksp_solve_mg_dist": (_I, [_P, C.POINTER(ox_sell), _P, _P, C.POINTER(ox_ksp_options), _P, C.c_size_t,
+                                  C.POINTER(ox_ksp_result), _P, _P]),
     "ox_profile_begin": (_I, [_I, _I]),
     "ox_profile_end": (_I, []),
     "ox_profile_get": (_I, [_I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_D)]),

@@ -15,6 +15,12 @@ The hierarchy is built on the host from the operator's scipy copy (``SellMatrix.
   * every other level is smoothed by Chebyshev-Jacobi of degree mg_levels_ksp_max_it on [0.1, 1.1] lambda_max (PETSc
     GAMG's smoother defaults); lambda_max(D^-1 A) comes from a Lanczos estimate with a fixed start vector.
 
+On a mesh-partitioned operator (PETSc's ``pc_type bjacobi`` + ``sub_pc_type gamg``: one block per rank) the hierarchy
+is built the same way from the rank's owned-by-owned block ``A_rr`` (``owned_block``: rows and columns < n_owned, ghost
+columns dropped), with a level-0 matrix of its own (``Hierarchy(..., block=True)``).  On two ranks or more that block of
+a pure-Neumann operator is SPD -- a principal submatrix of a matrix whose null space is the constants --, so the
+row-sum test finds it nonsingular and the coarse inverse is not projected.
+
 The device side (``csrc/ox_amg.hip``) runs a symmetric V-cycle -- the same Chebyshev polynomial before and after the
 coarse correction, R = P^T -- so that it is a valid CG preconditioner.  ``Hierarchy.vcycle_numpy`` is the same cycle in
 numpy (tests).
@@ -30,7 +36,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["Hierarchy", "build_levels", "vcycle_numpy"]
+__all__ = ["Hierarchy", "build_levels", "owned_block", "vcycle_numpy"]
 
 DEFAULTS = {"pc_gamg_threshold": 0.0, "pc_gamg_agg_nsmooths": 1, "pc_gamg_coarse_eq_limit": 50, "pc_mg_levels": 10,
             "mg_levels_ksp_max_it": 2}
@@ -174,6 +180,16 @@ def _coarse_inverse(A: sp.csr_matrix, singular: bool, scale: float = 0.0) -> np.
     return 0.5 * (inv + inv.T)
 
 
+def owned_block(M: sp.spmatrix) -> sp.csr_matrix:
+    """The owned-by-owned block of a rank's rows: ``M`` is (n_owned, n_local) with the owned columns first (a partitioned
+    ``SellMatrix.to_scipy()``); the ghost columns (>= n_owned) are dropped."""
+    M = sp.csr_matrix(M)
+    n = M.shape[0]
+    if M.shape[1] < n:
+        raise ValueError(f"amg: a block of {M.shape[0]} x {M.shape[1]} has fewer columns than rows")
+    return sp.csr_matrix(M[:, :n])
+
+
 class Level:
     def __init__(self, A, dinv, P=None, R=None, cheb=None, lmax=None, agg=None):
         self.A, self.dinv, self.P, self.R, self.cheb, self.lmax, self.agg = A, dinv, P, R, cheb, lmax, agg
@@ -280,13 +296,25 @@ class _DevMat:
 class Hierarchy:
     """Host levels + their device copies + the library's ``ox_mg`` handle."""
 
-    def __init__(self, A, options: dict | None = None, tail_rows: int = 0):
+    def __init__(self, A, options: dict | None = None, tail_rows: int = 0, block: bool = False):
         """``A``: the fine-level ``la.SellMatrix`` (its own storage -- value dictionary, pair slots, windows -- stays in
-        use on the fine level)."""
+        use on the fine level).  ``block``: the hierarchy of ``owned_block(A)`` (a mesh-partitioned operator: the
+        rank's block of pc_type bjacobi), whose level 0 is a plain-f64 copy of that block: the cycle's fine-level
+        vectors have n_owned entries and no mat-vec of the cycle reads a ghost column.  A block of no rows has no
+        device hierarchy (``handle`` None)."""
         t0 = time.perf_counter()
         self.A = A
+        self.block = bool(block)
         dev = A.vals.device
-        self.levels = build_levels(A.to_scipy(), options)
+        M = A.to_scipy()
+        if self.block:
+            M = owned_block(M)
+            if M.shape[0] == 0:
+                self.levels, self.handle, self._keep = [], None, []
+                self.setup_host_s = self.setup_s = time.perf_counter() - t0
+                self.nnz, self.rows = [], []
+                return
+        self.levels = build_levels(M, options)
         self.setup_host_s = time.perf_counter() - t0
         lib = _lib.load()
         L = len(self.levels)
@@ -297,7 +325,7 @@ class Hierarchy:
             self._keep.append(dinv)
             arr[i].dinv = dinv.data_ptr()
             arr[i].n_rows = lev.A.shape[0]
-            if i == 0:
+            if i == 0 and not self.block:
                 arr[i].A = A.struct
             elif i < L - 1:
                 m = _DevMat(lev.A, dev)
@@ -331,7 +359,7 @@ class Hierarchy:
             self.handle = None
 
     def kernels_per_cycle(self) -> int:
-        return int(_lib.load().ox_mg_kernels_per_cycle(self.handle))
+        return int(_lib.load().ox_mg_kernels_per_cycle(self.handle)) if self.handle is not None else 0
 
     def apply(self, r: torch.Tensor, z: torch.Tensor):
         """z = B r (one V-cycle) on device vectors of the fine level's rows."""

@@ -383,6 +383,7 @@ extern "C" int ox_mg_destroy(ox_mg *mg) {
 }
 
 extern "C" int ox_mg_kernels_per_cycle(const ox_mg *mg) { return mg ? mg->kernels : -1; }
+int64_t ox_mg_fine_rows(const ox_mg *mg) { return mg ? mg->lv[0].n_rows : -1; }
 
 // z = B r on `st`; every kernel is a no-op once *done (nullptr: always runs).  (Used by ox_ksp_solve_mg.)
 int ox_mg_vcycle(const ox_mg *mg, const double *r, double *z, const int *done, hipStream_t st) {

@@ -142,3 +142,5 @@ void ox_prof_stop(hipStream_t st);
 
 // one V-cycle of an AMG hierarchy (ox_amg.hip): z = B r; every kernel a no-op once *done (nullptr: none)
 int ox_mg_vcycle(const ox_mg *mg, const double *r, double *z, const int *done, hipStream_t st);
+// rows of the hierarchy's fine level
+int64_t ox_mg_fine_rows(const ox_mg *mg);

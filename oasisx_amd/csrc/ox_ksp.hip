@@ -1732,10 +1732,13 @@ static int ksp_run(int ksp_type, const ox_sell *A, const double *dinv, const dou
 }
 
 // ---------------------------------------------------------------------------------------
-// CG preconditioned by an AMG V-cycle (PETSc's KSPCG + PCGAMG; ox_amg.hip), one column, one GPU.  z = B r is stored (the
+// CG preconditioned by an AMG V-cycle (PETSc's KSPCG + PCGAMG; ox_amg.hip), one column.  z = B r is stored (the
 // preconditioner is not a diagonal the update kernels could apply on the fly); the synchronisation points, the state and
 // the run-ahead batches are those of the Jacobi CG (PH_CG_INIT, PH_CG_A, PH_CG_B): the convergence test sees |z| = |B r|.
 // Per iteration:  q = A p (+ p.q);  point A;  x += alpha p, r -= alpha q;  z = B r;  {r.z, z.z};  point B;  p = z + beta p.
+// On a mesh-partitioned operator (ox_ksp_solve_mg_dist: PETSc's pc_type bjacobi + sub_pc_type gamg) B is the V-cycle of
+// the rank's owned-by-owned block -- no communication inside it --, the mat-vec refreshes the ghosts of p (one halo
+// exchange), the dot products run over the owned rows and both points all-reduce.
 // ---------------------------------------------------------------------------------------
 // r = b - q (q = A x0) or r = b, x = 0
 __global__ __launch_bounds__(256) void k_mgcg_init(int64_t n, const double *__restrict__ b, double *x,
@@ -1793,26 +1796,30 @@ static int mgcg_iterations(const ox_mg *mg, const KspCtx &C, const KspVecs &V, c
   const int64_t n = C.A->n_rows;
   const int *done = &C.S->done;
   for (int k = 0; k < count; ++k) {
-    if (ox_spmv_dist(C.A, V.p, V.q, 1, OX_EPI_DOT, nullptr, nullptr, C.partial, done, nullptr, C.st)) return -1;
+    if (ox_spmv_dist(C.A, V.p, V.q, 1, OX_EPI_DOT, nullptr, nullptr, C.partial, done, C.dist, C.st)) return -1;
     KSP_SYNC(PH_CG_A, C.partial, C.nbs, 1);
     hipLaunchKernelGGL(k_mgcg_update1, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.x, V.r, V.p, V.q);
     OX_LAUNCH_CHECK();
-    if (ox_mg_vcycle(mg, V.r, V.z, done, C.st)) return -1;
+    if (mg && ox_mg_vcycle(mg, V.r, V.z, done, C.st)) return -1;  // (no hierarchy: a rank that owns no rows)
     hipLaunchKernelGGL(k_mgcg_dots<false>, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.r, V.z, nullptr, nullptr, C.partial);
     OX_LAUNCH_CHECK();
-    if (ksp_sync_point<PH_CG_B>(C.S, C.partial, C.nb, 2, C.sums, ksp_last_point(P, k, count), nullptr, C.st)) return -1;
+    if (ksp_sync_point<PH_CG_B>(C.S, C.partial, C.nb, 2, C.sums, ksp_last_point(P, k, count), C.dist, C.st)) return -1;
     hipLaunchKernelGGL(k_mgcg_update2, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.z, V.p);
     OX_LAUNCH_CHECK();
   }
   return 0;
 }
 
-extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
-                               void *work, size_t work_bytes, ox_ksp_result *result, void *stream) {
-  if (!mg || !A || !b || !x || !work || !result || !opt) OX_FAIL("ox_ksp_solve_mg: null argument");
+// dist: nullptr on one GPU (ox_ksp_solve_mg); mg: nullptr only on a rank that owns no rows (it still takes part in
+// every exchange and all-reduce)
+static int mgcg_solve(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt, void *work,
+                      size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, hipStream_t st) {
   if (work_bytes < ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG))
     OX_FAIL("ox_ksp_solve_mg: workspace too small (%zu < %zu)", work_bytes, ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG));
   if (!(opt->divtol > 0.0)) OX_FAIL("ox_ksp_solve_mg: divtol=%g (must be positive; PETSc's default is 1e4)", opt->divtol);
+  if (mg && ox_mg_fine_rows(mg) != A->n_rows)  // (the cycle's fine-level vectors have the hierarchy's rows)
+    OX_FAIL("ox_ksp_solve_mg: hierarchy of %lld fine rows for an operator of %lld rows", (long long)ox_mg_fine_rows(mg),
+            (long long)A->n_rows);
   memset(result, 0, sizeof(*result));
   KspParams P{};
   P.rtol = opt->rtol;
@@ -1825,7 +1832,6 @@ extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *
   const int check_every = opt->check_every < 1 ? 1 : opt->check_every;
   const int guess = opt->nonzero_guess;
   const bool ahead = opt->run_ahead != 0;
-  hipStream_t st = ox_stream(stream);
   const int64_t n = A->n_rows;
   char *work_c = static_cast<char *>(work);
   const KspLayout L = ksp_layout(A->n_rows, A->n_cols, 1, OX_KSP_CG_MG, ksp_grid_max(A));
@@ -1836,9 +1842,10 @@ extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *
   C.sums = reinterpret_cast<double *>(work_c + L.sums);
   C.partial = reinterpret_cast<double *>(work_c + L.partial);
   C.partial2 = reinterpret_cast<double *>(work_c + L.partial2);
+  C.dist = dist;
   C.st = st;
   C.nb = ox_vec_blocks(2 * (n > 0 ? n : 1));
-  C.nbs = ox_spmv_dist_nparts(A, nullptr, 1);
+  C.nbs = ox_spmv_dist_nparts(A, dist, 1);
   double *vec[6];
   for (int i = 0; i < 6; ++i) vec[i] = reinterpret_cast<double *>(work_c + L.vec0 + L.vec_stride * i);
   if (!g_state_host) OX_HIP(hipHostMalloc(&g_state_host, 3 * sizeof(KspState)));
@@ -1846,12 +1853,12 @@ extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *
   V.x = x, V.r = vec[0], V.z = vec[1], V.p = vec[2], V.q = vec[3];
   double *zb = vec[4];  // B b (nonzero initial guess: the norm the relative test uses)
   if (guess && !opt->ax0) {
-    if (ox_spmv_dist(A, x, V.q, 1, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, nullptr, st)) return -1;
+    if (ox_spmv_dist(A, x, V.q, 1, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
   }
   hipLaunchKernelGGL(k_mgcg_init, dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && opt->ax0) ? opt->ax0 : V.q, V.r, guess);
   OX_LAUNCH_CHECK();
-  if (guess && ox_mg_vcycle(mg, b, zb, nullptr, st)) return -1;
-  if (ox_mg_vcycle(mg, V.r, V.z, nullptr, st)) return -1;
+  if (mg && guess && ox_mg_vcycle(mg, b, zb, nullptr, st)) return -1;
+  if (mg && ox_mg_vcycle(mg, V.r, V.z, nullptr, st)) return -1;
   hipLaunchKernelGGL(k_mgcg_dots<true>, dim3(C.nb), dim3(256), 0, st, n, C.S, V.r, V.z, guess ? zb : V.z, V.p, C.partial);
   OX_LAUNCH_CHECK();
   KSP_SYNC(PH_CG_INIT, C.partial, C.nb, 3);
@@ -1872,6 +1879,20 @@ extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *
   result->rnorm[0] = g_state_host->rn[0];
   result->bnorm[0] = g_state_host->bn[0];
   return 0;
+}
+
+extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
+                               void *work, size_t work_bytes, ox_ksp_result *result, void *stream) {
+  if (!mg || !A || !b || !x || !work || !result || !opt) OX_FAIL("ox_ksp_solve_mg: null argument");
+  return mgcg_solve(mg, A, b, x, opt, work, work_bytes, result, nullptr, ox_stream(stream));
+}
+
+extern "C" int ox_ksp_solve_mg_dist(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
+                                    void *work, size_t work_bytes, ox_ksp_result *result, const ox_dist *dist,
+                                    void *stream) {
+  if (!A || !b || !x || !work || !result || !opt || !dist) OX_FAIL("ox_ksp_solve_mg_dist: null argument");
+  if (!mg && A->n_rows > 0) OX_FAIL("ox_ksp_solve_mg_dist: no hierarchy for %lld owned rows", (long long)A->n_rows);
+  return mgcg_solve(mg, A, b, x, opt, work, work_bytes, result, dist, ox_stream(stream));
 }
 
 extern "C" int ox_ksp_options_default(ox_ksp_options *o) {

@@ -10,7 +10,14 @@ Option mapping (PETSc string keys, as the reference passes them):
             AMG, oasisx_amd/amg.py: a V-cycle with Chebyshev-Jacobi smoothers preconditions CG) with ksp_type cg on ONE
             column of an operator that is not mesh-partitioned, with its options pc_gamg_threshold,
             pc_gamg_agg_nsmooths, pc_gamg_coarse_eq_limit, pc_mg_levels and mg_levels_ksp_max_it; gamg anywhere else
-            (BiCGStab, several columns, partitioned operators, preonly) runs jacobi and says so.  Anything else (ilu,
+            (BiCGStab, several columns, partitioned operators, preonly) runs jacobi and says so;
+            bjacobi (PETSc's block Jacobi, one block per rank) with sub_pc_type gamg and ksp_type cg on one column: every
+            rank applies one V-cycle of the hierarchy of its owned-by-owned block (no communication inside the
+            preconditioner; on one GPU the one block is the operator: exactly pc_type gamg), with the sub_-prefixed gamg
+            options; sub_ksp_type preonly (PETSc's default) is accepted; bjacobi with sub_pc_type jacobi / none is
+            exactly jacobi / none and runs that path; any other sub_pc_type (unset: PETSc's ilu), another ksp_type or
+            several columns run jacobi and say so; a pc_bjacobi_blocks other than the rank count or a sub_ksp_type other
+            than preonly is reported and still runs one block per rank and one V-cycle.  Anything else (ilu,
             hypre, gamg, ...; lu/cholesky outside preonly) runs as jacobi AND SAYS SO: every option this path cannot
             honour -- another preconditioner, an unknown Krylov type, a key it does not know -- is reported once per
             solver with a warning on the ``oasisx`` logger (the reference forwards any key to PETSc, ksp.py:38-53)
@@ -91,6 +98,9 @@ HONOURED_KEYS = ("ksp_type", "pc_type", "ksp_rtol", "ksp_atol", "ksp_divtol", "k
 DIRECT_ONLY_KEYS = ("pc_factor_mat_solver_type", "mat_mumps_icntl_24", "mat_mumps_icntl_25")
 # options of pc_type gamg (oasisx_amd/amg.py): accepted silently next to it
 GAMG_KEYS = ("pc_gamg_threshold", "pc_gamg_agg_nsmooths", "pc_gamg_coarse_eq_limit", "pc_mg_levels", "mg_levels_ksp_max_it")
+# pc_type bjacobi: its own keys, and the sub_-prefixed gamg options of its blocks (sub_pc_type gamg)
+BJACOBI_KEYS = ("sub_pc_type", "sub_ksp_type", "pc_bjacobi_blocks")
+SUB_GAMG_KEYS = tuple("sub_" + k for k in GAMG_KEYS)
 
 
 class KSPSolver:
@@ -144,16 +154,44 @@ class KSPSolver:
             if not direct:
                 warn("pc_type", "pc_type unset (PETSc's default: ilu / bjacobi): runs jacobi", logging.INFO)
         elif pc == "gamg" and not self._gamg(nc):
+            part = self._A is not None and self._A.pattern.dist is not None
             warn("pc_type", f"pc_type=gamg is available with ksp_type=cg on one column of an operator that is not "
                             f"mesh-partitioned only (here: ksp_type={kt or 'unset'}, {nc} column(s)"
-                            f"{', partitioned' if self._A is not None and self._A.pattern.dist is not None else ''}): "
-                            f"runs jacobi")
+                            f"{', partitioned' if part else ''}): runs jacobi"
+                            f"{' (use pc_type bjacobi with sub_pc_type gamg)' if part else ''}")
+        elif pc == "bjacobi" and not direct:
+            sub = self._sub_pc()
+            if sub == "":
+                warn("sub_pc_type", "pc_type=bjacobi with sub_pc_type unset (PETSc's default: ilu): runs jacobi")
+            elif sub == "gamg":
+                if not self._bjacobi_gamg(nc):
+                    warn("sub_pc_type", f"pc_type=bjacobi with sub_pc_type=gamg is available with ksp_type=cg on one "
+                                        f"column only (here: ksp_type={kt or 'unset'}, {nc} column(s)): runs jacobi")
+                else:
+                    nb = o.get("pc_bjacobi_blocks")
+                    nr = self._nranks()
+                    if nb is not None and str(nb) != str(nr):
+                        warn("pc_bjacobi_blocks", f"pc_bjacobi_blocks={nb}: runs one block per rank ({nr})")
+                    skt = str(o.get("sub_ksp_type", "preonly")).lower()
+                    if skt != "preonly":
+                        warn("sub_ksp_type", f"sub_ksp_type={skt} is not available: runs preonly (one V-cycle per block)")
+            elif sub in ("jacobi", "none"):
+                # (point Jacobi / the identity is the same preconditioner for any blocking: pc_bjacobi_blocks holds as
+                # given; an inner Krylov solve per block does not exist on this path)
+                skt = str(o.get("sub_ksp_type", "preonly")).lower()
+                if skt != "preonly":
+                    warn("sub_ksp_type", f"sub_ksp_type={skt} is not available: runs preonly (pc_type {sub} on the "
+                                         f"whole operator)")
+            else:
+                warn("sub_pc_type", f"pc_type=bjacobi with sub_pc_type={sub} is not available on the device: runs jacobi")
         elif pc not in ("jacobi", "none", "gamg") and not (direct and pc in ("lu", "cholesky")):
             warn("pc_type", f"pc_type={pc} is not available on the device: runs jacobi")
         elif pc == "none" and direct:
             warn("pc_type", "pc_type=none with ksp_type=preonly solves nothing in PETSc; runs the Krylov stand-in")
         for k in o:
             if k in HONOURED_KEYS or (direct and k in DIRECT_ONLY_KEYS) or (pc == "gamg" and k in GAMG_KEYS):
+                continue
+            if pc == "bjacobi" and not direct and (k in BJACOBI_KEYS or (self._sub_pc() == "gamg" and k in SUB_GAMG_KEYS)):
                 continue
             warn(k, f"option {k}={o[k]!r} is not known to this path and is ignored")
 
@@ -163,25 +201,48 @@ class KSPSolver:
         return (str(o.get("pc_type", "")).lower() == "gamg" and str(o.get("ksp_type", "")).lower() == "cg" and nc == 1
                 and self._A is not None and self._A.pattern.dist is None)
 
+    def _sub_pc(self) -> str:
+        return str(self._options.get("sub_pc_type", "")).lower()
+
+    def _bjacobi_gamg(self, nc: int = 1) -> bool:
+        """pc_type bjacobi + sub_pc_type gamg honoured: ksp_type cg, one column (one block per rank, one V-cycle of the
+        rank's owned-by-owned block; on one GPU the one block is the operator: the pc_type gamg path)."""
+        o = self._options
+        return (str(o.get("pc_type", "")).lower() == "bjacobi" and self._sub_pc() == "gamg"
+                and str(o.get("ksp_type", "")).lower() == "cg" and nc == 1 and self._A is not None)
+
+    def _nranks(self) -> int:
+        if self._A is None or self._A.pattern.dist is None:
+            return 1
+        return int(getattr(self._comm, "size", 1))
+
     def _hierarchy(self):
         """The AMG hierarchy of the current operator, built once per set of values (A.version, as the Jacobi diagonal)
-        and per storage of the fine level (its ox_sell is copied into the hierarchy)."""
+        and per storage of the fine level (its ox_sell is copied into the hierarchy).  pc_type bjacobi on a
+        mesh-partitioned operator: the hierarchy of the rank's owned-by-owned block (amg.owned_block), with the
+        sub_-prefixed options; on one GPU the block is the operator itself and the hierarchy is pc_type gamg's."""
         from .amg import Hierarchy
 
         A = self._A
         A.ref()  # (drops value codes that no longer describe the values: the hierarchy copies the storage as it is)
-        gopts = {k: self._options[k] for k in GAMG_KEYS if k in self._options}
-        key = (id(A), A.version, bytes(A.struct), tuple(sorted((k, str(v)) for k, v in gopts.items())))
+        if str(self._options.get("pc_type", "")).lower() == "bjacobi":
+            gopts = {k[4:]: self._options[k] for k in SUB_GAMG_KEYS if k in self._options}
+            block = A.pattern.dist is not None
+        else:
+            gopts = {k: self._options[k] for k in GAMG_KEYS if k in self._options}
+            block = False
+        key = (id(A), A.version, bytes(A.struct), block, tuple(sorted((k, str(v)) for k, v in gopts.items())))
         if self._mg is None or self._mg_key != key:
             self._mg = None
-            self._mg = Hierarchy(A, gopts)
+            self._mg = Hierarchy(A, gopts, block=block)
             self._mg_key = key
-            logging.getLogger("oasisx").info("KSPSolver[%s]: gamg hierarchy %s rows, set-up %.2f s", self._prefix,
-                                             self._mg.rows, self._mg.setup_s)
+            logging.getLogger("oasisx").info("KSPSolver[%s]: %s hierarchy %s rows, set-up %.2f s", self._prefix,
+                                             "bjacobi block gamg" if block else "gamg", self._mg.rows, self._mg.setup_s)
         return self._mg
 
     def _pc_none(self) -> bool:
-        return str(self._options.get("pc_type", "")).lower() == "none" and \
+        pc = str(self._options.get("pc_type", "")).lower()
+        return (pc == "none" or (pc == "bjacobi" and self._sub_pc() == "none")) and \
             str(self._options.get("ksp_type", "")).lower() != "preonly"
 
     def setOptions(self, op):
@@ -291,7 +352,9 @@ class KSPSolver:
         if self._A is None:
             return 5
         meth = self._method()[0]
-        if self._gamg(1):
+        if self._gamg(1) or self._bjacobi_gamg(1):
+            # mat-vec (a partitioned one: its halo exchange and split launches not counted), two points, three vector
+            # kernels, and the V-cycle (of the rank's block on a partitioned operator)
             return int(self._hierarchy().kernels_per_cycle()) + 6
         if meth in (_lib.KSP_CG, _lib.KSP_CG_SINGLE) and self._cg_merged():
             meth = _lib.KSP_CG_MERGED
@@ -309,7 +372,7 @@ class KSPSolver:
         lib = _lib.load()
         A = self._A
         nc = X.nc
-        if self._gamg(nc):
+        if self._gamg(nc) or self._bjacobi_gamg(nc):
             return self._solve_gamg(B, X, ax0)
         meth, rtol, atol, max_it, direct = self._method()
         if meth in (_lib.KSP_CG, _lib.KSP_CG_SINGLE) and nc == 1 and self._cg_merged():
@@ -380,7 +443,8 @@ class KSPSolver:
         return reasons
 
     def _solve_gamg(self, B: FieldStorage, X: FieldStorage, ax0):
-        """One-column CG preconditioned by the AMG V-cycle (ox_ksp_solve_mg)."""
+        """One-column CG preconditioned by the AMG V-cycle (ox_ksp_solve_mg); on a mesh-partitioned operator (pc_type
+        bjacobi + sub_pc_type gamg) by the V-cycle of the rank's block (ox_ksp_solve_mg_dist)."""
         lib = _lib.load()
         A = self._A
         self._audit_options(1)
@@ -403,8 +467,15 @@ class KSPSolver:
         opt.run_ahead = self._run_ahead()
         opt.ax0 = ax0.ptr() if (ax0 is not None and guess) else None
         res = _lib.ox_ksp_result()
-        _lib.check(lib.ox_ksp_solve_mg(mg.handle, A.ref(), B.ptr(), X.ptr(), C.byref(opt), _lib.ptr(self._work),
-                                       int(self._work.shape[0]), C.byref(res), _lib.current_stream()), "ox_ksp_solve_mg")
+        st = _lib.current_stream()
+        if A.pattern.dist is None:
+            _lib.check(lib.ox_ksp_solve_mg(mg.handle, A.ref(), B.ptr(), X.ptr(), C.byref(opt), _lib.ptr(self._work),
+                                           int(self._work.shape[0]), C.byref(res), st), "ox_ksp_solve_mg")
+        else:
+            _lib.check(lib.ox_ksp_solve_mg_dist(mg.handle, A.ref(), B.ptr(), X.ptr(), C.byref(opt), _lib.ptr(self._work),
+                                                int(self._work.shape[0]), C.byref(res), A.pattern.dist, st),
+                       "ox_ksp_solve_mg_dist")
+            _lib.check(lib.ox_halo_forward(A.pattern.dist, X.ptr(), 1, st), "ox_halo_forward")  # x.scatter_forward()
         self.last_result = res
         reasons = [int(res.reason[0])]
         if _truthy(o.get("ksp_error_if_not_converged", False)) and reasons[0] <= 0:
