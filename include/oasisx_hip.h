@@ -624,6 +624,28 @@ int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *
 int ox_ksp_solve_mg_dist(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
                          void *work, size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, void *stream);
 
+/* ---- Projected initial guesses (PETSc's -ksp_guess_type fischer) for repeated CG solves on one operator (ox_guess.hip)
+ * Per column of an interleaved (n_rows x ncomp) block the object keeps k <= size A-orthonormal directions x~_j (model 1
+ * also A x~_j; model 2 only x~_j) in device memory it owns.  n_rows: local rows (owned + ghost), n_owned: the operator's
+ * rows; dot products run over the owned rows and are all-reduced on a partitioned operator (dist != NULL).  Nothing is
+ * read back by the host: every call is stream-ordered on `stream`.
+ *   ox_guess_form:   k = 0: nothing (*ax0_out = NULL).  Otherwise x <- x_w + sum_j x~_j (x~_j . (b - A x_w)) on all
+ *                    local rows, x_w = x if nonzero_guess else 0; A x_w is ax_w (device [n_owned][ncomp]) or, when NULL,
+ *                    one mat-vec.  Model 1: *ax0_out = A x (device, owned by the object) for ox_ksp_options.ax0.
+ *   ox_guess_update: after a converged solve whose initial guess ox_guess_form formed (x's ghosts refreshed): adds the
+ *                    A-orthonormalised d = x - x0 (d = x when k was 0); with k = size the basis restarts from x alone.
+ *                    A direction with d.A d <= 1e-20 of its value before the orthogonalisation (or either <= 0) is kept as
+ *                    a zero slot. */
+typedef struct ox_guess ox_guess;
+int ox_guess_create(int64_t n_rows, int64_t n_owned, int ncomp, int model, int size, ox_guess **out);
+int ox_guess_destroy(ox_guess *g);
+int ox_guess_reset(ox_guess *g);        /* k = 0 (the operator's values or layout changed) */
+int ox_guess_dim(const ox_guess *g);    /* the current k */
+size_t ox_guess_bytes(const ox_guess *g); /* device bytes of the basis (reporting) */
+int ox_guess_form(ox_guess *g, const ox_sell *A, const double *b, double *x, int nonzero_guess, const double *ax_w,
+                  const double **ax0_out, const ox_dist *dist, void *stream);
+int ox_guess_update(ox_guess *g, const ox_sell *A, const double *x, const ox_dist *dist, void *stream);
+
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */
 int ox_comm_create(const char *id128, int rank, int nranks, void **comm_out); /* ncclCommInitRank */

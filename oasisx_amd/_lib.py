@@ -288,6 +288,13 @@ SIGNATURES = {
                              C.POINTER(ox_ksp_result), _P]),
     "ox_ksp_solve_mg_dist": (_I, [_P, C.POINTER(ox_sell), _P, _P, C.POINTER(ox_ksp_options), _P, C.c_size_t,
                                   C.POINTER(ox_ksp_result), _P, _P]),
+    "ox_guess_create": (_I, [_L, _L, _I, _I, _I, C.POINTER(_P)]),
+    "ox_guess_destroy": (_I, [_P]),
+    "ox_guess_reset": (_I, [_P]),
+    "ox_guess_dim": (_I, [_P]),
+    "ox_guess_bytes": (C.c_size_t, [_P]),
+    "ox_guess_form": (_I, [_P, C.POINTER(ox_sell), _P, _P, _I, _P, C.POINTER(_P), _P, _P]),
+    "ox_guess_update": (_I, [_P, C.POINTER(ox_sell), _P, _P, _P]),
     "ox_profile_begin": (_I, [_I, _I]),
     "ox_profile_end": (_I, []),
     "ox_profile_get": (_I, [_I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_D)]),

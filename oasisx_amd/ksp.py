@@ -47,6 +47,26 @@ Option mapping (PETSc string keys, as the reference passes them):
             for an explicit "bcgs" (PETSc's KSPBCGS stops with DIVERGED_BREAKDOWN), 5 when the
             method stands in for a direct solver, which cannot break down (e.g. a cold start with
             identity-row Dirichlet conditions makes rho = 0 after one iteration)
+  ksp_guess_type fischer  PETSc's KSPGUESSFISCHER (P. Fischer, CMAME 163, 1998; csrc/ox_guess.hip): per column the solver
+            keeps k <= size A-orthonormal earlier solution directions x~_j and starts each solve from
+                x0 = x_w + sum_j x~_j (x~_j . (b - A x_w)),
+            x_w the caller's initial guess (0 unless ksp_initial_guess_nonzero): with x_w = 0 Fischer's projection,
+            with a warm start the warm start corrected by the A-orthogonal projection of its error -- never worse than
+            the warm start in the A-norm.  DEVIATION from PETSc, whose KSPGuessFormGuess overwrites x with the projection
+            and so discards a warm start (a CPU replay of the velocity update took more iterations that way than with the
+            warm start alone).  After a solve in which every column converged, d = x - x0 (d = x when
+            k was 0) is A-orthonormalised against the basis and added; with k = size the basis restarts from the latest
+            solution alone; a direction with d.A d <= 1e-20 of its value before the orthogonalisation (or either <= 0:
+            in the span, a constant of a singular operator, an operator that is not SPD) takes its slot as a zero vector.
+            A failed solve leaves the basis as it was.  The basis is dropped when the operator's values (A.version) or
+            layout change and on setOperators.  Honoured for every CG recurrence (standard, single- and merged-reduction,
+            pc_type jacobi / none / gamg / bjacobi + sub_pc_type gamg, 1-3 columns, one GPU or partitioned) on an
+            operator flagged symmetric; reported once and ignored for BiCGStab, a non-symmetric operator and preonly
+            (a direct solve takes no initial guess).  Another ksp_guess_type (pod, ...) is reported and ignored.
+  ksp_guess_fischer_model  "model,size" (PETSc's command line, e.g. "1,10") or a 2-sequence; default 1,10.  Model 1
+            also stores A x~_j (2 size vectors per column set) and hands A x0 to the solver (no extra mat-vec); model 2
+            stores x~_j only (size vectors) and the solver forms A x0.  Another model is reported and runs model 1; size
+            is clamped to 1..32 with a warning (32: this path's storage and register budget, not a PETSc limit).
 """
 from __future__ import annotations
 
@@ -92,7 +112,8 @@ CG_MERGED_MAX_ROWS = 1 << 20
 KRYLOV_TYPES = ("cg", "bcgs", "bicgstab", "ibcgs", "pipebcgs", "fbcgsr")
 HONOURED_KEYS = ("ksp_type", "pc_type", "ksp_rtol", "ksp_atol", "ksp_divtol", "ksp_max_it", "ksp_initial_guess_nonzero",
                  "ksp_error_if_not_converged", "ksp_cg_single_reduction", "ksp_cg_merged_reduction",
-                 "ksp_bcgs_merged_reduction", "ksp_bcgs_restarts", "ksp_cg_fold_blocks", "ksp_run_ahead")
+                 "ksp_bcgs_merged_reduction", "ksp_bcgs_restarts", "ksp_cg_fold_blocks", "ksp_run_ahead",
+                 "ksp_guess_type", "ksp_guess_fischer_model")
 # keys the reference itself sets next to a direct solver (fracstep.py:565-570): they configure MUMPS, which the Krylov
 # stand-in has no use for -- accepted silently with ksp_type=preonly
 DIRECT_ONLY_KEYS = ("pc_factor_mat_solver_type", "mat_mumps_icntl_24", "mat_mumps_icntl_25")
@@ -101,6 +122,53 @@ GAMG_KEYS = ("pc_gamg_threshold", "pc_gamg_agg_nsmooths", "pc_gamg_coarse_eq_lim
 # pc_type bjacobi: its own keys, and the sub_-prefixed gamg options of its blocks (sub_pc_type gamg)
 BJACOBI_KEYS = ("sub_pc_type", "sub_ksp_type", "pc_bjacobi_blocks")
 SUB_GAMG_KEYS = tuple("sub_" + k for k in GAMG_KEYS)
+GUESS_MAX_SIZE = 32  # OX_GUESS_MAX of csrc/ox_guess.hip
+
+
+def fischer_model(value) -> tuple[int, int, str | None]:
+    """(model, size, problem) of ``ksp_guess_fischer_model``: "model,size" as PETSc's command line writes it or a
+    2-sequence; default (1, 10).  A model other than 1 / 2 runs model 1 and a size outside 1..GUESS_MAX_SIZE is clamped;
+    ``problem`` then says so (None: as given)."""
+    if value is None:
+        return 1, 10, None
+    try:
+        parts = str(value).strip("()[] ").split(",") if isinstance(value, str) else list(value)
+        if len(parts) != 2:
+            raise ValueError
+        model, size = int(parts[0]), int(parts[1])
+    except (TypeError, ValueError):
+        return 1, 10, f"ksp_guess_fischer_model={value!r} is not 'model,size': runs 1,10"
+    why = []
+    if model not in (1, 2):
+        why.append(f"model {model} is not available: runs model 1")
+        model = 1
+    if not 1 <= size <= GUESS_MAX_SIZE:
+        clamped = min(max(size, 1), GUESS_MAX_SIZE)
+        why.append(f"size {size} is clamped to {clamped} (1..{GUESS_MAX_SIZE})")
+        size = clamped
+    return model, size, (f"ksp_guess_fischer_model={value!r}: " + "; ".join(why)) if why else None
+
+
+class _Guess:
+    """The device basis of ksp_guess_type fischer (ox_guess_create); freed with the object."""
+
+    def __init__(self, n_rows: int, n_owned: int, nc: int, model: int, size: int):
+        self.handle = C.c_void_p()
+        _lib.check(_lib.load().ox_guess_create(n_rows, n_owned, nc, model, size, C.byref(self.handle)), "ox_guess_create")
+        self.shape = (n_rows, n_owned, nc, model, size)
+
+    @property
+    def dim(self) -> int:
+        return int(_lib.load().ox_guess_dim(self.handle))
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                _lib.load().ox_guess_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
 
 
 class KSPSolver:
@@ -119,6 +187,8 @@ class KSPSolver:
         self._env_ahead = _env_int("OX_KSP_RUN_AHEAD", -1)
         self._mg = None  # amg.Hierarchy of pc_type gamg, cached on the operator's values (see _hierarchy)
         self._mg_key = None
+        self._guess = None  # _Guess of ksp_guess_type fischer, kept while the operator's values and layout hold
+        self._guess_key = None
         self.updateOptions({} if petsc_options is None else petsc_options)
 
     # -- reference surface --------------------------------------------------------------
@@ -188,6 +258,21 @@ class KSPSolver:
             warn("pc_type", f"pc_type={pc} is not available on the device: runs jacobi")
         elif pc == "none" and direct:
             warn("pc_type", "pc_type=none with ksp_type=preonly solves nothing in PETSc; runs the Krylov stand-in")
+        gt = str(o.get("ksp_guess_type", "")).lower()
+        if gt not in ("", "fischer"):
+            warn("ksp_guess_type", f"ksp_guess_type={gt} is not available on the device (fischer is): ignored")
+        elif gt == "fischer":
+            if direct:
+                warn("ksp_guess_type", "ksp_guess_type=fischer with ksp_type=preonly: a direct solve takes no initial "
+                                       "guess: ignored")
+            elif not self._guess_on():
+                meth = "CG" if self._method()[0] in (_lib.KSP_CG, _lib.KSP_CG_SINGLE) else "BiCGStab"
+                warn("ksp_guess_type", f"ksp_guess_type=fischer applies to CG on an operator flagged symmetric only "
+                                       f"(here: {meth}, {'a symmetric' if sym else 'a non-symmetric'} operator): ignored")
+            else:
+                why = fischer_model(o.get("ksp_guess_fischer_model"))[2]
+                if why:
+                    warn("ksp_guess_fischer_model", why)
         for k in o:
             if k in HONOURED_KEYS or (direct and k in DIRECT_ONLY_KEYS) or (pc == "gamg" and k in GAMG_KEYS):
                 continue
@@ -210,6 +295,59 @@ class KSPSolver:
         o = self._options
         return (str(o.get("pc_type", "")).lower() == "bjacobi" and self._sub_pc() == "gamg"
                 and str(o.get("ksp_type", "")).lower() == "cg" and nc == 1 and self._A is not None)
+
+    def _guess_on(self) -> bool:
+        """ksp_guess_type fischer honoured: a CG recurrence (any form and preconditioner of this path) on an operator
+        flagged symmetric, not a preonly stand-in."""
+        if str(self._options.get("ksp_guess_type", "")).lower() != "fischer" or self._A is None or not self._A.symmetric:
+            return False
+        meth, _, _, _, direct = self._method()
+        return not direct and meth in (_lib.KSP_CG, _lib.KSP_CG_SINGLE)
+
+    def _guess_for(self, nc: int):
+        """The basis of this solve (None: no ksp_guess_type fischer here), dropped when the operator's values (A.version)
+        or layout change, recreated when its shape or the model / size change."""
+        if not self._guess_on():
+            return None
+        A = self._A
+        model, size, _ = fischer_model(self._options.get("ksp_guess_fischer_model"))
+        shape = (int(A.pattern.n_cols), int(A.pattern.n_rows), int(nc), model, size)
+        key = (id(A), id(A.pattern), A.version, shape)
+        if self._guess is None or self._guess.shape != shape:
+            self._guess = None
+            self._guess = _Guess(*shape)
+        elif self._guess_key != key:
+            _lib.check(_lib.load().ox_guess_reset(self._guess.handle), "ox_guess_reset")
+        self._guess_key = key
+        return self._guess
+
+    def _guess_form(self, g, B: FieldStorage, X: FieldStorage, guess: bool, ax0):
+        """x <- the projected guess where the basis is not empty: returns (nonzero_guess, ax0 pointer) for the solve --
+        A x0 of model 1, None for model 2 (the caller's A x_w no longer describes x); else the caller's as they were."""
+        axw = ax0.ptr() if (ax0 is not None and guess) else None
+        if g is None:
+            return guess, axw
+        if X.n < g.shape[0] or B.n < g.shape[1]:  # (the basis spans the operator's columns: the kernels read X that far)
+            raise ValueError(f"KSPSolver[{self._prefix}]: ksp_guess_type fischer needs x of {g.shape[0]} rows (has {X.n}) "
+                             f"and b of {g.shape[1]} (has {B.n})")
+        if g.dim == 0:
+            return guess, axw
+        out = C.c_void_p()
+        A = self._A
+        _lib.check(_lib.load().ox_guess_form(g.handle, A.ref(), B.rptr(), X.ptr(), int(guess), axw, C.byref(out),
+                                             A.pattern.dist, _lib.current_stream()), "ox_guess_form")
+        return True, out.value
+
+    def _guess_update(self, g, X: FieldStorage, reasons):
+        if g is not None and all(r > 0 for r in reasons):
+            A = self._A
+            _lib.check(_lib.load().ox_guess_update(g.handle, A.ref(), X.rptr(), A.pattern.dist, _lib.current_stream()),
+                       "ox_guess_update")
+
+    @property
+    def guess_dim(self) -> int:
+        """k of ksp_guess_type fischer: directions in the basis (0 without the option or after a reset)."""
+        return 0 if self._guess is None else self._guess.dim
 
     def _nranks(self) -> int:
         if self._A is None or self._A.pattern.dist is None:
@@ -252,6 +390,7 @@ class KSPSolver:
 
     def setOperators(self, A: SellMatrix, P: typing.Optional[SellMatrix] = None):
         self._A = A
+        self._guess = self._guess_key = None
         self._dinv_version = -1
         self._every = {}
         self._merged_auto = None  # decided at the first one-column CG solve on this operator (see _cg_merged)
@@ -405,6 +544,8 @@ class KSPSolver:
         need = lib.ox_ksp_work_bytes_for(A.ref(), nc, meth)
         if self._work is None or self._work.shape[0] < need:
             self._work = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        g = self._guess_for(nc)
+        nonzero, ax0_ptr = self._guess_form(g, B, X, guess, ax0)
         res = _lib.ox_ksp_result()
         # Iterations enqueued between two host reads of the device state (a read costs ~30 us of
         # idle GPU).  One right-hand side: amortise the read over ~1.5 ms of iterations, at most 16
@@ -423,9 +564,9 @@ class KSPSolver:
         _lib.check(lib.ox_ksp_options_default(C.byref(opt)), "ox_ksp_options_default")
         opt.rtol, opt.atol, opt.max_it = rtol, atol, max_it
         opt.divtol = float(self._options.get("ksp_divtol", 1e4))  # PETSc's default ("divergence=10000." in -ksp_view)
-        opt.nonzero_guess, opt.check_every, opt.max_restarts = int(guess), int(every), restarts
+        opt.nonzero_guess, opt.check_every, opt.max_restarts = int(nonzero), int(every), restarts
         opt.fold_blocks, opt.run_ahead = self._fold_blocks(), self._run_ahead()
-        opt.ax0 = ax0.ptr() if (ax0 is not None and guess) else None
+        opt.ax0 = ax0_ptr
         if dcode is not None:
             opt.dinv_code, opt.dinv_dict = _lib.ptr(dcode), _lib.ptr(self._ddict)
             opt.n_dinv_dict = int(self._ddict.shape[0])
@@ -436,6 +577,7 @@ class KSPSolver:
             _lib.check(lib.ox_halo_forward(A.pattern.dist, X.ptr(), nc, st), "ox_halo_forward")
         self.last_result = res
         reasons = [int(res.reason[c]) for c in range(nc)]
+        self._guess_update(g, X, reasons)
         if direct:
             reasons = [_lib.CONVERGED_ITS if r > 0 else r for r in reasons]
         if _truthy(self._options.get("ksp_error_if_not_converged", False)) and any(r <= 0 for r in reasons):
@@ -452,6 +594,8 @@ class KSPSolver:
         o = self._options
         rtol, atol, max_it = float(o.get("ksp_rtol", 1e-5)), float(o.get("ksp_atol", 1e-50)), int(o.get("ksp_max_it", 10000))
         guess = bool(o.get("ksp_initial_guess_nonzero", False))
+        g = self._guess_for(1)
+        nonzero, ax0_ptr = self._guess_form(g, B, X, guess, ax0)
         need = lib.ox_ksp_work_bytes_for(A.ref(), 1, _lib.KSP_CG_MG)
         if self._work is None or self._work.shape[0] < need:
             self._work = torch.empty(int(need), dtype=torch.uint8, device=X.dev().device)
@@ -463,9 +607,9 @@ class KSPSolver:
         _lib.check(lib.ox_ksp_options_default(C.byref(opt)), "ox_ksp_options_default")
         opt.rtol, opt.atol, opt.max_it = rtol, atol, max_it
         opt.divtol = float(o.get("ksp_divtol", 1e4))
-        opt.nonzero_guess, opt.check_every = int(guess), int(every)
+        opt.nonzero_guess, opt.check_every = int(nonzero), int(every)
         opt.run_ahead = self._run_ahead()
-        opt.ax0 = ax0.ptr() if (ax0 is not None and guess) else None
+        opt.ax0 = ax0_ptr
         res = _lib.ox_ksp_result()
         st = _lib.current_stream()
         if A.pattern.dist is None:
@@ -478,6 +622,7 @@ class KSPSolver:
             _lib.check(lib.ox_halo_forward(A.pattern.dist, X.ptr(), 1, st), "ox_halo_forward")  # x.scatter_forward()
         self.last_result = res
         reasons = [int(res.reason[0])]
+        self._guess_update(g, X, reasons)
         if _truthy(o.get("ksp_error_if_not_converged", False)) and reasons[0] <= 0:
             raise KSPConvergenceError(self._prefix, reasons, [int(res.its[0])])
         return reasons
