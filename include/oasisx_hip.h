@@ -646,6 +646,39 @@ int ox_guess_form(ox_guess *g, const ox_sell *A, const double *b, double *x, int
                   const double **ax0_out, const ox_dist *dist, void *stream);
 int ox_guess_update(ox_guess *g, const ox_sell *A, const double *x, const ox_dist *dist, void *stream);
 
+/* ---- Point evaluation: cell locator, evaluation at points, probes (ox_probe.hip) ------------------------------------
+ * Locator over the straight simplices of a mesh (coords [n_vertices][gdim], cells [n_cells][gdim + 1] int64, both on the
+ * device), or over the cells cell_ids[n_ids] only (device, ASCENDING mesh cell ids; NULL: all cells): a uniform
+ * background grid, about one cell per bin, per bin the ascending list of the cells whose bounding box -- grown by the
+ * barycentric tolerance `tol` and the absolute `padding` -- overlaps it.  The object owns its device memory; creation
+ * synchronises `stream`, the queries are stream-ordered and read nothing back.
+ *   ox_locator_find: per point x[i][gdim] the LOWEST mesh cell id whose barycentric coordinates all are >= -tol (tol <=
+ *                    the tolerance of the creation) into cells[i] (-1: none; points outside the grid's box touch no
+ *                    memory) and those gdim + 1 coordinates into bary[i][gdim + 1] (NaN when none).
+ *   ox_locator_bary: the barycentric coordinates of x[i] in the GIVEN mesh cell cells[i] (NaN for -1 or a cell that is
+ *                    not in the locator). */
+typedef struct ox_locator ox_locator;
+int ox_locator_create(int gdim, const double *coords, int64_t n_vertices, const int64_t *cells, int64_t n_cells,
+                      const int64_t *cell_ids, int64_t n_ids, double tol, double padding, void *stream, ox_locator **out);
+int ox_locator_destroy(ox_locator *loc);
+int ox_locator_info(const ox_locator *loc, int64_t *n_cells, int64_t *n_bins, int64_t *n_list, int *bins_per_axis3);
+int ox_locator_find(const ox_locator *loc, int64_t n_points, const double *x, double tol, int64_t *cells, double *bary,
+                    void *stream);
+int ox_locator_bary(const ox_locator *loc, int64_t n_points, const double *x, const int64_t *cells, double *bary,
+                    void *stream);
+/* Values of a Lagrange field of degree 1..3 (P1, P2, the gll_warped P3 element; node order of the assembly kernels) at
+ * located points.  cell_dofs [n_cells][nd]: the space's table in kernel cell order; field: interleaved block [n_rows][nc];
+ * col = -1: all nc columns, else that one.  Point i -- the caller passes the points SORTED by cell_pos, so that the lanes
+ * of a wave read neighbouring rows -- lies in the cell at kernel position cell_pos[i] (-1: none -> NaN) with barycentric
+ * coordinates bary[i][gdim + 1]; its values go to out[perm[i] * ld + off + v] (perm == NULL: i), one lane per point, sums
+ * in dof order.  ox_probe_sample writes the same into slot `slot` of a ring [capacity][n_points][ld] on `stream`. */
+int ox_eval_points(int degree, int gdim, const int32_t *cell_dofs, int64_t n_cells, int64_t n_rows, int64_t n_points,
+                   const int64_t *cell_pos, const double *bary, const int64_t *perm, const double *field, int nc, int col,
+                   double *out, int64_t ld, int64_t off, void *stream);
+int ox_probe_sample(int degree, int gdim, const int32_t *cell_dofs, int64_t n_cells, int64_t n_rows, int64_t n_points,
+                    const int64_t *cell_pos, const double *bary, const int64_t *perm, const double *field, int nc, int col,
+                    double *ring, int64_t capacity, int64_t slot, int64_t ld, int64_t off, void *stream);
+
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */
 int ox_comm_create(const char *id128, int rank, int nranks, void **comm_out); /* ncclCommInitRank */

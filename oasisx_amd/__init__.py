@@ -5,10 +5,11 @@ Same names as reference src/oasisx/__init__.py:12-18; the compute path is the HI
 """
 import logging
 
-from . import fem, io, mesh  # noqa: F401
+from . import fem, geometry, io, mesh  # noqa: F401
 from .bcs import DirichletBC, LocatorMethod, PressureBC
 from .fracstep import FractionalStep_AB_CN
 from .function import Projector
+from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 
 logging.basicConfig()

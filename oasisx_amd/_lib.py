@@ -295,6 +295,13 @@ SIGNATURES = {
     "ox_guess_bytes": (C.c_size_t, [_P]),
     "ox_guess_form": (_I, [_P, C.POINTER(ox_sell), _P, _P, _I, _P, C.POINTER(_P), _P, _P]),
     "ox_guess_update": (_I, [_P, C.POINTER(ox_sell), _P, _P, _P]),
+    "ox_locator_create": (_I, [_I, _P, _L, _P, _L, _P, _L, _D, _D, _P, C.POINTER(_P)]),
+    "ox_locator_destroy": (_I, [_P]),
+    "ox_locator_info": (_I, [_P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),
+    "ox_locator_find": (_I, [_P, _L, _P, _D, _P, _P, _P]),
+    "ox_locator_bary": (_I, [_P, _L, _P, _P, _P, _P]),
+    "ox_eval_points": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P]),
+    "ox_probe_sample": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _L, _L, _P]),
     "ox_profile_begin": (_I, [_I, _I]),
     "ox_profile_end": (_I, []),
     "ox_profile_get": (_I, [_I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_D)]),

@@ -1,0 +1,659 @@
+// Point evaluation of Lagrange fields: a cell locator, the evaluation at located points and the sampling of probes into a
+// device-resident ring (the counterpart of dolfinx.geometry + Function.eval for the oasisx callers).
+//
+// Locator.  A uniform background grid over the bounding box of the (selected) straight simplices, about one cell per bin;
+// per bin the list of the cells whose bounding box, grown by the tolerance, overlaps it: a count pass, an exclusive scan,
+// a fill pass with integer cursors and a sort of every segment -- the lists come out ASCENDING in cell position whatever
+// the launch order.  ``find`` takes one lane per point: bin of the point, walk the bin's list, barycentric coordinates
+// lambda_a = grad(lambda_a) . (x - x_0) (a = 1..d; the rows of fem.cell_geometry), lambda_0 = 1 - sum; the point is in the
+// cell when min lambda >= -tol.  The first hit of the ascending list is the LOWEST containing cell: the same answer on
+// every run, for points on shared faces too.  Points outside the grid's box return -1 without touching memory.
+//
+// Evaluation.  One lane per point, the points sorted by kernel-cell position by the caller (the cell order is the tiled
+// spatial order of the mat-vecs: the lanes of a wave open neighbouring rows of the field): gather the cell's dof rows,
+// evaluate the basis in barycentric form (P1, P2, the gll_warped P3 element through its monomial coefficients in
+// __constant__ memory), accumulate in dof order, write out[perm[i]].  No atomics on doubles, no LDS, nothing read back.
+#include "ox_kernels.h"
+
+#define OX_P3_COEF_QUAL __constant__
+#include "fe_tables_eval.h"
+
+#define OX_LOC_SCAN_ITEMS 8                          // bins per thread of the scan's first pass
+#define OX_LOC_SCAN_TILE (256 * OX_LOC_SCAN_ITEMS)   // bins per block
+#define OX_LOC_MAX_BINS ((int64_t)1 << 30)
+
+struct LocGrid {
+  double lo[3], hi[3], inv_h[3];
+  int nb[3];
+};
+
+struct ox_locator {
+  int gdim;
+  int64_t n_cells;   // cells in the grid (the selection, or all cells of the mesh)
+  int64_t n_bins, n_list;
+  double tol;
+  LocGrid grid;
+  void *mem;         // x0, grad, box
+  void *mem_grid;    // bin_ptr, cursor
+  void *mem_list;
+  double *x0;        // [n_cells][d]   first vertex
+  double *grad;      // [n_cells][d*d] grad(lambda_1..d), the rows of fem.cell_geometry
+  double *box;       // [n_cells][2d]  bounding box grown by the tolerance
+  int64_t *ids;      // [n_cells] mesh cell id of position i, ascending (nullptr: position = id)
+  int64_t *bin_ptr;  // [n_bins + 1]
+  int32_t *list;     // [n_list] cell positions, ascending inside every bin
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// set-up kernels
+template <int D>
+__global__ __launch_bounds__(256) void k_loc_geom(int64_t n, int64_t n_verts, int64_t n_mesh_cells,
+                                                  const double *__restrict__ coords, const int64_t *__restrict__ cells,
+                                                  const int64_t *__restrict__ ids, double tol, double pad_abs,
+                                                  double *__restrict__ x0, double *__restrict__ grad,
+                                                  double *__restrict__ box, double *__restrict__ partial) {
+  __shared__ double red[4 * 2 * D];
+  double mn[D], mx[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) mn[k] = INFINITY, mx[k] = -INFINITY;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const int64_t c = ids ? ids[i] : i;
+    double x[D + 1][D];
+    bool ok = c >= 0 && c < n_mesh_cells;
+#pragma unroll
+    for (int a = 0; a <= D; ++a) {
+      const int64_t v = ok ? cells[c * (D + 1) + a] : -1;
+      ok = ok && v >= 0 && v < n_verts;
+#pragma unroll
+      for (int k = 0; k < D; ++k) x[a][k] = ok ? coords[v * D + k] : NAN;
+    }
+    double e[D][D];  // rows = edge vectors x_a - x_0
+#pragma unroll
+    for (int a = 0; a < D; ++a)
+#pragma unroll
+      for (int k = 0; k < D; ++k) e[a][k] = x[a + 1][k] - x[0][k];
+    double g[D * D];
+    if constexpr (D == 2) {
+      const double a = e[0][0], b = e[1][0], c2 = e[0][1], dd = e[1][1];  // J = [[a, b], [c2, dd]]
+      const double det = a * dd - b * c2;
+      g[0] = dd / det, g[1] = -b / det, g[2] = -c2 / det, g[3] = a / det;
+    } else {
+      const double *e1 = e[0], *e2 = e[1], *e3 = e[D - 1];
+      double c23[3] = {e2[1] * e3[2] - e2[2] * e3[1], e2[2] * e3[0] - e2[0] * e3[2], e2[0] * e3[1] - e2[1] * e3[0]};
+      double c31[3] = {e3[1] * e1[2] - e3[2] * e1[1], e3[2] * e1[0] - e3[0] * e1[2], e3[0] * e1[1] - e3[1] * e1[0]};
+      double c12[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+      const double det = e1[0] * c23[0] + e1[1] * c23[1] + e1[2] * c23[2];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g[k] = c23[k] / det, g[3 + k] = c31[k] / det, g[6 + k] = c12[k] / det;
+    }
+#pragma unroll
+    for (int k = 0; k < D * D; ++k) grad[i * D * D + k] = g[k];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      double l = x[0][k], h = x[0][k];
+#pragma unroll
+      for (int a = 1; a <= D; ++a) l = fmin(l, x[a][k]), h = fmax(h, x[a][k]);
+      // a point with min lambda >= -tol lies within (d + 1) tol cell extents of the hull
+      const double pad = (D + 2) * tol * (h - l) + 1e-15 * fmax(fabs(l), fabs(h)) + pad_abs;
+      l -= pad, h += pad;
+      x0[i * D + k] = x[0][k];
+      box[i * 2 * D + k] = l, box[i * 2 * D + D + k] = h;
+      if (ok) mn[k] = l, mx[k] = h;
+    }
+  }
+  // the block's box: minima then maxima (fixed order; min / max do not depend on it anyway)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    double a = mn[k], b = mx[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a = fmin(a, __shfl_down(a, off, 64)), b = fmax(b, __shfl_down(b, off, 64));
+    if (lane == 0) red[wave * 2 * D + k] = a, red[wave * 2 * D + D + k] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * D) {
+    const int k = threadIdx.x;
+    double v = red[k];
+    for (int w = 1; w < 4; ++w) v = k < D ? fmin(v, red[w * 2 * D + k]) : fmax(v, red[w * 2 * D + k]);
+    partial[(size_t)blockIdx.x * 2 * D + k] = v;
+  }
+}
+
+// out[k] = min (k < D) / max (k >= D) over the blocks' partial boxes; one block
+template <int D>
+__global__ __launch_bounds__(256) void k_loc_box(const double *__restrict__ partial, int nblk, double *__restrict__ out) {
+  __shared__ double red[256];
+  for (int k = 0; k < 2 * D; ++k) {
+    double v = k < D ? INFINITY : -INFINITY;
+    for (int b = threadIdx.x; b < nblk; b += 256) {
+      const double p = partial[(size_t)b * 2 * D + k];
+      v = k < D ? fmin(v, p) : fmax(v, p);
+    }
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) red[threadIdx.x] = k < D ? fmin(red[threadIdx.x], red[threadIdx.x + s]) : fmax(red[threadIdx.x], red[threadIdx.x + s]);
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) out[k] = red[0];
+    __syncthreads();
+  }
+}
+
+// bin index along axis k of a coordinate inside [lo, hi]; monotone in x, so lo_cell <= x <= hi_cell puts the point's bin
+// inside the cell's bin range
+__device__ __forceinline__ int loc_bin(const LocGrid &G, int k, double x) {
+  const double t = (x - G.lo[k]) * G.inv_h[k];
+  int b = t > 0.0 ? (t < 2.0e9 ? (int)t : G.nb[k] - 1) : 0;
+  return b < G.nb[k] ? b : G.nb[k] - 1;
+}
+
+// pass 0: counts (cursor[bin] += 1); pass 1: fill (list[bin_ptr[bin] + cursor[bin]++] = cell)
+template <int D, int FILL>
+__global__ __launch_bounds__(256) void k_loc_bins(int64_t n, LocGrid G, const double *__restrict__ box, int64_t n_bins,
+                                                  const int64_t *__restrict__ bin_ptr, int *__restrict__ cursor,
+                                                  int32_t *__restrict__ list, int64_t n_list) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  int b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const double l = box[i * 2 * D + k], h = box[i * 2 * D + D + k];
+    if (!(l <= h)) return;  // (a cell with an invalid vertex: in no bin)
+    b0[k] = loc_bin(G, k, l), b1[k] = loc_bin(G, k, h);
+  }
+  for (int z = b0[2]; z <= b1[2]; ++z)
+    for (int y = b0[1]; y <= b1[1]; ++y)
+      for (int x = b0[0]; x <= b1[0]; ++x) {
+        const int64_t bin = ((int64_t)z * G.nb[1] + y) * G.nb[0] + x;
+        if (bin < 0 || bin >= n_bins) continue;
+        const int slot = atomicAdd(&cursor[bin], 1);
+        if (FILL) {
+          const int64_t at = bin_ptr[bin] + slot;
+          if (at >= 0 && at < bin_ptr[bin + 1] && at < n_list) list[at] = (int32_t)i;
+        }
+      }
+}
+
+// exclusive scan of int counts into int64 offsets, three passes
+__global__ __launch_bounds__(256) void k_loc_scan_tiles(int64_t n, const int *__restrict__ cnt, int64_t *__restrict__ off,
+                                                        int64_t *__restrict__ tile_sum) {
+  __shared__ int64_t sh[256];
+  const int64_t base = (int64_t)blockIdx.x * OX_LOC_SCAN_TILE + (int64_t)threadIdx.x * OX_LOC_SCAN_ITEMS;
+  int64_t v[OX_LOC_SCAN_ITEMS], s = 0;
+#pragma unroll
+  for (int j = 0; j < OX_LOC_SCAN_ITEMS; ++j) {
+    v[j] = s;
+    s += base + j < n ? (int64_t)cnt[base + j] : 0;
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {  // inclusive scan of the thread sums
+    const int64_t t = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
+    __syncthreads();
+    sh[threadIdx.x] += t;
+    __syncthreads();
+  }
+  const int64_t excl = sh[threadIdx.x] - s;
+#pragma unroll
+  for (int j = 0; j < OX_LOC_SCAN_ITEMS; ++j)
+    if (base + j < n) off[base + j] = excl + v[j];
+  if (threadIdx.x == 255) tile_sum[blockIdx.x] = sh[255];
+}
+__global__ __launch_bounds__(64) void k_loc_scan_sums(int64_t ntiles, int64_t *__restrict__ tile_sum, int64_t *__restrict__ total) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int64_t s = 0;
+  for (int64_t t = 0; t < ntiles; ++t) {
+    const int64_t v = tile_sum[t];
+    tile_sum[t] = s;
+    s += v;
+  }
+  *total = s;
+}
+__global__ __launch_bounds__(256) void k_loc_scan_add(int64_t n, int64_t *__restrict__ off, const int64_t *__restrict__ tile_sum,
+                                                      const int64_t *__restrict__ total) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) off[i] += tile_sum[i / OX_LOC_SCAN_TILE];
+  if (i == n) off[n] = *total;
+}
+
+// one lane per bin: insertion sort of the bin's segment (a few tens of entries)
+__global__ __launch_bounds__(256) void k_loc_sort(int64_t n_bins, const int64_t *__restrict__ bin_ptr, int32_t *__restrict__ list,
+                                                  int64_t n_list) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= n_bins) return;
+  const int64_t s0 = bin_ptr[b], s1 = bin_ptr[b + 1];
+  if (s0 < 0 || s1 > n_list) return;
+  for (int64_t i = s0 + 1; i < s1; ++i) {
+    const int32_t v = list[i];
+    int64_t j = i;
+    while (j > s0 && list[j - 1] > v) {
+      list[j] = list[j - 1];
+      --j;
+    }
+    list[j] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// queries
+template <int D>
+__device__ __forceinline__ double loc_bary(const double *__restrict__ x0, const double *__restrict__ grad, int64_t c,
+                                           const double (&x)[D], double (&lam)[D + 1]) {
+  double r[D], l0 = 1.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) r[k] = x[k] - x0[c * D + k];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) s = fma(grad[c * D * D + a * D + k], r[k], s);
+    lam[a + 1] = s;
+    l0 -= s;
+  }
+  lam[0] = l0;
+  double m = l0;
+#pragma unroll
+  for (int a = 1; a <= D; ++a) m = fmin(m, lam[a]);
+  return m;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_loc_find(int64_t n, const double *__restrict__ xs, LocGrid G, int64_t n_cells,
+                                                  int64_t n_bins, const int64_t *__restrict__ bin_ptr,
+                                                  const int32_t *__restrict__ list, int64_t n_list,
+                                                  const double *__restrict__ x0, const double *__restrict__ grad,
+                                                  const int64_t *__restrict__ ids, double tol, int64_t *__restrict__ cell_out,
+                                                  double *__restrict__ bary_out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double x[D];
+  bool inside = true;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    x[k] = xs[i * D + k];
+    inside = inside && (x[k] >= G.lo[k]) && (x[k] <= G.hi[k]);  // (NaN: outside)
+  }
+  int64_t found = -1;
+  double lam[D + 1];
+#pragma unroll
+  for (int a = 0; a <= D; ++a) lam[a] = NAN;
+  if (inside) {
+    int64_t bin = 0;
+#pragma unroll
+    for (int k = D - 1; k >= 0; --k) bin = bin * G.nb[k] + loc_bin(G, k, x[k]);
+    if (bin >= 0 && bin < n_bins) {
+      int64_t s0 = bin_ptr[bin], s1 = bin_ptr[bin + 1];
+      if (s0 < 0) s0 = 0;
+      if (s1 > n_list) s1 = n_list;
+      for (int64_t s = s0; s < s1; ++s) {
+        const int64_t c = list[s];
+        if (c < 0 || c >= n_cells) continue;
+        double l[D + 1];
+        if (loc_bary<D>(x0, grad, c, x, l) >= -tol) {  // ascending list: the first hit is the lowest containing cell
+          found = c;
+#pragma unroll
+          for (int a = 0; a <= D; ++a) lam[a] = l[a];
+          break;
+        }
+      }
+    }
+  }
+  cell_out[i] = found < 0 ? -1 : (ids ? ids[found] : found);
+#pragma unroll
+  for (int a = 0; a <= D; ++a) bary_out[i * (D + 1) + a] = lam[a];
+}
+
+// barycentric coordinates of points in GIVEN cells (mesh cell ids; -1 or a cell outside the locator: NaN)
+template <int D>
+__global__ __launch_bounds__(256) void k_loc_bary(int64_t n, const double *__restrict__ xs, const int64_t *__restrict__ cells,
+                                                  int64_t n_cells, const double *__restrict__ x0, const double *__restrict__ grad,
+                                                  const int64_t *__restrict__ ids, double *__restrict__ bary_out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = cells[i];
+  int64_t pos = -1;
+  if (!ids) {
+    pos = c >= 0 && c < n_cells ? c : -1;
+  } else if (c >= 0) {  // ids ascending: binary search
+    int64_t a = 0, b = n_cells;
+    while (a < b) {
+      const int64_t m = (a + b) >> 1;
+      if (ids[m] < c) a = m + 1;
+      else b = m;
+    }
+    if (a < n_cells && ids[a] == c) pos = a;
+  }
+  double lam[D + 1];
+#pragma unroll
+  for (int a = 0; a <= D; ++a) lam[a] = NAN;
+  if (pos >= 0) {
+    double x[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) x[k] = xs[i * D + k];
+    loc_bary<D>(x0, grad, pos, x, lam);
+  }
+#pragma unroll
+  for (int a = 0; a <= D; ++a) bary_out[i * (D + 1) + a] = lam[a];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// evaluation
+__host__ __device__ constexpr int probe_nd(int d, int degree) {
+  return degree == 1 ? d + 1 : (degree == 2 ? (d + 1) * (d + 2) / 2 : (d == 2 ? 10 : 20));
+}
+
+// phi of the P1 / P2 element of fem.lagrange_basis at the barycentric point lam
+template <int D, int DEG>
+__device__ __forceinline__ void probe_basis(const double (&lam)[D + 1], double (&phi)[probe_nd(D, DEG)]) {
+  if constexpr (DEG == 1) {
+#pragma unroll
+    for (int a = 0; a <= D; ++a) phi[a] = lam[a];
+  } else {
+#pragma unroll
+    for (int a = 0; a <= D; ++a) phi[a] = lam[a] * (2.0 * lam[a] - 1.0);
+    if constexpr (D == 2) {  // local_edges(2): (1, 2), (0, 2), (0, 1)
+      phi[3] = 4.0 * lam[1] * lam[2], phi[4] = 4.0 * lam[0] * lam[2], phi[5] = 4.0 * lam[0] * lam[1];
+    } else {  // local_edges(3): (2, 3), (1, 3), (1, 2), (0, 3), (0, 2), (0, 1)
+      phi[4] = 4.0 * lam[2] * lam[3], phi[5] = 4.0 * lam[1] * lam[3], phi[6] = 4.0 * lam[1] * lam[2];
+      phi[7] = 4.0 * lam[0] * lam[3], phi[8] = 4.0 * lam[0] * lam[2], phi[9] = 4.0 * lam[0] * lam[1];
+    }
+  }
+}
+// the monomials of fem._p3_mono at lam: m_c = lambda_1^i lambda_2^j [lambda_3^k], exponents with i slowest
+template <int D>
+__device__ __forceinline__ void probe_mono3(const double (&lam)[D + 1], double (&m)[probe_nd(D, 3)]) {
+  double p[D][4];
+#pragma unroll
+  for (int v = 0; v < D; ++v) {
+    p[v][0] = 1.0, p[v][1] = lam[v + 1];
+    p[v][2] = p[v][1] * p[v][1], p[v][3] = p[v][2] * p[v][1];
+  }
+  int c = 0;
+  if constexpr (D == 2) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4 - i; ++j) m[c++] = p[0][i] * p[1][j];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4 - i; ++j)
+#pragma unroll
+        for (int k = 0; k < 4 - i - j; ++k) m[c++] = p[0][i] * p[1][j] * p[D - 1][k];
+  }
+}
+// phi_a of the gll_warped P3 element from the monomials: column a of the coefficient matrix (a uniform over the wave: the
+// coefficients arrive by scalar loads)
+template <int D>
+__device__ __forceinline__ double probe_phi3(const double (&m)[probe_nd(D, 3)], int a) {
+  constexpr int ND = probe_nd(D, 3);
+  double s = 0.0;
+#pragma unroll
+  for (int q = 0; q < ND; ++q) {
+    if constexpr (D == 2) s = fma(m[q], OX_P3_COEF2[q][a], s);
+    else s = fma(m[q], OX_P3_COEF3[q][a], s);
+  }
+  return s;
+}
+
+// out[perm[i] * ld + v] = sum_a phi_a(bary_i) field[cell_dofs[pos_i][a]][col0 + v], v < nv; a point without a cell: NaN
+template <int D, int DEG>
+__global__ __launch_bounds__(256) void k_eval_points(int64_t n, const int32_t *__restrict__ cell_dofs, int64_t n_cells,
+                                                     int64_t n_rows, const int64_t *__restrict__ cell_pos,
+                                                     const double *__restrict__ bary, const int64_t *__restrict__ perm,
+                                                     const double *__restrict__ field, int nc, int col0, int nv,
+                                                     double *__restrict__ out, int64_t ld) {
+  constexpr int ND = probe_nd(D, DEG);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t dst = perm ? perm[i] : i;
+  if (dst < 0 || dst >= n) return;
+  const int64_t c = cell_pos[i];
+  double acc[OX_MAXC];
+#pragma unroll
+  for (int v = 0; v < OX_MAXC; ++v) acc[v] = 0.0;
+  bool ok = c >= 0 && c < n_cells;
+  if (ok) {
+    double lam[D + 1];
+#pragma unroll
+    for (int a = 0; a <= D; ++a) lam[a] = bary[i * (D + 1) + a];
+    auto add = [&](int a, double phi_a) {
+      const int64_t r = cell_dofs[c * ND + a];
+      if (r < 0 || r >= n_rows) {
+        ok = false;
+        return;
+      }
+      const double *row = field + r * nc + col0;
+#pragma unroll
+      for (int v = 0; v < OX_MAXC; ++v)
+        if (v < nv) acc[v] = fma(phi_a, row[v], acc[v]);
+    };
+    if constexpr (DEG < 3) {
+      double phi[ND];
+      probe_basis<D, DEG>(lam, phi);
+#pragma unroll
+      for (int a = 0; a < ND; ++a) add(a, phi[a]);
+    } else {
+      double m[ND];
+      probe_mono3<D>(lam, m);
+#pragma unroll 2
+      for (int a = 0; a < ND; ++a) add(a, probe_phi3<D>(m, a));
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < OX_MAXC; ++v)
+    if (v < nv) out[dst * ld + v] = ok ? acc[v] : NAN;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+static void loc_free(ox_locator *L) {
+  if (!L) return;
+  if (L->mem) (void)hipFree(L->mem);
+  if (L->mem_grid) (void)hipFree(L->mem_grid);
+  if (L->mem_list) (void)hipFree(L->mem_list);
+  delete L;
+}
+
+template <int D>
+static int loc_create(ox_locator *L, const double *coords, int64_t n_verts, const int64_t *cells, int64_t n_mesh_cells,
+                      const int64_t *ids, double padding, hipStream_t st) {
+  const int64_t n = L->n_cells;
+  const int nblk = (int)((n + 255) / 256);
+  const size_t dbl = (size_t)n * (D + D * D + 2 * D) + (size_t)nblk * 2 * D + 2 * D;
+  const size_t bytes = dbl * sizeof(double) + (ids ? (size_t)n * sizeof(int64_t) : 0);
+  if (hipMalloc(&L->mem, bytes) != hipSuccess) OX_FAIL("ox_locator_create: hipMalloc of %zu bytes failed", bytes);
+  double *p = static_cast<double *>(L->mem);
+  L->x0 = p, p += (size_t)n * D;
+  L->grad = p, p += (size_t)n * D * D;
+  L->box = p, p += (size_t)n * 2 * D;
+  double *partial = p;
+  p += (size_t)nblk * 2 * D;
+  double *gbox = p;
+  p += 2 * D;
+  if (ids) {
+    L->ids = reinterpret_cast<int64_t *>(p);
+    OX_HIP(hipMemcpyAsync(L->ids, ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+  }
+  hipLaunchKernelGGL(k_loc_geom<D>, dim3(nblk), dim3(256), 0, st, n, n_verts, n_mesh_cells, coords, cells, L->ids, L->tol,
+                     padding, L->x0, L->grad, L->box, partial);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_box<D>, dim3(1), dim3(256), 0, st, partial, nblk, gbox);
+  OX_LAUNCH_CHECK();
+  double hb[2 * D];
+  OX_HIP(hipMemcpyAsync(hb, gbox, sizeof(hb), hipMemcpyDeviceToHost, st));
+  OX_HIP(hipStreamSynchronize(st));
+  // bins per axis from the extents: about one cell per bin
+  LocGrid &G = L->grid;
+  double vol = 1.0;
+  int nz = 0;
+  for (int k = 0; k < D; ++k) {
+    if (!(hb[k] <= hb[D + k])) OX_FAIL("ox_locator_create: the cells have no finite bounding box");
+    G.lo[k] = hb[k], G.hi[k] = hb[D + k];
+    const double ext = G.hi[k] - G.lo[k];
+    if (ext > 0.0) vol *= ext, ++nz;
+  }
+  const double h = nz ? pow(vol / (double)n, 1.0 / nz) : 1.0;
+  int64_t nbins = 1;
+  for (int k = 0; k < 3; ++k) G.nb[k] = 1;
+  for (int k = 0; k < D; ++k) {
+    const double ext = G.hi[k] - G.lo[k];
+    double q = ext > 0.0 && h > 0.0 ? ceil(ext / h) : 1.0;
+    if (!(q >= 1.0)) q = 1.0;
+    if (q > 1024.0) q = 1024.0;
+    G.nb[k] = (int)q;
+    G.inv_h[k] = ext > 0.0 ? q / ext : 0.0;
+    nbins *= G.nb[k];
+  }
+  for (int k = D; k < 3; ++k) G.lo[k] = G.hi[k] = G.inv_h[k] = 0.0;
+  if (nbins > OX_LOC_MAX_BINS) OX_FAIL("ox_locator_create: %lld bins", (long long)nbins);
+  L->n_bins = nbins;
+  const int64_t ntiles = (nbins + OX_LOC_SCAN_TILE - 1) / OX_LOC_SCAN_TILE;
+  const size_t gbytes = (size_t)(nbins + 1 + ntiles + 1) * sizeof(int64_t) + (size_t)nbins * sizeof(int);
+  if (hipMalloc(&L->mem_grid, gbytes) != hipSuccess) OX_FAIL("ox_locator_create: hipMalloc of %zu bytes failed", gbytes);
+  L->bin_ptr = static_cast<int64_t *>(L->mem_grid);
+  int64_t *tile_sum = L->bin_ptr + nbins + 1, *total = tile_sum + ntiles;
+  int *cursor = reinterpret_cast<int *>(total + 1);
+  OX_HIP(hipMemsetAsync(cursor, 0, (size_t)nbins * sizeof(int), st));
+  hipLaunchKernelGGL((k_loc_bins<D, 0>), dim3(nblk), dim3(256), 0, st, n, G, L->box, nbins, L->bin_ptr, cursor, nullptr, (int64_t)0);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, st, nbins, cursor, L->bin_ptr, tile_sum);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_scan_sums, dim3(1), dim3(64), 0, st, ntiles, tile_sum, total);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_scan_add, dim3((unsigned)((nbins + 1 + 255) / 256)), dim3(256), 0, st, nbins, L->bin_ptr, tile_sum, total);
+  OX_LAUNCH_CHECK();
+  int64_t n_list = 0;
+  OX_HIP(hipMemcpyAsync(&n_list, total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  OX_HIP(hipStreamSynchronize(st));
+  if (n_list < 0) OX_FAIL("ox_locator_create: list size %lld", (long long)n_list);
+  L->n_list = n_list;
+  const size_t lbytes = (size_t)(n_list > 0 ? n_list : 1) * sizeof(int32_t);
+  if (hipMalloc(&L->mem_list, lbytes) != hipSuccess) OX_FAIL("ox_locator_create: hipMalloc of %zu bytes failed", lbytes);
+  L->list = static_cast<int32_t *>(L->mem_list);
+  OX_HIP(hipMemsetAsync(L->list, 0xff, lbytes, st));  // (-1: skipped by find)
+  OX_HIP(hipMemsetAsync(cursor, 0, (size_t)nbins * sizeof(int), st));
+  hipLaunchKernelGGL((k_loc_bins<D, 1>), dim3(nblk), dim3(256), 0, st, n, G, L->box, nbins, L->bin_ptr, cursor, L->list, n_list);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_sort, dim3((unsigned)((nbins + 255) / 256)), dim3(256), 0, st, nbins, L->bin_ptr, L->list, n_list);
+  OX_LAUNCH_CHECK();
+  OX_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+extern "C" int ox_locator_create(int gdim, const double *coords, int64_t n_vertices, const int64_t *cells, int64_t n_cells,
+                                 const int64_t *cell_ids, int64_t n_ids, double tol, double padding, void *stream,
+                                 ox_locator **out) {
+  if (!out) OX_FAIL("ox_locator_create: null argument");
+  *out = nullptr;
+  if (gdim != 2 && gdim != 3) OX_FAIL("ox_locator_create: gdim=%d", gdim);
+  if (!coords || !cells || n_vertices < 1 || n_cells < 1) OX_FAIL("ox_locator_create: empty mesh");
+  if (!(tol >= 0.0) || !(tol <= 1e-2)) OX_FAIL("ox_locator_create: tol=%g (0..1e-2)", tol);
+  if (!(padding >= 0.0)) OX_FAIL("ox_locator_create: padding=%g", padding);
+  const int64_t n = cell_ids ? n_ids : n_cells;
+  if (n < 1 || n > n_cells || n >= ((int64_t)1 << 31) - 256) OX_FAIL("ox_locator_create: %lld cells selected", (long long)n);
+  ox_locator *L = new ox_locator();
+  memset(L, 0, sizeof(*L));
+  L->gdim = gdim, L->n_cells = n, L->tol = tol;
+  hipStream_t st = ox_stream(stream);
+  const int rc = gdim == 2 ? loc_create<2>(L, coords, n_vertices, cells, n_cells, cell_ids, padding, st)
+                           : loc_create<3>(L, coords, n_vertices, cells, n_cells, cell_ids, padding, st);
+  if (rc) {
+    loc_free(L);
+    return -1;
+  }
+  *out = L;
+  return 0;
+}
+
+extern "C" int ox_locator_destroy(ox_locator *L) {
+  loc_free(L);
+  return 0;
+}
+
+extern "C" int ox_locator_info(const ox_locator *L, int64_t *n_cells, int64_t *n_bins, int64_t *n_list, int *bins_per_axis) {
+  if (!L) OX_FAIL("ox_locator_info: null handle");
+  if (n_cells) *n_cells = L->n_cells;
+  if (n_bins) *n_bins = L->n_bins;
+  if (n_list) *n_list = L->n_list;
+  if (bins_per_axis)
+    for (int k = 0; k < 3; ++k) bins_per_axis[k] = L->grid.nb[k];
+  return 0;
+}
+
+extern "C" int ox_locator_find(const ox_locator *L, int64_t n_points, const double *x, double tol, int64_t *cells, double *bary,
+                               void *stream) {
+  if (!L || (n_points > 0 && (!x || !cells || !bary))) OX_FAIL("ox_locator_find: null argument");
+  if (!(tol >= 0.0) || tol > L->tol) OX_FAIL("ox_locator_find: tol=%g, the grid was built for tol <= %g", tol, L->tol);
+  if (n_points <= 0) return 0;
+  hipStream_t st = ox_stream(stream);
+  const dim3 grid((unsigned)((n_points + 255) / 256));
+  if (L->gdim == 2)
+    hipLaunchKernelGGL(k_loc_find<2>, grid, dim3(256), 0, st, n_points, x, L->grid, L->n_cells, L->n_bins, L->bin_ptr, L->list,
+                       L->n_list, L->x0, L->grad, L->ids, tol, cells, bary);
+  else
+    hipLaunchKernelGGL(k_loc_find<3>, grid, dim3(256), 0, st, n_points, x, L->grid, L->n_cells, L->n_bins, L->bin_ptr, L->list,
+                       L->n_list, L->x0, L->grad, L->ids, tol, cells, bary);
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ox_locator_bary(const ox_locator *L, int64_t n_points, const double *x, const int64_t *cells, double *bary,
+                               void *stream) {
+  if (!L || (n_points > 0 && (!x || !cells || !bary))) OX_FAIL("ox_locator_bary: null argument");
+  if (n_points <= 0) return 0;
+  hipStream_t st = ox_stream(stream);
+  const dim3 grid((unsigned)((n_points + 255) / 256));
+  if (L->gdim == 2)
+    hipLaunchKernelGGL(k_loc_bary<2>, grid, dim3(256), 0, st, n_points, x, cells, L->n_cells, L->x0, L->grad, L->ids, bary);
+  else
+    hipLaunchKernelGGL(k_loc_bary<3>, grid, dim3(256), 0, st, n_points, x, cells, L->n_cells, L->x0, L->grad, L->ids, bary);
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+static int eval_launch(const char *who, int degree, int gdim, const int32_t *cell_dofs, int64_t n_cells, int64_t n_rows,
+                       int64_t n_points, const int64_t *cell_pos, const double *bary, const int64_t *perm, const double *field,
+                       int nc, int col, double *out, int64_t ld, int64_t off, hipStream_t st) {
+  if (gdim != 2 && gdim != 3) OX_FAIL("%s: gdim=%d", who, gdim);
+  if (degree < 1 || degree > 3) OX_FAIL("%s: degree %d (1..3)", who, degree);
+  if (nc < 1 || nc > OX_MAXC || col < -1 || col >= nc) OX_FAIL("%s: nc=%d col=%d", who, nc, col);
+  const int nv = col < 0 ? nc : 1, col0 = col < 0 ? 0 : col;
+  if (off < 0 || ld < off + nv) OX_FAIL("%s: row of %lld values, %d at offset %lld", who, (long long)ld, nv, (long long)off);
+  if (n_points <= 0) return 0;
+  if (!cell_dofs || !cell_pos || !bary || !field || !out || n_cells < 1 || n_rows < 1) OX_FAIL("%s: null argument", who);
+  const dim3 grid((unsigned)((n_points + 255) / 256)), blk(256);
+#define OX_EVAL_CASE(D, G)                                                                                              \
+  hipLaunchKernelGGL((k_eval_points<D, G>), grid, blk, 0, st, n_points, cell_dofs, n_cells, n_rows, cell_pos, bary, perm, \
+                     field, nc, col0, nv, out + off, ld)
+  switch (gdim * 10 + degree) {
+    case 21: OX_EVAL_CASE(2, 1); break;
+    case 22: OX_EVAL_CASE(2, 2); break;
+    case 23: OX_EVAL_CASE(2, 3); break;
+    case 31: OX_EVAL_CASE(3, 1); break;
+    case 32: OX_EVAL_CASE(3, 2); break;
+    default: OX_EVAL_CASE(3, 3); break;
+  }
+#undef OX_EVAL_CASE
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ox_eval_points(int degree, int gdim, const int32_t *cell_dofs, int64_t n_cells, int64_t n_rows, int64_t n_points,
+                              const int64_t *cell_pos, const double *bary, const int64_t *perm, const double *field, int nc,
+                              int col, double *out, int64_t ld, int64_t off, void *stream) {
+  return eval_launch("ox_eval_points", degree, gdim, cell_dofs, n_cells, n_rows, n_points, cell_pos, bary, perm, field, nc,
+                     col, out, ld, off, ox_stream(stream));
+}
+
+extern "C" int ox_probe_sample(int degree, int gdim, const int32_t *cell_dofs, int64_t n_cells, int64_t n_rows, int64_t n_points,
+                               const int64_t *cell_pos, const double *bary, const int64_t *perm, const double *field, int nc,
+                               int col, double *ring, int64_t capacity, int64_t slot, int64_t ld, int64_t off, void *stream) {
+  if (n_points <= 0) return 0;
+  if (!ring || slot < 0 || slot >= capacity) OX_FAIL("ox_probe_sample: slot %lld of %lld", (long long)slot, (long long)capacity);
+  return eval_launch("ox_probe_sample", degree, gdim, cell_dofs, n_cells, n_rows, n_points, cell_pos, bary, perm, field, nc,
+                     col, ring + (size_t)slot * (size_t)n_points * (size_t)ld, ld, off, ox_stream(stream));
+}

@@ -1470,7 +1470,10 @@ class Function:
     def interpolate(self, f):
         """Nodal interpolation of ``f(x)``, x of shape (3, npts) (reference bcs.py:125,133)."""
         if isinstance(f, Function):
-            self.x.array[:] = f.x.array
+            if _same_layout(self.function_space, f.function_space):
+                self.x.array[:] = f.x.array
+                return
+            self._interpolate_from(f)
             return
         V = self.function_space
         if getattr(f, "supports_torch", False) and self._comp is not None:
@@ -1492,6 +1495,52 @@ class Function:
             self._storage.host()[:, :] = vals.reshape(dim, -1).T
         else:
             self.x.array[:] = vals.reshape(-1)
+
+    def _interpolate_from(self, f: "Function"):
+        """Nodal interpolation of a Function on ANOTHER space or mesh (P2 -> P1 on one mesh for output, a coarse solution
+        onto a fine mesh for a restart): this space's dof coordinates are located in ``f``'s mesh and ``f`` is evaluated
+        there on the device (geometry.eval_function).  One GPU."""
+        from . import geometry as G
+
+        V = self.function_space
+        Vs, Fs = G.scalar_space(V), G.scalar_space(f.function_space)
+        if Vs.part is not None or Fs.part is not None:
+            raise NotImplementedError("interpolate(Function) between different spaces on a mesh partition")
+        nv_f = f._storage.nc if f._comp is None else 1
+        nv = self._storage.nc if self._comp is None else 1
+        if nv != nv_f:
+            raise ValueError(f"interpolate: a function of {nv_f} value(s) into one of {nv}")
+        n = Vs.n_local
+        vals = G.eval_function(f, Vs.x[:n])
+        if bool(torch.isnan(vals).any()):
+            raise ValueError("interpolate: a dof of this space lies in no cell of the other function's mesh")
+        dst = self._storage.dev()
+        if self._comp is None:
+            dst[:n] = vals
+        else:
+            dst[:n, self._comp] = vals[:, 0]
+        self._storage.mark_written()
+
+    def eval(self, x, cells=None) -> np.ndarray:
+        """``dolfinx.fem.Function.eval``: values (n, value_size) at the points ``x`` ((n, 3) or (n, gdim), numpy or a
+        device tensor) of the mesh cells ``cells`` (a cell id of -1 gives a NaN row).  With ``cells=None`` the points are
+        located first (a convenience DOLFINx lacks): the lowest cell id containing each point; on a mesh partition points
+        that belong to another rank give NaN rows.  Evaluated on the device (csrc/ox_probe.hip); the field is read
+        through ``rptr()``: no write is recorded."""
+        from . import geometry as G
+
+        return G.eval_function(self, x, cells).cpu().numpy()
+
+
+def _same_layout(V, W) -> bool:
+    """Two spaces whose dof arrays correspond entry by entry: the same object, or the same mesh, kind and degree."""
+    if V is W:
+        return True
+    if getattr(V, "mesh", None) is not getattr(W, "mesh", None) or type(V) is not type(W):
+        return False
+    if isinstance(V, VectorFunctionSpace):
+        return V.dim == W.dim and _same_layout(V.scalar, W.scalar)
+    return getattr(V, "degree", None) == getattr(W, "degree", None) and getattr(V, "part", None) is getattr(W, "part", None)
 
 
 _marker_scope: dict | None = None  # see shared_marker_evaluations()
