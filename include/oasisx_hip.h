@@ -679,6 +679,20 @@ int ox_probe_sample(int degree, int gdim, const int32_t *cell_dofs, int64_t n_ce
                     const int64_t *cell_pos, const double *bary, const int64_t *perm, const double *field, int nc, int col,
                     double *ring, int64_t capacity, int64_t slot, int64_t ld, int64_t off, void *stream);
 
+/* ---- Passive scalar transport (ox_scalar.hip) ------------------------------------------------------------------------
+ * The Crank-Nicolson system of a group of 1..OX_MAXC scalars (same diffusivity kappa, same Dirichlet rows) from the
+ * matrices of the velocity step, in ONE pass over the shared SELL-64 pattern -- no element loop:
+ *   A   : the velocity matrix as ox_assemble_first* leaves it, M/dt + C(u_ab)/2 + nu K/2, BEFORE ox_zero_rows* on it
+ *   A_c = A + s K                           (s = (kappa - nu)/2; written to Ac->vals, padding slots stay 0)
+ *   b   = (2/dt) M c1 - A_c c1 + b0         (= (M/dt - C/2 - kappa K/2) c1 + b0; rows < n_rows)
+ *   a_c1 = A_c c1                            (optional, may be NULL: bit-identical to ox_spmv(Ac, c1), the solver's ax0)
+ * A, M, K, Ac share one pattern (equal slice_ptr); Ac has a value array of its own.  M and K are read through their
+ * 1-byte value codes where BOTH carry a dictionary, as f64 otherwise.  c1, b0, b, a_c1: interleaved (n, ncomp) device
+ * blocks.  The group's Dirichlet rows follow with ox_zero_rows_au(Ac, rows, n, 1.0, a_c1, c1, ncomp).  No atomics,
+ * fixed order of sums: two runs give the same bits. */
+int ox_scalar_rows(const ox_sell *A, const ox_sell *M, const ox_sell *K, const ox_sell *Ac, double s, double dt, int ncomp,
+                   const double *c1, const double *b0, double *b, double *a_c1, void *stream);
+
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */
 int ox_comm_create(const char *id128, int rank, int nranks, void **comm_out); /* ncclCommInitRank */

@@ -11,6 +11,7 @@ from .fracstep import FractionalStep_AB_CN
 from .function import Projector
 from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
+from .scalar import ScalarTransport
 
 logging.basicConfig()
 logger = logging.getLogger("oasisx")
@@ -22,4 +23,5 @@ __all__ = [
     "DirichletBC",
     "LocatorMethod",
     "PressureBC",
+    "ScalarTransport",
 ]

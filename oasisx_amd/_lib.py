@@ -302,6 +302,8 @@ SIGNATURES = {
     "ox_locator_bary": (_I, [_P, _L, _P, _P, _P, _P]),
     "ox_eval_points": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P]),
     "ox_probe_sample": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _L, _L, _P]),
+    "ox_scalar_rows": (_I, [C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _D, _D, _I,
+                            _P, _P, _P, _P, _P]),
     "ox_profile_begin": (_I, [_I, _I]),
     "ox_profile_end": (_I, []),
     "ox_profile_get": (_I, [_I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_D)]),

@@ -95,16 +95,20 @@ class FractionalStep_AB_CN:
         bcs_p: list of pressure BCs
         rotational: If True, use rotational form of pressure update
         solver_options: dict with keys ``'tentative'``, ``'pressure'``, ``'scalar'`` leading
-            to PETSc-style option dicts (see :mod:`oasisx_amd.ksp`)
+            to PETSc-style option dicts (see :mod:`oasisx_amd.ksp`); ``'scalar_transport'`` for the
+            passive scalars (default: the ``'tentative'`` options -- the operator is non-symmetric)
         jit_options: accepted for compatibility, ignored (nothing is JIT compiled)
         options: ``"low_memory_version"`` accepted (see module docstring)
         body_force: per direction a constant, a callable ``f(x)``, a Function of the component space or a
             :class:`oasisx_amd.function.Expression` of fields (assembled once, as in the reference)
+        scalars: list of :class:`oasisx_amd.ScalarTransport`: passive scalars on the velocity component space, advected by
+            the extrapolated velocity and solved once per step after the velocity update (:mod:`oasisx_amd.scalar`);
+            ``None`` / ``[]``: no scalar phase runs.  One GPU only
     """
 
     def __init__(self, mesh, u_element, p_element, bcs_u, bcs_p, rotational: bool = False,
                  solver_options: dict | None = None, jit_options: dict | None = None,
-                 body_force=None, options: dict | None = None):
+                 body_force=None, options: dict | None = None, scalars=None):
         self._lib = _lib.load()  # fails loudly when the HIP library is missing
         self._mesh = mesh
         gdim = mesh.geometry.dim
@@ -120,6 +124,10 @@ class FractionalStep_AB_CN:
         # ---- spaces (reference fracstep.py:186-216) ----------------------------------------
         comm = getattr(mesh, "comm", None)
         self._comm = comm
+        scalars = list(scalars or [])
+        if scalars and comm is not None and getattr(comm, "size", 1) > 1:
+            raise NotImplementedError("scalars= on a mesh-partitioned solver (comm.size > 1): the scalar pass is built for "
+                                      "one GPU; the halo-aware form does not exist yet")
         part = None
         if comm is not None and getattr(comm, "size", 1) > 1:
             from .parallel import MeshPartition
@@ -241,6 +249,18 @@ class FractionalStep_AB_CN:
         self._solver_c.setOperators(self._M)
         self._solver_u.setOperators(self._A)
         self._solver_u.setOptions(self._A)
+        # ---- passive scalars (scalar.py): groups of scalars that share one operator ----------------
+        self._scalar_groups, self._scalar_index = [], {}
+        self._A_pre_bc = False
+        if scalars:
+            from . import scalar as _sc
+
+            self._scalar_groups = _sc.build_groups(self, scalars, solver_options.get("scalar_transport",
+                                                                                     solver_options.get("tentative")))
+            for g in self._scalar_groups:
+                _sc.set_initial(self, g)
+                for j, m in enumerate(g.members):
+                    self._scalar_index[m.name] = (g, j)
         self.timings = {}
 
     # ------------------------------------------------------------------------------------
@@ -337,24 +357,32 @@ class FractionalStep_AB_CN:
                                            _lib.ptr(self._wQ), st), "ox_assemble_weights")
         B0 = self._B0.dev()
         for i, f in enumerate(self._body_force):
-            if isinstance(f, Function):  # a field of the component space: int f v dx = M f
-                if getattr(f.function_space, "scalar", f.function_space) is not Vi:
-                    raise ValueError("body_force: a Function must live on the velocity component space")
-                src = f._storage.rdev()[:, 0 if f._comp is None else f._comp].contiguous().unsqueeze(1)
-                tmp = torch.zeros(Vi.n_local, 1, dtype=torch.float64, device=dev)
-                self._M.mult(src, tmp, 1)
-                B0[: Vi.n_owned, i] = tmp[: Vi.n_owned, 0]
-            elif not isinstance(f, float):
-                # a spatial expression (or a pointwise expression of fields, function.Expression): tabulated at quadrature
-                # points, summed by ox_assemble_load_vector
-                from .function import load_vector, metadata_points
-
-                q = metadata_points({"quadrature_degree": self._options.get("body_force_quadrature_degree")}, Vi.degree)
-                B0[: Vi.n_owned, i] = load_vector(Vi, f, self._geom, q)[: Vi.n_owned]
-            else:
-                B0[: Vi.n_owned, i] = self._wV * float(f)
+            B0[: Vi.n_owned, i] = self._source_vector(f, "body_force")
         vol = float(self._wQ.sum().item())  # assemble_scalar(1*dx) + allreduce (:581-584)
         self._vol = vol if self._part is None else float(self._comm.allreduce(vol))
+
+    def _source_vector(self, f, what: str = "body_force"):
+        """int f v dx on the owned rows of the velocity component space for a float, a callable ``f(x)``, a Function of that
+        space or a :class:`oasisx_amd.function.Expression` (body force components, scalar sources)."""
+        from .function import Expression
+
+        Vi = self._Vi[0][0]
+        dev = self._mesh.device
+        if isinstance(f, Function):  # a field of the component space: int f v dx = M f
+            if getattr(f.function_space, "scalar", f.function_space) is not Vi:
+                raise ValueError(f"{what}: a Function must live on the velocity component space")
+            src = f._storage.rdev()[:, 0 if f._comp is None else f._comp].contiguous().unsqueeze(1)
+            tmp = torch.zeros(Vi.n_local, 1, dtype=torch.float64, device=dev)
+            self._M.mult(src, tmp, 1)
+            return tmp[: Vi.n_owned, 0]
+        if callable(f) or isinstance(f, Expression):
+            # a spatial expression (or a pointwise expression of fields, function.Expression): tabulated at quadrature
+            # points, summed by ox_assemble_load_vector
+            from .function import load_vector, metadata_points
+
+            q = metadata_points({"quadrature_degree": self._options.get("body_force_quadrature_degree")}, Vi.degree)
+            return load_vector(Vi, f, self._geom, q)[: Vi.n_owned]
+        return self._wV * float(f)
 
     # ------------------------------------------------------------------------------------
     @_phase
@@ -392,6 +420,12 @@ class FractionalStep_AB_CN:
                                                 float(dt), float(nu), nb, bptr, bsl, bw, st,
                                                 self._B3.ptr() if want_au else None), "ox_assemble_first")
         self._A.version += 1
+        if self._scalar_groups:  # A still is M/dt + C/2 + nu K/2 on EVERY row: the scalars' operators come from it
+            self._A_pre_bc = True
+            try:
+                self.scalar_assemble(dt, nu)
+            finally:
+                self._A_pre_bc = False
         # outlet terms int h n_i dv/dx_i ds (:445-446, :461-465)
         for bcp in self._bcs_p:
             bcp.update_bc()
@@ -524,6 +558,42 @@ class FractionalStep_AB_CN:
                        "ox_assemble_grad_vector")
         return np.asarray(self._solver_c.solve_block(self._B3, self._U, ax0=MU), dtype=np.int32)
 
+    @_phase
+    def scalar_assemble(self, dt: float, nu: float):
+        """Per scalar group: A_c = A + (kappa - nu)/2 K, b_c = (2/dt) M c_1 - A_c c_1 + b0_c and, for a solver with a nonzero
+        initial guess, A_c c_1 -- one pass over the values of the shared pattern (``ox_scalar_rows``); then the group's own
+        Dirichlet rows.  Runs INSIDE ``assemble_first``, between the fused kernel and the velocity's boundary rows:
+        afterwards those rows of ``A`` are gone."""
+        if not self._A_pre_bc:
+            raise RuntimeError("scalar_assemble runs inside assemble_first (which calls it): afterwards the velocity's "
+                               "Dirichlet rows of A have been replaced and the scalar operator cannot be formed from it")
+        from . import scalar as _sc
+
+        for g in self._scalar_groups:
+            _sc.assemble(self, g, dt, nu)
+
+    @_phase
+    def scalar_solve(self) -> dict:
+        """Solve every scalar group (columns in lock-step), then c_1 <- c.  Returns {name: converged reason}."""
+        from . import scalar as _sc
+
+        out = {}
+        for g in self._scalar_groups:
+            reasons = _sc.solve(self, g)
+            for j, m in enumerate(g.members):
+                out[m.name] = int(reasons[j])
+        return out
+
+    def scalar(self, name: str, level: int = 0) -> Function:
+        """The scalar ``name``: the current level ``c`` (``level=0``) or the previous one ``c_1`` (``level=1``), from which
+        the next step starts -- write initial data there."""
+        if name not in self._scalar_index:
+            raise KeyError(f"no scalar named {name!r} (have: {sorted(self._scalar_index)})")
+        if level not in (0, 1):
+            raise ValueError("scalar: level is 0 (c) or 1 (c_1)")
+        g, j = self._scalar_index[name]
+        return (g.c if level == 0 else g.c1)[j]
+
     def solve(self, dt: float, nu: float, max_error: float = 1e-12, max_iter: int = 10):
         """Propagate the splitting scheme one time step (reference fracstep.py:660-696)."""
         lib, st = self._lib, _lib.current_stream()
@@ -534,6 +604,10 @@ class FractionalStep_AB_CN:
         for bcu in self._bcs_u:
             for bc in bcu:
                 bc.update_bc()
+        for g in self._scalar_groups:
+            for m in g.members:
+                for bc in m.bcs:
+                    bc.update_bc()
         self.assemble_first(dt, nu)
         while inner_it < max_iter and diff > max_error:
             inner_it += 1
@@ -545,6 +619,9 @@ class FractionalStep_AB_CN:
             assert int(error_p) > 0, f"pressure solve failed: {error_p}"
         errors_c = self.velocity_update(dt)
         self._last_errors = (errors, error_p, errors_c)
+        if self._scalar_groups:  # after the velocity update (Oasis' order); u_ab of this step is in the operator already
+            reasons = self.scalar_solve()
+            assert all(r > 0 for r in reasons.values()), f"scalar transport solve failed: {reasons}"
         # u2 <- u1, u1 <- u, p <- ps (:689-693)
         _lib.check(lib.ox_axpby(n, 1.0, self._U1.ptr(), 0.0, None, self._U2.ptr(), st), "ox_axpby")
         _lib.check(lib.ox_axpby(n, 1.0, self._U.ptr(), 0.0, None, self._U1.ptr(), st), "ox_axpby")
@@ -562,5 +639,9 @@ class FractionalStep_AB_CN:
         return self._sol_u
 
     def iteration_counts(self):
-        return {"tentative": self._solver_u.iterations, "pressure": self._solver_p.iterations,
-                "update": self._solver_c.iterations}
+        its = {"tentative": self._solver_u.iterations, "pressure": self._solver_p.iterations,
+               "update": self._solver_c.iterations}
+        if self._scalar_groups:
+            its["scalar_transport"] = {m.name: (g.ksp.iterations[j] if g.ksp.iterations else None)
+                                       for g in self._scalar_groups for j, m in enumerate(g.members)}
+        return its
