@@ -469,6 +469,30 @@ int ox_assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *c
                              double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
                              double *a_u1);
 
+/* ---- eddy-viscosity models: a viscosity per cell in the fused assemble_first ---- */
+/* nut[e], e in kernel cell order (the order of cells->geom and cell_dofs), from grad uab at the cell's centroid:
+ * model 0, Smagorinsky: (coefficient Delta)^2 sqrt(2 S:S); model 1, WALE (gdim = 3 only):
+ * (coefficient Delta)^2 (Sd:Sd)^(3/2) / ((S:S)^(5/2) + (Sd:Sd)^(5/4)), 0 where the denominator is 0; S = sym(grad uab),
+ * Sd = sym(g g) - tr(g g)/3 I with g = grad uab, Delta = |cell|^(1/gdim).  uab interleaved [n_u][gdim], cell_dofs
+ * [n_cells][nd] of the velocity component space of `degree` (1, 2, 3).  One lane per cell. */
+int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
+                      double coefficient, double *nut, void *stream);
+/* ox_assemble_first_au / ox_assemble_first_blocks with C replaced by C + sum_e nut[e] K_e (K_e: the stiffness matrix of
+ * cell e), i.e. A = M/dt + C/2 + (nu K + K_nut)/2 and b_first to match: the Laplacian form div(nut grad u) of a viscosity
+ * that varies per cell.  nut: device [n_cells], kernel cell order, not NULL.  Same launch forms, same epilogue, a_u1 as
+ * there; nut = 0 everywhere gives the bits of the plain entry points. */
+int ox_assemble_first_au_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs,
+                             const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
+                             const ox_sell *M, const ox_sell *K, const double *uab,
+                             const double *u1, const double *b0, double *b_first, double dt, double nu,
+                             int n_bins, const int64_t *bin_ptr_host, const int32_t *bin_slices,
+                             const int32_t *bin_width_host, void *stream, double *a_u1, const double *nut);
+int ox_assemble_first_blocks_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
+                                 const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
+                                 const double *uab, const double *u1, const double *b0, double *b_first, double dt,
+                                 double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
+                                 double *a_u1, const double *nut);
+
 /* ---- A6 / A8: assemble_vector(p * v.dx(i) * dx) and (dp.dx(i) * v * dx), all i at once
  *      (fracstep.py:487-497 and :618).  kind 0: out[r][i] = base[r][i] + scale * int p d_i(phi_r)
  *      kind 1: out[r][i] = base[r][i] + scale * int d_i(p) phi_r.  base may be NULL (=0). */

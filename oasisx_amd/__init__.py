@@ -12,6 +12,7 @@ from .function import Projector
 from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .scalar import ScalarTransport
+from .viscosity import CellViscosity, Smagorinsky, Wale
 
 logging.basicConfig()
 logger = logging.getLogger("oasisx")
@@ -24,4 +25,7 @@ __all__ = [
     "LocatorMethod",
     "PressureBC",
     "ScalarTransport",
+    "Smagorinsky",
+    "Wale",
+    "CellViscosity",
 ]

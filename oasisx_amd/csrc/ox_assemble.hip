@@ -175,6 +175,47 @@ __device__ __forceinline__ const ConvTab<GDIM, DEG> &ct() {
   else return CT32;
 }
 
+// The stiffness row as the same kind of contraction (eddy-viscosity models): with GG[a][b] =
+// G[a] . G[b],  K_e[i][j] = |J| sum_(a, b) GG[a][b] int d(phi_i)/d(lambda_a) d(phi_j)/d(lambda_b), so
+//   nut K_e[i][j] / |J| = sum_b sum_a S[i][a][(j, b)] (nut GG[a][b]),   S[i][a][(j, b)] = sum_q w_q dphi_i(q, a) dphi_j(q, b)
+// -- the sums of the OX_KIND_STIFF branch with the quadrature sum taken first, at compile time, on the same rule and over
+// the same (j, b) pairs as ConvTab.  A lane adds GDIM + 1 "k" turns to the convection contraction: 64 FMAs per pair for P2
+// tetrahedra instead of the 616 the quadrature form of OX_KIND_STIFF spends, and no registers beyond GG.
+template <int GDIM, int DEG>
+struct StiffTab {
+  using E = Elem<GDIM, DEG>;
+  static constexpr int NCB = COMBOS<GDIM, DEG>.n;
+  double t[E::ND][GDIM + 1][NCB];
+};
+template <int GDIM, int DEG>
+constexpr StiffTab<GDIM, DEG> make_stiff() {
+  using E = Elem<GDIM, DEG>;
+  StiffTab<GDIM, DEG> T{};
+  constexpr auto CB = COMBOS<GDIM, DEG>;
+  for (int i = 0; i < E::ND; ++i)
+    for (int a = 0; a <= GDIM; ++a)
+      for (int m = 0; m < CB.n; ++m) {
+        double s = 0.0;
+        for (int q = 0; q < E::NQ; ++q) s += E::w(q) * E::dphi(q, i, a) * E::dphi(q, CB.j[m], CB.b[m]);
+        T.t[i][a][m] = s;
+      }
+  return T;
+}
+__device__ const StiffTab<2, 1> ST21 = make_stiff<2, 1>();
+__device__ const StiffTab<2, 2> ST22 = make_stiff<2, 2>();
+__device__ const StiffTab<3, 1> ST31 = make_stiff<3, 1>();
+__device__ const StiffTab<3, 2> ST32 = make_stiff<3, 2>();
+__device__ const StiffTab<2, 3> ST23 = make_stiff<2, 3>();
+template <int GDIM, int DEG>
+__device__ __forceinline__ const StiffTab<GDIM, DEG> &st_tab() {
+  static_assert(!(GDIM == 3 && DEG == 3), "P3 tetrahedra: stiffness by quadrature, merged into the convection points");
+  if constexpr (DEG == 3) return ST23;
+  else if constexpr (GDIM == 2 && DEG == 1) return ST21;
+  else if constexpr (GDIM == 2 && DEG == 2) return ST22;
+  else if constexpr (GDIM == 3 && DEG == 1) return ST31;
+  else return ST32;
+}
+
 // P3 on tetrahedra: the tensor T[i][k][(j, b)] the kernels above read from LDS would be 20 x 20 x 60 doubles = 192 KB --
 // it does not fit.  The convection rows of that element are formed by QUADRATURE at run time instead: the values and
 // derivatives of all 20 basis functions at the 70 points sit in device memory and are read with wave-uniform indices
@@ -194,6 +235,16 @@ constexpr QuadTab33 make_qt33() {
   return t;
 }
 __device__ const QuadTab33 QT33 = make_qt33();
+// (the rule's weights alone: the weighted stiffness rows of the NUT form of that path)
+struct QuadW33 {
+  double w[OX_NQ3H];
+};
+constexpr QuadW33 make_qw33() {
+  QuadW33 t{};
+  for (int q = 0; q < OX_NQ3H; ++q) t.w[q] = OX_QW3H[q];
+  return t;
+}
+__device__ const QuadW33 QW33 = make_qw33();
 template <int GDIM, int DEG>
 inline constexpr bool OX_CONV_BY_QUADRATURE = (GDIM == 3 && DEG == 3);
 
@@ -231,6 +282,15 @@ struct FirstArgs {
             // pair loop, bit 1 the epilogue -- wrong results, for timing the two halves
 #endif
 };
+// NUT (eddy-viscosity models): a viscosity per cell, nut[e] in kernel cell order, whose weighted
+// stiffness rows the pair loop adds to the convection rows.  The field exists in the NUT instantiations only: the others
+// keep the argument block -- and the code -- they had.
+template <bool NUT>
+struct FirstArgsT : FirstArgs {};
+template <>
+struct FirstArgsT<true> : FirstArgs {
+  const double *nut;
+};
 #ifdef OX_DIAG
 #define OX_AF_SKIP_PAIRS(F) ((F).dbg & 1)
 #define OX_AF_SKIP_EPILOGUE(F) ((F).dbg & 2)
@@ -250,9 +310,9 @@ struct FirstArgs {
 //    for ~22 GB of streams, profiles/r04b_delaunay_pmc_hbm.csv); in storage order the ten rows of a cell pass through
 //    one L2 within a few blocks of each other.  Same per-slice arithmetic either way: bit-identical results.
 // one slice: the (row, cell) pair loop into the wave-private LDS accumulator `acc`, then the epilogue
-template <int GDIM, int DEG, int KIND, int PW, bool DICT, int U>
+template <int GDIM, int DEG, int KIND, int PW, bool DICT, int U, bool NUT = false>
 __device__ __forceinline__ void assemble_slice(const ox_cells &cells, const int32_t *__restrict__ cell_dofs, const ox_adj &adj,
-                                               const uint8_t *__restrict__ adj_pos, const ox_sell &A, const FirstArgs &F,
+                                               const uint8_t *__restrict__ adj_pos, const ox_sell &A, const FirstArgsT<NUT> &F,
                                                const int slice, double *acc, const int lane, const double *tconv,
                                                const double *dM, const double *dK) {
   using E = Elem<GDIM, DEG>;
@@ -260,6 +320,8 @@ __device__ __forceinline__ void assemble_slice(const ox_cells &cells, const int3
   constexpr bool QUAD = OX_CONV_BY_QUADRATURE<GDIM, DEG>;
   constexpr int NCB = QUAD ? 1 : COMBOS<GDIM, DEG>.n;
   constexpr int TS = NCB * ND + 2;
+  constexpr int SS = NCB * (GDIM + 1) + 2;  // (NUT) doubles per row dof of the stiffness tensor, padded like TS
+  static_assert(!NUT || KIND == OX_KIND_CONV, "a per-cell viscosity enters the fused assemble_first only");
   const int64_t base = A.slice_ptr[slice];
   const int width = (int)((A.slice_ptr[slice + 1] - base) >> 6);
   for (int k = 0; k < width; ++k) acc[k * 64 + lane] = 0.0;
@@ -294,9 +356,11 @@ __device__ __forceinline__ void assemble_slice(const ox_cells &cells, const int3
       }
     }
     double G[U][GDIM + 1][GDIM], adet[U];
+    double nutv[U];  // (NUT only) the cell's eddy viscosity: indexed by e like the geometry, the same memory round
     int32_t dd[U][KIND == OX_KIND_CONV ? ND : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      if constexpr (NUT) nutv[u] = F.nut[e[u]];
 #ifdef OX_DIAG
       // (OX_AF_DBG bit 2, diagnostic builds only: every pair reads one of 8 cells' geometry -- L1 hits --: what a
       // dictionary of the cell geometry could save at most)
@@ -393,6 +457,25 @@ __device__ __forceinline__ void assemble_slice(const ox_cells &cells, const int3
             for (int d = 0; d < GDIM; ++d) v = fma(G[u][b][d], uq[d], v);
             sb[b - 1] = wq * v;
           }
+          if constexpr (NUT) {
+            // + nut K_e[i][j] = nut sum_q w_q grad(phi_i) . grad(phi_j): w_q nut G[b] . grad(phi_i) multiplies the same
+            // d(phi_j)/d(lambda_b) as w_q phi_i beta_b does (the arithmetic of the OX_KIND_STIFF branch; lambda_0 column zero)
+            double gi[GDIM];
+#pragma unroll
+            for (int d = 0; d < GDIM; ++d) {
+              gi[d] = 0.0;
+#pragma unroll
+              for (int b = 1; b <= GDIM; ++b) gi[d] = fma(R.dphi[i][q][b], G[u][b][d], gi[d]);
+            }
+            const double wn = QW33.w[q] * nutv[u];
+#pragma unroll
+            for (int b = 1; b <= GDIM; ++b) {
+              double h = 0.0;
+#pragma unroll
+              for (int d = 0; d < GDIM; ++d) h = fma(G[u][b][d], gi[d], h);
+              sb[b - 1] = fma(wn, h, sb[b - 1]);
+            }
+          }
 #pragma unroll
           for (int j = 0; j < ND; ++j) {
 #pragma unroll
@@ -419,6 +502,25 @@ __device__ __forceinline__ void assemble_slice(const ox_cells &cells, const int3
           }
 #pragma unroll
           for (int m = 0; m < NCB; ++m) cm[m] = fma(ti[k * NCB + m], gam[CB.b[m]], cm[m]);
+        }
+        if constexpr (NUT) {
+          // + nut K_e[i][j] / |J| = sum_(a, b) S[i][a][(j, b)] (nut G[a] . G[b]) (StiffTab): GDIM + 1 more turns of the
+          // same contraction on the same NCB accumulators
+          const double *__restrict__ si = tconv + ND * TS + i * SS;
+          double gg[GDIM + 1][GDIM + 1];
+#pragma unroll
+          for (int a = 0; a <= GDIM; ++a)
+#pragma unroll
+            for (int b = a; b <= GDIM; ++b) {
+              double v = 0.0;
+#pragma unroll
+              for (int d = 0; d < GDIM; ++d) v = fma(G[u][a][d], G[u][b][d], v);
+              gg[a][b] = gg[b][a] = nutv[u] * v;
+            }
+#pragma unroll
+          for (int a = 0; a <= GDIM; ++a)
+#pragma unroll
+            for (int m = 0; m < NCB; ++m) cm[m] = fma(si[a * NCB + m], gg[a][CB.b[m]], cm[m]);
         }
 #pragma unroll
         for (int m = 0; m < NCB; ++m) c[CB.j[m]] += cm[m];
@@ -518,10 +620,10 @@ __device__ __forceinline__ void assemble_slice(const ox_cells &cells, const int3
   }
 }
 
-template <int GDIM, int DEG, int KIND, int PW, bool DICT = false, int U = 1, bool BLK = false>
+template <int GDIM, int DEG, int KIND, int PW, bool DICT = false, int U = 1, bool BLK = false, bool NUT = false>
 __global__ __launch_bounds__(BLK ? 512 : 256) void k_assemble_rows(ox_cells cells, const int32_t *__restrict__ cell_dofs,
                                                        ox_adj adj, const uint8_t *__restrict__ adj_pos,
-                                                       ox_sell A, FirstArgs F,
+                                                       ox_sell A, FirstArgsT<NUT> F,
                                                        const int32_t *__restrict__ slice_list, int n_list,
                                                        int bin_width) {
   using E = Elem<GDIM, DEG>;
@@ -533,7 +635,8 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_assemble_rows(ox_cells cell
   extern __shared__ double acc_all[];  // [4 waves][bin_width][64]  (BLK: the row block's slices back to back)
   __shared__ double dM[DICT ? 256 : 1], dK[DICT ? 256 : 1];
   // (P3 tetrahedra: w_q phi_i(x_q), [ND][NQ], for the quadrature form of the convection rows)
-  __shared__ __attribute__((aligned(16))) double tconv[KIND == OX_KIND_CONV ? (QUAD ? ND * E::NQ : ND * TS) : 2];
+  constexpr int SS = NCB * (GDIM + 1) + 2;  // (NUT: the stiffness tensor of StiffTab behind the convection tensor)
+  __shared__ __attribute__((aligned(16))) double tconv[KIND == OX_KIND_CONV ? (QUAD ? ND * E::NQ : ND * TS + (NUT ? ND * SS : 0)) : 2];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int nthr = blockDim.x, nwave = blockDim.x >> 6;  // 4 waves per block, fewer for very wide rows
   if constexpr (DICT) {
@@ -561,6 +664,14 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_assemble_rows(ox_cells cell
       }
     }
   }
+  if constexpr (NUT && !QUAD) {
+    const double *src = &st_tab<GDIM, DEG>().t[0][0][0];
+    constexpr int PER_I = (GDIM + 1) * NCB;
+    for (int idx = threadIdx.x; idx < ND * PER_I; idx += nthr) {
+      const int i = idx / PER_I;
+      tconv[ND * TS + i * SS + (idx - i * PER_I)] = src[idx];
+    }
+  }
   if constexpr (DICT || KIND == OX_KIND_CONV) __syncthreads();
   if constexpr (BLK) {
     // one block per row block; the blocks of one XCD take a contiguous eighth of them.  (A PERSISTENT grid -- one block per
@@ -572,7 +683,7 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_assemble_rows(ox_cells cell
     const int slice = s0 + wave;
     if (slice >= slice_list[b + 1]) return;
     // (consecutive slices: the entries before this one)
-    assemble_slice<GDIM, DEG, KIND, PW, DICT, U>(cells, cell_dofs, adj, adj_pos, A, F, slice,
+    assemble_slice<GDIM, DEG, KIND, PW, DICT, U, NUT>(cells, cell_dofs, adj, adj_pos, A, F, slice,
                                                  acc_all + (A.slice_ptr[slice] - A.slice_ptr[s0]), lane, tconv, dM, dK);
   } else {
     // 4 slices of the bin per block; blocks that share an XCD (equal blockIdx % 8) take one contiguous
@@ -581,19 +692,19 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_assemble_rows(ox_cells cell
     // its cell; with the chunked order 24.4 GB)
     const int li = ox_xcd_remap(blockIdx.x, gridDim.x) * nwave + wave;
     if (li >= n_list) return;
-    assemble_slice<GDIM, DEG, KIND, PW, DICT, U>(cells, cell_dofs, adj, adj_pos, A, F, slice_list[li],
+    assemble_slice<GDIM, DEG, KIND, PW, DICT, U, NUT>(cells, cell_dofs, adj, adj_pos, A, F, slice_list[li],
                                                  acc_all + (size_t)wave * bin_width * 64, lane, tconv, dM, dK);
   }
 }
 
-template <int GDIM, int DEG, int KIND, int PW, bool DICT = false>
+template <int GDIM, int DEG, int KIND, int PW, bool DICT = false, bool NUT = false>
 static int launch_rows_t(const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                         const uint8_t *adj_pos, const ox_sell *A, const FirstArgs &F, int n_bins,
+                         const uint8_t *adj_pos, const ox_sell *A, const FirstArgsT<NUT> &F, int n_bins,
                          const int64_t *bin_ptr, const int32_t *bin_slices, const int32_t *bin_width,
                          hipStream_t st) {
   if constexpr (KIND == OX_KIND_CONV && !DICT) {
     if (F.Mc && F.Kc && F.Md && F.Kd && F.nMd >= 1 && F.nMd <= 256 && F.nKd >= 1 && F.nKd <= 256)
-      return launch_rows_t<GDIM, DEG, KIND, PW, true>(cells, cell_dofs, adj, adj_pos, A, F, n_bins, bin_ptr,
+      return launch_rows_t<GDIM, DEG, KIND, PW, true, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_bins, bin_ptr,
                                                       bin_slices, bin_width, st);
   }
   for (int b = 0; b < n_bins; ++b) {
@@ -601,10 +712,12 @@ static int launch_rows_t(const ox_cells *cells, const int32_t *cell_dofs, const 
     if (cnt <= 0) continue;
     // wave-private accumulators [width][64]; 4 waves per block unless the rows are so wide (unstructured
     // meshes: > 70 entries) that fewer fit beside the 17 KB of tables
+    // (NUT: 134 KB, the row blocks' budget -- the stiffness tensor takes up to 5 KB of LDS more)
+    constexpr size_t CAP = NUT ? OX_ROW_BLOCK_LDS : 140 * 1024;
     int nw = 4;
-    while (nw > 1 && (size_t)nw * bin_width[b] * 64 * sizeof(double) > 140 * 1024) nw >>= 1;
+    while (nw > 1 && (size_t)nw * bin_width[b] * 64 * sizeof(double) > CAP) nw >>= 1;
     const size_t lds = (size_t)nw * bin_width[b] * 64 * sizeof(double);
-    if (lds > 140 * 1024) OX_FAIL("assemble: row width %d needs %zu B of LDS", bin_width[b], lds);
+    if (lds > CAP) OX_FAIL("assemble: row width %d needs %zu B of LDS", bin_width[b], lds);
     // (U = 2 / 3 (row, cell) pairs in flight per lane were measured at 128^3 -- 9.0 / 9.3 ms against 7.7 with one: the
     // pair loop is bound by the texture path, every lane gathering from another cell, not by latency -- and their
     // instantiations and the OX_ASSEMBLE_U / OX_ASSEMBLE_NW tuning switches removed in round 5)
@@ -617,25 +730,25 @@ static int launch_rows_t(const ox_cells *cells, const int32_t *cell_dofs, const 
       OX_LAUNCH_CHECK();
       return 0;
     };
-    const int rc = go(k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1>);
+    const int rc = go(k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1, false, NUT>);
     if (rc) return rc;
   }
   return 0;
 }
 
 // row-block launch (k_assemble_rows<..., BLK = true>): one launch, 8 waves per block
-template <int GDIM, int DEG, int KIND, int PW, bool DICT = false>
+template <int GDIM, int DEG, int KIND, int PW, bool DICT = false, bool NUT = false>
 static int launch_row_blocks_t(const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj, const uint8_t *adj_pos,
-                               const ox_sell *A, const FirstArgs &F, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries,
+                               const ox_sell *A, const FirstArgsT<NUT> &F, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries,
                                hipStream_t st) {
   if constexpr (KIND == OX_KIND_CONV && !DICT) {
     if (F.Mc && F.Kc && F.Md && F.Kd && F.nMd >= 1 && F.nMd <= 256 && F.nKd >= 1 && F.nKd <= 256)
-      return launch_row_blocks_t<GDIM, DEG, KIND, PW, true>(cells, cell_dofs, adj, adj_pos, A, F, n_blocks, blk_ptr, lds_entries, st);
+      return launch_row_blocks_t<GDIM, DEG, KIND, PW, true, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_blocks, blk_ptr, lds_entries, st);
   }
   if (n_blocks <= 0) return 0;
   const size_t lds = (size_t)lds_entries * sizeof(double);
   if (lds > OX_ROW_BLOCK_LDS) OX_FAIL("assemble: a row block needs %zu B of LDS (limit %d)", lds, OX_ROW_BLOCK_LDS);
-  auto kern = k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1, true>;
+  auto kern = k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1, true, NUT>;
   if (lds > 32 * 1024)
     OX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)n_blocks), dim3(512), lds, st, *cells, cell_dofs, *adj, adj_pos, *A, F, blk_ptr,
@@ -643,31 +756,31 @@ static int launch_row_blocks_t(const ox_cells *cells, const int32_t *cell_dofs, 
   OX_LAUNCH_CHECK();
   return 0;
 }
-template <int KIND>
+template <int KIND, bool NUT = false>
 static int launch_row_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                             const uint8_t *adj_pos, int pw, const ox_sell *A, const FirstArgs &F, int n_blocks,
+                             const uint8_t *adj_pos, int pw, const ox_sell *A, const FirstArgsT<NUT> &F, int n_blocks,
                              const int32_t *blk_ptr, int64_t lds_entries, hipStream_t st) {
   const int g = cells->gdim;
 #define OX_ROWS_CASE(GD, DG, P)                                                                                       \
   if (g == GD && degree == DG) {                                                                                      \
     if (pw != P) OX_FAIL("assemble: adj_pos stride %d, expected %d", pw, P);                                          \
-    return launch_row_blocks_t<GD, DG, KIND, P>(cells, cell_dofs, adj, adj_pos, A, F, n_blocks, blk_ptr, lds_entries, st); \
+    return launch_row_blocks_t<GD, DG, KIND, P, false, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_blocks, blk_ptr, lds_entries, st); \
   }
   OX_ROWS_CASE(2, 1, 4) OX_ROWS_CASE(2, 2, 8) OX_ROWS_CASE(3, 1, 4) OX_ROWS_CASE(3, 2, 16) OX_ROWS_CASE(2, 3, 16) OX_ROWS_CASE(3, 3, 32)
 #undef OX_ROWS_CASE
   OX_FAIL("assemble: unsupported gdim=%d degree=%d", g, degree);
 }
 
-template <int KIND>
+template <int KIND, bool NUT = false>
 static int launch_rows(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                       const uint8_t *adj_pos, int pw, const ox_sell *A, const FirstArgs &F,
+                       const uint8_t *adj_pos, int pw, const ox_sell *A, const FirstArgsT<NUT> &F,
                        int n_bins, const int64_t *bin_ptr, const int32_t *bin_slices,
                        const int32_t *bin_width, hipStream_t st) {
   const int g = cells->gdim;
 #define OX_ROWS_CASE(GD, DG, P)                                                               \
   if (g == GD && degree == DG) {                                                              \
     if (pw != P) OX_FAIL("assemble: adj_pos stride %d, expected %d", pw, P);                  \
-    return launch_rows_t<GD, DG, KIND, P>(cells, cell_dofs, adj, adj_pos, A, F, n_bins, bin_ptr, \
+    return launch_rows_t<GD, DG, KIND, P, false, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_bins, bin_ptr, \
                                           bin_slices, bin_width, st);                         \
   }
   OX_ROWS_CASE(2, 1, 4) OX_ROWS_CASE(2, 2, 8) OX_ROWS_CASE(3, 1, 4) OX_ROWS_CASE(3, 2, 16) OX_ROWS_CASE(2, 3, 16) OX_ROWS_CASE(3, 3, 32)
@@ -680,7 +793,7 @@ extern "C" int ox_assemble_matrix(int kind, int degree, const ox_cells *cells, c
                                   int n_bins, const int64_t *bin_ptr_host, const int32_t *bin_slices,
                                   const int32_t *bin_width_host, void *stream) {
   if (!cells || !cell_dofs || !adj || !adj_pos || !A) OX_FAIL("ox_assemble_matrix: null argument");
-  FirstArgs F{};
+  FirstArgsT<false> F{};
   hipStream_t st = ox_stream(stream);
   if (kind == OX_KIND_MASS)
     return launch_rows<OX_KIND_MASS>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_bins,
@@ -691,13 +804,14 @@ extern "C" int ox_assemble_matrix(int kind, int degree, const ox_cells *cells, c
   OX_FAIL("ox_assemble_matrix: kind=%d", kind);
 }
 
-extern "C" int ox_assemble_first_au(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                                    const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                                    const ox_sell *M, const ox_sell *K, const double *uab,
-                                    const double *u1, const double *b0, double *b_first, double dt,
-                                    double nu, int n_bins, const int64_t *bin_ptr_host,
-                                    const int32_t *bin_slices, const int32_t *bin_width_host,
-                                    void *stream, double *a_u1) {
+// nut == nullptr: the constant-viscosity form, the instantiations and argument blocks of before
+static int assemble_first_bins(int degree, const ox_cells *cells, const int32_t *cell_dofs,
+                               const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
+                               const ox_sell *M, const ox_sell *K, const double *uab,
+                               const double *u1, const double *b0, double *b_first, double dt,
+                               double nu, int n_bins, const int64_t *bin_ptr_host,
+                               const int32_t *bin_slices, const int32_t *bin_width_host,
+                               void *stream, double *a_u1, const double *nut) {
   if (!cells || !cell_dofs || !adj || !adj_pos || !A || !M || !K || !M->vals || !K->vals || !uab || !u1 ||
       !b0 || !b_first)
     OX_FAIL("ox_assemble_first: null argument");
@@ -713,10 +827,44 @@ extern "C" int ox_assemble_first_au(int degree, const ox_cells *cells, const int
   }
 #endif
   if (ox_prof_on) ox_prof_start(OX_TAG_ASSEMBLE_FIRST, ox_stream(stream));
-  const int rc = launch_rows<OX_KIND_CONV>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_bins,
-                                           bin_ptr_host, bin_slices, bin_width_host, ox_stream(stream));
+  int rc;
+  if (nut) {
+    FirstArgsT<true> Fn{};
+    static_cast<FirstArgs &>(Fn) = F;
+    Fn.nut = nut;
+    rc = launch_rows<OX_KIND_CONV, true>(degree, cells, cell_dofs, adj, adj_pos, pw, A, Fn, n_bins, bin_ptr_host, bin_slices,
+                                         bin_width_host, ox_stream(stream));
+  } else {
+    FirstArgsT<false> F0{};
+    static_cast<FirstArgs &>(F0) = F;
+    rc = launch_rows<OX_KIND_CONV>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F0, n_bins,
+                                   bin_ptr_host, bin_slices, bin_width_host, ox_stream(stream));
+  }
   if (ox_prof_on) ox_prof_stop(ox_stream(stream));
   return rc;
+}
+
+extern "C" int ox_assemble_first_au(int degree, const ox_cells *cells, const int32_t *cell_dofs,
+                                    const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
+                                    const ox_sell *M, const ox_sell *K, const double *uab,
+                                    const double *u1, const double *b0, double *b_first, double dt,
+                                    double nu, int n_bins, const int64_t *bin_ptr_host,
+                                    const int32_t *bin_slices, const int32_t *bin_width_host,
+                                    void *stream, double *a_u1) {
+  return assemble_first_bins(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_bins,
+                             bin_ptr_host, bin_slices, bin_width_host, stream, a_u1, nullptr);
+}
+
+extern "C" int ox_assemble_first_au_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs,
+                                        const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
+                                        const ox_sell *M, const ox_sell *K, const double *uab,
+                                        const double *u1, const double *b0, double *b_first, double dt,
+                                        double nu, int n_bins, const int64_t *bin_ptr_host,
+                                        const int32_t *bin_slices, const int32_t *bin_width_host,
+                                        void *stream, double *a_u1, const double *nut) {
+  if (!nut) OX_FAIL("ox_assemble_first_au_nut: null nut (the constant-viscosity form is ox_assemble_first_au)");
+  return assemble_first_bins(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_bins,
+                             bin_ptr_host, bin_slices, bin_width_host, stream, a_u1, nut);
 }
 
 extern "C" int ox_assemble_first(int degree, const ox_cells *cells, const int32_t *cell_dofs,
@@ -734,7 +882,7 @@ extern "C" int ox_assemble_matrix_blocks(int kind, int degree, const ox_cells *c
                                          const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A, int n_blocks,
                                          const int32_t *blk_ptr, int64_t lds_entries, void *stream) {
   if (!cells || !cell_dofs || !adj || !adj_pos || !A || (n_blocks > 0 && !blk_ptr)) OX_FAIL("ox_assemble_matrix_blocks: null argument");
-  FirstArgs F{};
+  FirstArgsT<false> F{};
   hipStream_t st = ox_stream(stream);
   if (kind == OX_KIND_MASS)
     return launch_row_blocks<OX_KIND_MASS>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_blocks, blk_ptr, lds_entries, st);
@@ -743,11 +891,11 @@ extern "C" int ox_assemble_matrix_blocks(int kind, int degree, const ox_cells *c
   OX_FAIL("ox_assemble_matrix_blocks: kind=%d", kind);
 }
 
-extern "C" int ox_assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                                        const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
-                                        const double *uab, const double *u1, const double *b0, double *b_first, double dt,
-                                        double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
-                                        double *a_u1) {
+static int assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
+                                 const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
+                                 const double *uab, const double *u1, const double *b0, double *b_first, double dt,
+                                 double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
+                                 double *a_u1, const double *nut) {
   if (!cells || !cell_dofs || !adj || !adj_pos || !A || !M || !K || !M->vals || !K->vals || !uab || !u1 || !b0 ||
       !b_first || (n_blocks > 0 && !blk_ptr))
     OX_FAIL("ox_assemble_first_blocks: null argument");
@@ -763,10 +911,40 @@ extern "C" int ox_assemble_first_blocks(int degree, const ox_cells *cells, const
   }
 #endif
   if (ox_prof_on) ox_prof_start(OX_TAG_ASSEMBLE_FIRST, ox_stream(stream));
-  const int rc = launch_row_blocks<OX_KIND_CONV>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_blocks, blk_ptr, lds_entries,
-                                                 ox_stream(stream));
+  int rc;
+  if (nut) {
+    FirstArgsT<true> Fn{};
+    static_cast<FirstArgs &>(Fn) = F;
+    Fn.nut = nut;
+    rc = launch_row_blocks<OX_KIND_CONV, true>(degree, cells, cell_dofs, adj, adj_pos, pw, A, Fn, n_blocks, blk_ptr, lds_entries,
+                                               ox_stream(stream));
+  } else {
+    FirstArgsT<false> F0{};
+    static_cast<FirstArgs &>(F0) = F;
+    rc = launch_row_blocks<OX_KIND_CONV>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F0, n_blocks, blk_ptr, lds_entries,
+                                         ox_stream(stream));
+  }
   if (ox_prof_on) ox_prof_stop(ox_stream(stream));
   return rc;
+}
+
+extern "C" int ox_assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
+                                        const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
+                                        const double *uab, const double *u1, const double *b0, double *b_first, double dt,
+                                        double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
+                                        double *a_u1) {
+  return assemble_first_blocks(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_blocks,
+                               blk_ptr, lds_entries, stream, a_u1, nullptr);
+}
+
+extern "C" int ox_assemble_first_blocks_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
+                                            const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M,
+                                            const ox_sell *K, const double *uab, const double *u1, const double *b0,
+                                            double *b_first, double dt, double nu, int n_blocks, const int32_t *blk_ptr,
+                                            int64_t lds_entries, void *stream, double *a_u1, const double *nut) {
+  if (!nut) OX_FAIL("ox_assemble_first_blocks_nut: null nut (the constant-viscosity form is ox_assemble_first_blocks)");
+  return assemble_first_blocks(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_blocks,
+                               blk_ptr, lds_entries, stream, a_u1, nut);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -1,0 +1,163 @@
+// Eddy viscosity per cell: nut[e] from grad u_ab at the cell's centroid, for the fused
+// assemble_first with a per-cell viscosity (ox_assemble_first_*_nut).
+//
+//   g[d][k] = d(u_ab)_d / dx_k = sum_i u_ab[dof_i][d] sum_b dphi_i/dlambda_b (centroid) G[b][k]
+//   S       = (g + g^T)/2,   Delta^2 = |cell|^(2/gdim),  |cell| = |det J| / gdim!
+//   Smagorinsky:  nut = Cs^2 Delta^2 sqrt(2 S:S)
+//   WALE (3-D):   Sd  = sym(g g) - tr(g g)/3 I,  x = Sd:Sd,  y = S:S
+//                 nut = Cw^2 Delta^2 x sqrt(x) / (y^2 sqrt(y) + x sqrt(sqrt(x))),  0 where the denominator is 0
+//
+// One lane per cell, in kernel cell order: the cell's dof list (ND x 4 B) and geometry record (GS x 8 B) are streamed,
+// the ND x GDIM coefficients are gathered, 8 B are written.  The centroid derivatives are compile-time constants
+// (fe_tables_c.h): identically-zero entries cost nothing.  No atomics, no LDS; every sum has a fixed order.
+#include "fe_tables_c.h"
+#include "ox_kernels.h"
+
+namespace {
+
+template <int GDIM, int DEG>
+struct Centroid {
+  static_assert(DEG >= 1 && DEG <= 3, "Lagrange degree 1, 2, 3");
+  static constexpr int ND = DEG == 1 ? GDIM + 1 : (DEG == 3 ? (GDIM == 2 ? 10 : 20) : (GDIM == 2 ? 6 : 10));
+  static constexpr int GS = GDIM == 2 ? 6 : 10;
+  __host__ __device__ static constexpr double dphi(int i, int b) {
+    if constexpr (GDIM == 2 && DEG == 1) return OX_DPHIC2_1[i][b];
+    else if constexpr (GDIM == 2 && DEG == 2) return OX_DPHIC2_2[i][b];
+    else if constexpr (GDIM == 2) return OX_DPHIC2_3[i][b];
+    else if constexpr (DEG == 1) return OX_DPHIC3_1[i][b];
+    else if constexpr (DEG == 2) return OX_DPHIC3_2[i][b];
+    else return OX_DPHIC3_3[i][b];
+  }
+};
+
+#define OX_NUT_SMAGORINSKY 0
+#define OX_NUT_WALE 1
+
+template <int GDIM, int DEG, int MODEL>
+__global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const int32_t *__restrict__ cell_dofs,
+                                                        const double *__restrict__ uab, double coef2,
+                                                        double *__restrict__ nut) {
+  using E = Centroid<GDIM, DEG>;
+  constexpr int ND = E::ND, GS = E::GS;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= cells.n_cells) return;
+  // round 1: the cell's dofs and geometry (both indexed by e); round 2: the coefficient gathers
+  int32_t dd[ND];
+#pragma unroll
+  for (int i = 0; i < ND; ++i) dd[i] = cell_dofs[(size_t)e * ND + i];
+  const double *__restrict__ gp = cells.geom + (size_t)e * GS;
+  double G[GDIM + 1][GDIM];
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) G[0][d] = 0.0;
+#pragma unroll
+  for (int a = 1; a <= GDIM; ++a)
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) {
+      G[a][d] = gp[(a - 1) * GDIM + d];
+      G[0][d] -= G[a][d];
+    }
+  const double adet = gp[GDIM * GDIM];
+  double uc[ND][GDIM];
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) uc[i][d] = uab[(size_t)dd[i] * GDIM + d];
+  // t[d][b] = sum_i u_i[d] dphi_i/dlambda_b, in dof order
+  double t[GDIM][GDIM + 1];
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+    for (int b = 0; b <= GDIM; ++b) t[d][b] = 0.0;
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+#pragma unroll
+    for (int b = 0; b <= GDIM; ++b)
+      if (E::dphi(i, b) != 0.0) {
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) t[d][b] = fma(uc[i][d], E::dphi(i, b), t[d][b]);
+      }
+  // g[d][k] = sum_b t[d][b] G[b][k]
+  double g[GDIM][GDIM];
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+    for (int k = 0; k < GDIM; ++k) {
+      double v = 0.0;
+#pragma unroll
+      for (int b = 0; b <= GDIM; ++b) v = fma(t[d][b], G[b][k], v);
+      g[d][k] = v;
+    }
+  double ss = 0.0;  // S:S
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+    for (int k = 0; k < GDIM; ++k) {
+      const double s = 0.5 * (g[d][k] + g[k][d]);
+      ss = fma(s, s, ss);
+    }
+  // Delta^2 = |cell|^(2/gdim)
+  double delta2;
+  if constexpr (GDIM == 2) delta2 = 0.5 * adet;
+  else {
+    const double h = cbrt(adet * (1.0 / 6.0));
+    delta2 = h * h;
+  }
+  double out;
+  if constexpr (MODEL == OX_NUT_SMAGORINSKY) {
+    out = coef2 * delta2 * sqrt(2.0 * ss);
+  } else {
+    static_assert(GDIM == 3, "WALE is built for three dimensions");
+    double g2[GDIM][GDIM];
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+      for (int k = 0; k < GDIM; ++k) {
+        double v = 0.0;
+#pragma unroll
+        for (int m = 0; m < GDIM; ++m) v = fma(g[d][m], g[m][k], v);
+        g2[d][k] = v;
+      }
+    const double tr3 = (g2[0][0] + g2[1][1] + g2[2][2]) * (1.0 / 3.0);
+    double x = 0.0;  // Sd:Sd
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+      for (int k = 0; k < GDIM; ++k) {
+        const double s = 0.5 * (g2[d][k] + g2[k][d]) - (d == k ? tr3 : 0.0);
+        x = fma(s, s, x);
+      }
+    const double num = x * sqrt(x);
+    const double den = ss * ss * sqrt(ss) + x * sqrt(sqrt(x));
+    out = den > 0.0 ? coef2 * delta2 * (num / den) : 0.0;
+  }
+  nut[e] = out;
+}
+
+}  // namespace
+
+extern "C" int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
+                                 double coefficient, double *nut, void *stream) {
+  if (!cells || !cell_dofs || !uab || !nut || !cells->geom) OX_FAIL("ox_eddy_viscosity: null argument");
+  if (!(coefficient >= 0.0)) OX_FAIL("ox_eddy_viscosity: coefficient=%g", coefficient);
+  if (cells->n_cells <= 0) return 0;
+  if (cells->n_cells > (int64_t)0x7fffffff) OX_FAIL("ox_eddy_viscosity: %lld cells", (long long)cells->n_cells);
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const unsigned nblk = (unsigned)((cells->n_cells + 255) / 256);
+  const double c2 = coefficient * coefficient;
+  if (model == OX_NUT_WALE && g != 3) OX_FAIL("ox_eddy_viscosity: WALE is built for gdim = 3 (got %d)", g);
+  if (model != OX_NUT_SMAGORINSKY && model != OX_NUT_WALE) OX_FAIL("ox_eddy_viscosity: model=%d", model);
+#define OX_NUT_CASE(GD, DG, MD)                                                                                        \
+  if (g == GD && degree == DG && model == MD) {                                                                        \
+    if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                          \
+    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, c2, nut); \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                  \
+    OX_LAUNCH_CHECK();                                                                                                 \
+    return 0;                                                                                                          \
+  }
+  OX_NUT_CASE(2, 1, 0) OX_NUT_CASE(2, 2, 0) OX_NUT_CASE(2, 3, 0)
+  OX_NUT_CASE(3, 1, 0) OX_NUT_CASE(3, 2, 0) OX_NUT_CASE(3, 3, 0)
+  OX_NUT_CASE(3, 1, 1) OX_NUT_CASE(3, 2, 1) OX_NUT_CASE(3, 3, 1)
+#undef OX_NUT_CASE
+  OX_FAIL("ox_eddy_viscosity: unsupported gdim=%d degree=%d", g, degree);
+}

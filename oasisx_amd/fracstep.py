@@ -104,11 +104,20 @@ class FractionalStep_AB_CN:
         scalars: list of :class:`oasisx_amd.ScalarTransport`: passive scalars on the velocity component space, advected by
             the extrapolated velocity and solved once per step after the velocity update (:mod:`oasisx_amd.scalar`);
             ``None`` / ``[]``: no scalar phase runs.  One GPU only
+        viscosity_model: :class:`oasisx_amd.Smagorinsky`, :class:`oasisx_amd.Wale` or :class:`oasisx_amd.CellViscosity`:
+            an additional viscosity per cell, ``div(nut grad u)``, evaluated per step from the extrapolated velocity and
+            added by the fused assembly kernel (:mod:`oasisx_amd.viscosity`); ``None``: the constant-viscosity step,
+            unchanged.  One GPU only; not with ``rotational=True`` or ``scalars=``
     """
 
     def __init__(self, mesh, u_element, p_element, bcs_u, bcs_p, rotational: bool = False,
                  solver_options: dict | None = None, jit_options: dict | None = None,
-                 body_force=None, options: dict | None = None, scalars=None):
+                 body_force=None, options: dict | None = None, scalars=None, viscosity_model=None):
+        if viscosity_model is not None:  # the scope guards need neither the library nor a GPU
+            from .viscosity import check_model
+
+            check_model(viscosity_model, mesh, rotational, scalars)
+        self._viscosity_model = viscosity_model
         self._lib = _lib.load()  # fails loudly when the HIP library is missing
         self._mesh = mesh
         gdim = mesh.geometry.dim
@@ -237,6 +246,10 @@ class FractionalStep_AB_CN:
 
         self._compile_and_allocate_forms()
         self._preassemble()
+        self._nut = None
+        if viscosity_model is not None:  # nut per cell, in the kernels' cell order
+            self._nut = torch.zeros(int(self._geom.shape[0]), dtype=torch.float64, device=dev)
+            viscosity_model.bind(self)
 
         if self._rotational:  # Projector(p + dp - xi nu div(u), Q) (fracstep.py:237-247)
             from .function import Projector
@@ -401,7 +414,11 @@ class FractionalStep_AB_CN:
         self._AU1_valid = False
         want_au = bool(self._solver_u._options.get("ksp_initial_guess_nonzero", False)) and \
             str(self._solver_u._options.get("ksp_type", "")).lower() != "preonly"
-        if self._row_blocks and Vi.pattern.n_row_blocks > 0:
+        if self._viscosity_model is not None:
+            # nut per cell from u_ab, then the fused kernel with nut K_c added to the convection rows of every cell
+            self.viscosity_assemble()
+            self._assemble_first_nut(dt, nu, want_au)
+        elif self._row_blocks and Vi.pattern.n_row_blocks > 0:
             # ONE launch over the slices in storage order (round 5): the rows of a cell meet in one L2 instead of being
             # torn apart into the launches of up to ten width bins (options["assemble_row_blocks"]; bit-identical)
             nblk, bptr, ent = Vi.pattern.blocks_args()
@@ -435,6 +452,36 @@ class FractionalStep_AB_CN:
             self._A.zero_rows(bcu._rows_dev, 1.0, self._B3.ptr() if want_au else None,
                               self._U1.rptr() if want_au else None, self._gdim)
         self._AU1_valid = want_au
+
+    @_phase
+    def viscosity_assemble(self):
+        """``nut`` per cell (kernel cell order) of the model, from the ``u_ab`` block ``assemble_first`` has just formed
+        (``ox_eddy_viscosity``; a :class:`CellViscosity` copies its fixed values)."""
+        if self._viscosity_model is None:
+            raise RuntimeError("viscosity_assemble: the solver was built without a viscosity_model")
+        self._viscosity_model.evaluate(self, self._nut)
+
+    def _assemble_first_nut(self, dt, nu, want_au):
+        lib, st = self._lib, _lib.current_stream()
+        Vi = self._Vi[0][0]
+        head = (Vi.degree, C.byref(self._cells), _lib.ptr(Vi.cell_dofs), C.byref(self._adj_u), _lib.ptr(Vi.adj.adj_pos),
+                Vi.adj.pw, self._A.ref(), self._M.ref(), self._K.ref(), self._UAB.rptr(), self._U1.rptr(), self._B0.rptr(),
+                self._BFIRST.ptr(), float(dt), float(nu))
+        tail = (st, self._B3.ptr() if want_au else None, _lib.ptr(self._nut))
+        if self._row_blocks and Vi.pattern.n_row_blocks > 0:
+            _lib.check(lib.ox_assemble_first_blocks_nut(*head, *Vi.pattern.blocks_args(), *tail),
+                       "ox_assemble_first_blocks_nut")
+        else:
+            _lib.check(lib.ox_assemble_first_au_nut(*head, *Vi.pattern.bins_args(), *tail), "ox_assemble_first_au_nut")
+
+    def eddy_viscosity(self) -> torch.Tensor:
+        """``nut`` per cell of the last ``assemble_first``: a device tensor ``(num_cells,)`` in the MESH's cell order (the
+        kernels hold it in their own order, ``Vi.cells_in_kernel_order()``)."""
+        if self._viscosity_model is None:
+            raise RuntimeError("eddy_viscosity: the solver was built without a viscosity_model")
+        out = torch.zeros(int(self._mesh.num_cells), dtype=torch.float64, device=self._nut.device)
+        out[self._Vi[0][0].local_cells.to(torch.int64)] = self._nut
+        return out
 
     @_phase
     def velocity_tentative_assemble(self):
