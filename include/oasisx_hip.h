@@ -717,6 +717,26 @@ int ox_probe_sample(int degree, int gdim, const int32_t *cell_dofs, int64_t n_ce
 int ox_scalar_rows(const ox_sell *A, const ox_sell *M, const ox_sell *K, const ox_sell *Ac, double s, double dt, int ncomp,
                    const double *c1, const double *b0, double *b, double *a_c1, void *stream);
 
+/* ---- Wall shear stress, traction and boundary forces on exterior facets (ox_wall.hip) ----------
+ * Facet i -- the caller passes the facets SORTED by tag -- belongs to the cell at kernel position facet_rec[2 i] and lies
+ * opposite that cell's local vertex facet_rec[2 i + 1] (a record outside the tables reads nothing and leaves NaN).  With
+ * the outward unit normal n = -grad(lambda_a) / |grad(lambda_a)|, the measure |f| = |det J| |grad(lambda_a)| / (gdim-1)!
+ * and the facet means gbar of grad u and pbar of p (exact: compile-time facet means of the basis):
+ *   t[i]   = -pbar n + nu_eff (gbar + gbar^T) n,  nu_eff = nu + nut[cell] (nut: device [n_cells] in kernel cell order,
+ *            or NULL);   wss[i] = t[i] - (t[i].n) n;   ft[i] = |f| t[i]                (device [n_facets][gdim] each)
+ * weight > 0: acc_vec += weight wss, acc_mag += weight |wss| ([n_facets]), acc_t += weight t, in the same launch.
+ * u interleaved [n_u][gdim], p [n_q]; cell_vdofs / cell_qdofs: the tables of the velocity component space (degree 1, 2, 3)
+ * and the pressure space (P1-P1, P2-P1, P3-P2) in kernel cell order.  One lane per facet, no atomics, fixed order. */
+int ox_wall_stress(int u_degree, int p_degree, const ox_cells *cells, const int32_t *cell_vdofs, const int32_t *cell_qdofs,
+                   int64_t n_facets, const int32_t *facet_rec, const double *u, const double *p, const double *nut,
+                   double nu, double weight, double *t, double *wss, double *ft, double *acc_vec, double *acc_mag,
+                   double *acc_t, void *stream);
+/* ring[slot][k][:] = -rho sum_{tag_ptr[k] <= i < tag_ptr[k+1]} ft[i]  (the force the fluid exerts on the facets of tag k);
+ * ring: device [capacity][n_tags][gdim], tag_ptr: device [n_tags + 1].  One block per tag, a fixed tree: identical inputs
+ * give identical bits. */
+int ox_wall_forces(int gdim, int n_tags, const int64_t *tag_ptr, const double *ft, double rho, double *ring,
+                   int64_t capacity, int64_t slot, void *stream);
+
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */
 int ox_comm_create(const char *id128, int rank, int nranks, void **comm_out); /* ncclCommInitRank */

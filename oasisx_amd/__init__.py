@@ -13,6 +13,7 @@ from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .scalar import ScalarTransport
 from .viscosity import CellViscosity, Smagorinsky, Wale
+from .wall import WallStress
 
 logging.basicConfig()
 logger = logging.getLogger("oasisx")
@@ -28,4 +29,5 @@ __all__ = [
     "Smagorinsky",
     "Wale",
     "CellViscosity",
+    "WallStress",
 ]

@@ -147,9 +147,48 @@ class VTXWriter:
         self.close()
 
 
+def write_facet_vtu(path, mesh, facets, cell_data=None, time: float = 0.0) -> None:
+    """The surface made of the given facets of ``mesh`` (facet ids of ``mesh._entities(gdim - 1)``, e.g.
+    ``WallStress.facets``) as one ``.vtu``: straight VTK_LINE (3) / VTK_TRIANGLE (5) cells on the facets' own vertices,
+    with per-facet data ``{name: (n_facets,) or (n_facets, ncomp)}`` (host arrays or tensors, in the order of
+    ``facets``; vectors are padded to 3 components).  ``read_vtu`` reads it back (``"cell_data"``)."""
+    d = mesh.gdim
+    facets = np.asarray(facets, dtype=np.int64).reshape(-1)
+    fv, _ = mesh._entities(d - 1)
+    verts = fv[facets]  # (nf, d) mesh vertex ids
+    used, conn = np.unique(verts.reshape(-1), return_inverse=True)
+    X = np.zeros((used.shape[0], 3))
+    X[:, :d] = mesh.coords.cpu().numpy()[used]
+    nf = facets.shape[0]
+    out = ['<?xml version="1.0"?>\n<VTKFile type="UnstructuredGrid" version="1.0" byte_order="LittleEndian" '
+           'header_type="UInt64">\n<UnstructuredGrid>\n',
+           f'<FieldData><DataArray type="Float64" Name="TimeValue" NumberOfTuples="1" format="ascii">{float(time)!r}'
+           '</DataArray></FieldData>\n',
+           f'<Piece NumberOfPoints="{X.shape[0]}" NumberOfCells="{nf}">\n<PointData>\n</PointData>\n<CellData>\n']
+    for name, a in (cell_data or {}).items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape[0] != nf or a.ndim > 2:
+            raise ValueError(f"write_facet_vtu: {name!r} has shape {a.shape} for {nf} facets")
+        if a.ndim == 2 and a.shape[1] > 1:
+            v = np.zeros((nf, 3))
+            v[:, : a.shape[1]] = a
+            out.append(_data_array(name, v, 3))
+        else:
+            out.append(_data_array(name, a.reshape(-1)))
+    out.append("</CellData>\n<Points>\n" + _data_array("Points", X, 3) + "</Points>\n<Cells>\n")
+    out.append(_data_array("connectivity", conn.astype(np.int64).reshape(-1))
+               + _data_array("offsets", (np.arange(nf, dtype=np.int64) + 1) * d)
+               + _data_array("types", np.full(nf, 3 if d == 2 else 5, dtype=np.uint8)))
+    out.append("</Cells>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n")
+    os.makedirs(os.path.dirname(str(path)) or ".", exist_ok=True)
+    with open(str(path), "w") as fh:
+        fh.write("".join(out))
+
+
 def read_vtu(path: str) -> dict:
     """Minimal reader of the files this module writes (tests, post-processing without VTK):
-    {"points", "connectivity", "offsets", "types", "time", "point_data": {name: array}}."""
+    {"points", "connectivity", "offsets", "types", "time", "point_data": {name: array}, "cell_data": {name: array}}."""
     import xml.etree.ElementTree as ET
 
     np_t = {"Float64": np.float64, "Int64": np.int64, "UInt8": np.uint8}
@@ -163,11 +202,14 @@ def read_vtu(path: str) -> dict:
         return a.reshape(-1, nc) if nc > 1 else a
 
     piece = root.find("UnstructuredGrid/Piece")
-    out = {"point_data": {}}
+    out = {"point_data": {}, "cell_data": {}}
     out["time"] = float(root.find("UnstructuredGrid/FieldData/DataArray").text)
     out["points"] = arr(piece.find("Points/DataArray"))
     for el in piece.find("Cells"):
         out[el.get("Name")] = arr(el)
     for el in piece.find("PointData"):
         out["point_data"][el.get("Name")] = arr(el)
+    cd = piece.find("CellData")
+    for el in (cd if cd is not None else []):
+        out["cell_data"][el.get("Name")] = arr(el)
     return out
