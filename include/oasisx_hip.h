@@ -493,6 +493,23 @@ int ox_assemble_first_blocks_nut(int degree, const ox_cells *cells, const int32_
                                  double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
                                  double *a_u1, const double *nut);
 
+/* ---- generalised-Newtonian laws and the full stress form ---- */
+/* nut[e] = max(nu(gd_e) - base, 0), gd = sqrt(2 S:S) with S = sym(grad uab) at the cell's centroid (the quantity of
+ * ox_eddy_viscosity's Smagorinsky model), arguments as there.  law 2, Carreau-Yasuda, params = {nu0, nu_inf, lam, n, a}:
+ * nu = nu_inf + (nu0 - nu_inf) (1 + (lam gd)^a)^((n - 1)/a), base = min(nu0, nu_inf);  law 3, Cross, params = {nu0, nu_inf,
+ * lam, m}: nu = nu_inf + (nu0 - nu_inf) / (1 + (lam gd)^m), same base;  law 4, power law, params = {k, n, nu_min, nu_max}:
+ * nu = min(max(k gd^(n - 1), nu_min), nu_max), base = nu_min; at gd == 0: nu_max for n < 1, nu_min for n > 1, the clipped
+ * k for n == 1.  params: HOST array of n_params doubles (5, 4, 4); the caller runs the step at nu = base. */
+int ox_viscosity_law(int law, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
+                     const double *params, int n_params, double *nut, void *stream);
+/* The transposed term of div(nut (grad u + grad u^T)), explicit in uab, added to b in place:
+ * b[r][i] += scale * sum_e nut[e] int_e sum_j d(uab)_j/dx_i d(phi_r)/dx_j, rows r < n_rows of the velocity component space
+ * of `degree` (1, 2, 3; adj and cell_dofs of that space), b and uab interleaved [n][gdim], nut [n_cells] in kernel cell
+ * order.  lane = row, fixed summation order, no atomics: two launches on equal inputs give equal bits. */
+int ox_assemble_stress_transpose(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
+                                 int64_t n_rows, const double *uab, const double *nut, double scale, double *b,
+                                 void *stream);
+
 /* ---- A6 / A8: assemble_vector(p * v.dx(i) * dx) and (dp.dx(i) * v * dx), all i at once
  *      (fracstep.py:487-497 and :618).  kind 0: out[r][i] = base[r][i] + scale * int p d_i(phi_r)
  *      kind 1: out[r][i] = base[r][i] + scale * int d_i(p) phi_r.  base may be NULL (=0). */

@@ -12,7 +12,7 @@ from .function import Projector
 from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .scalar import ScalarTransport
-from .viscosity import CellViscosity, Smagorinsky, Wale
+from .viscosity import CarreauYasuda, CellViscosity, Cross, PowerLaw, Smagorinsky, Wale
 from .wall import WallStress
 
 logging.basicConfig()
@@ -29,5 +29,8 @@ __all__ = [
     "Smagorinsky",
     "Wale",
     "CellViscosity",
+    "CarreauYasuda",
+    "Cross",
+    "PowerLaw",
     "WallStress",
 ]

@@ -1231,6 +1231,99 @@ extern "C" int ox_assemble_grad_vector(int kind, int row_degree, int p_degree, c
           row_degree, p_degree, kind);
 }
 
+// The transposed term of the full stress form div(nut (grad u + grad u^T)), explicit in u_ab:
+//   b[r][d] += scale * sum_e nut_e int_e sum_j d(u_ab)_j/dx_d d(phi_r)/dx_j
+// With gu[m][a] = G[a] . u_m (the cell's coefficients, gathered as the CONV pair loop gathers them) the cell integral is
+//   nut |J| sum_b G[b][d] Z[b],   Z[b] = sum_(m: (m, b) in COMBOS) sum_a S[i][a][(m, b)] gu[m][a]
+// with S = StiffTab (the quadrature sums taken at compile time, exact for the element): (GDIM + 1) NCB FMAs per (row, cell)
+// pair -- 64 for P2 tetrahedra, where the quadrature form spends ~1200 -- and no quadrature loop to keep live.  The table is
+// read with the lane's own row dof i, as k_grad_vector reads RtTab.  P3 tetrahedra have no StiffTab in the fused kernel (its
+// LDS copy of ConvTab does not fit); here the table is read in place (38 KB), so that pair gets one of its own.
+// lane = row, the OX_ADJ_WALK over the row's cells, register accumulation, a fixed order, no atomics; ONE in/out pointer.
+__device__ const StiffTab<3, 3> ST33 = make_stiff<3, 3>();
+template <int GDIM, int DEG>
+__device__ __forceinline__ const StiffTab<GDIM, DEG> &st_tab_vec() {
+  if constexpr (GDIM == 3 && DEG == 3) return ST33;
+  else return st_tab<GDIM, DEG>();
+}
+
+template <int GDIM, int DEG>
+__global__ __launch_bounds__(256) void k_stress_transpose(ox_cells cells, const int32_t *__restrict__ cell_dofs, ox_adj adj,
+                                                          int64_t n_rows, const double *__restrict__ uab,
+                                                          const double *__restrict__ nut, double scale,
+                                                          double *__restrict__ b) {
+  using E = Elem<GDIM, DEG>;
+  constexpr auto CB = COMBOS<GDIM, DEG>;
+  const auto &S = st_tab_vec<GDIM, DEG>();
+  double o[GDIM];
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) o[d] = 0.0;
+  OX_ADJ_WALK_BEGIN
+  double G[GDIM + 1][GDIM], adet;
+  load_geom<GDIM>(cells.geom + (size_t)e * E::GS, G, adet);
+  const double wn = nut[e] * adet;
+  const int32_t *__restrict__ ud = cell_dofs + (size_t)e * E::ND;
+  // gu[m][a] = G[a] . u_m
+  double gu[E::ND][GDIM + 1];
+#pragma unroll
+  for (int m = 0; m < E::ND; ++m) {
+    const double *up = uab + (size_t)ud[m] * GDIM;
+    double um[GDIM];
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) um[d] = up[d];
+#pragma unroll
+    for (int a = 0; a <= GDIM; ++a) {
+      double v = 0.0;
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d) v = fma(G[a][d], um[d], v);
+      gu[m][a] = v;
+    }
+  }
+  double Z[GDIM + 1];
+#pragma unroll
+  for (int bb = 0; bb <= GDIM; ++bb) Z[bb] = 0.0;
+#pragma unroll
+  for (int a = 0; a <= GDIM; ++a)
+#pragma unroll
+    for (int c = 0; c < CB.n; ++c) Z[CB.b[c]] = fma(S.t[i][a][c], gu[CB.j[c]][a], Z[CB.b[c]]);
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) {
+    double v = 0.0;
+#pragma unroll
+    for (int bb = 0; bb <= GDIM; ++bb) v = fma(Z[bb], G[bb][d], v);
+    o[d] = fma(wn, v, o[d]);
+  }
+  OX_ADJ_WALK_END
+  if (row < n_rows) {
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) b[row * GDIM + d] = fma(scale, o[d], b[row * GDIM + d]);
+  }
+}
+
+extern "C" int ox_assemble_stress_transpose(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
+                                            int64_t n_rows, const double *uab, const double *nut, double scale, double *b,
+                                            void *stream) {
+  if (!cells || !cell_dofs || !adj || !uab || !nut || !b) OX_FAIL("ox_assemble_stress_transpose: null argument");
+  if (n_rows < 0 || n_rows > (int64_t)adj->n_slices * 64)
+    OX_FAIL("ox_assemble_stress_transpose: n_rows=%lld for %d slices", (long long)n_rows, adj->n_slices);
+  const int nblk = (adj->n_slices + 3) / 4;
+  if (nblk == 0) return 0;
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+#define OX_ST_CASE(GD, DG)                                                                                              \
+  if (g == GD && degree == DG) {                                                                                        \
+    if (ox_prof_on) ox_prof_start(OX_TAG_STRESS_TRANSPOSE, st);                                                         \
+    hipLaunchKernelGGL((k_stress_transpose<GD, DG>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, *adj, n_rows, uab, \
+                       nut, scale, b);                                                                                  \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                   \
+    OX_LAUNCH_CHECK();                                                                                                  \
+    return 0;                                                                                                           \
+  }
+  OX_ST_CASE(2, 1) OX_ST_CASE(2, 2) OX_ST_CASE(2, 3) OX_ST_CASE(3, 1) OX_ST_CASE(3, 2) OX_ST_CASE(3, 3)
+#undef OX_ST_CASE
+  OX_FAIL("ox_assemble_stress_transpose: unsupported gdim=%d degree=%d", g, degree);
+}
+
 // out[r] = scale * int div(u) psi_r                              (A7, fracstep.py:538,546)
 template <int GDIM, int RDEG, int UDEG>
 __global__ __launch_bounds__(256) void k_div_vector(ox_cells cells, const int32_t *__restrict__ cell_udofs,

@@ -137,6 +137,7 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_HALO 150       // one halo exchange (key = components); includes waiting for the peers
 #define OX_TAG_SYNC_POINT 151 // one distributed Krylov synchronisation point (reduce + all-reduce + logic)
 #define OX_TAG_EDDY_VISCOSITY 160  // ox_eddy_viscosity (key = cells)
+#define OX_TAG_STRESS_TRANSPOSE 161 // ox_assemble_stress_transpose
 #define OX_TAG_WALL_STRESS 170     // ox_wall_stress (key = facets)
 #define OX_TAG_WALL_FORCES 171     // ox_wall_forces (key = tags)
 extern bool ox_prof_on;

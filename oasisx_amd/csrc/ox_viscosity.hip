@@ -7,11 +7,19 @@
 //   WALE (3-D):   Sd  = sym(g g) - tr(g g)/3 I,  x = Sd:Sd,  y = S:S
 //                 nut = Cw^2 Delta^2 x sqrt(x) / (y^2 sqrt(y) + x sqrt(sqrt(x))),  0 where the denominator is 0
 //
+// Generalised-Newtonian laws, gd = sqrt(2 S:S), nut = max(nu(gd) - base, 0):
+//   Carreau-Yasuda:  nu = nu_inf + (nu0 - nu_inf) (1 + (lam gd)^a)^((n - 1)/a),  base = min(nu0, nu_inf)
+//   Cross:           nu = nu_inf + (nu0 - nu_inf) / (1 + (lam gd)^m),            base = min(nu0, nu_inf)
+//   power law:       nu = min(max(k gd^(n - 1), nu_min), nu_max),                base = nu_min
+//                    (gd == 0: nu_max for n < 1, nu_min for n > 1, the clipped k for n == 1 -- no 0^negative)
+//
 // One lane per cell, in kernel cell order: the cell's dof list (ND x 4 B) and geometry record (GS x 8 B) are streamed,
 // the ND x GDIM coefficients are gathered, 8 B are written.  The centroid derivatives are compile-time constants
 // (fe_tables_c.h): identically-zero entries cost nothing.  No atomics, no LDS; every sum has a fixed order.
 #include "fe_tables_c.h"
 #include "ox_kernels.h"
+#include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -32,10 +40,22 @@ struct Centroid {
 
 #define OX_NUT_SMAGORINSKY 0
 #define OX_NUT_WALE 1
+#define OX_NUT_CARREAU_YASUDA 2
+#define OX_NUT_CROSS 3
+#define OX_NUT_POWER_LAW 4
+
+// The parameters of a generalised-Newtonian law, by value in the kernel arguments (the eddy-viscosity models keep their
+// one double).  Carreau-Yasuda: c0 = nu_inf, c1 = nu0 - nu_inf, c2 = lam, c3 = a, c4 = (n - 1)/a;  Cross: c0 = nu_inf,
+// c1 = nu0 - nu_inf, c2 = lam, c3 = m;  power law: c0 = k, c1 = n - 1, c2 = nu_min, c3 = nu_max.
+struct LawParams {
+  double c0, c1, c2, c3, c4, base;
+};
+template <int MODEL>
+using NutArg = std::conditional_t<(MODEL >= OX_NUT_CARREAU_YASUDA), LawParams, double>;
 
 template <int GDIM, int DEG, int MODEL>
 __global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const int32_t *__restrict__ cell_dofs,
-                                                        const double *__restrict__ uab, double coef2,
+                                                        const double *__restrict__ uab, NutArg<MODEL> coef2,
                                                         double *__restrict__ nut) {
   using E = Centroid<GDIM, DEG>;
   constexpr int ND = E::ND, GS = E::GS;
@@ -105,6 +125,21 @@ __global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const in
   double out;
   if constexpr (MODEL == OX_NUT_SMAGORINSKY) {
     out = coef2 * delta2 * sqrt(2.0 * ss);
+  } else if constexpr (MODEL == OX_NUT_CARREAU_YASUDA) {
+    const double gd = sqrt(2.0 * ss);
+    const double nu = fma(coef2.c1, pow(1.0 + pow(coef2.c2 * gd, coef2.c3), coef2.c4), coef2.c0);
+    out = fmax(nu - coef2.base, 0.0);
+  } else if constexpr (MODEL == OX_NUT_CROSS) {
+    const double gd = sqrt(2.0 * ss);
+    const double nu = coef2.c0 + coef2.c1 / (1.0 + pow(coef2.c2 * gd, coef2.c3));
+    out = fmax(nu - coef2.base, 0.0);
+  } else if constexpr (MODEL == OX_NUT_POWER_LAW) {
+    const double gd = sqrt(2.0 * ss);
+    double nu;
+    if (gd > 0.0) nu = coef2.c0 * pow(gd, coef2.c1);
+    else nu = coef2.c1 < 0.0 ? coef2.c3 : (coef2.c1 > 0.0 ? coef2.c2 : coef2.c0);
+    nu = fmin(fmax(nu, coef2.c2), coef2.c3);
+    out = fmax(nu - coef2.base, 0.0);
   } else {
     static_assert(GDIM == 3, "WALE is built for three dimensions");
     double g2[GDIM][GDIM];
@@ -160,4 +195,54 @@ extern "C" int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, c
   OX_NUT_CASE(3, 1, 1) OX_NUT_CASE(3, 2, 1) OX_NUT_CASE(3, 3, 1)
 #undef OX_NUT_CASE
   OX_FAIL("ox_eddy_viscosity: unsupported gdim=%d degree=%d", g, degree);
+}
+
+// nut[e] = max(nu(gd_e) - base, 0) of a generalised-Newtonian law (include/oasisx_hip.h): the centroid gradient of
+// k_eddy_viscosity, the law as one more branch of it.
+extern "C" int ox_viscosity_law(int law, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
+                                const double *params, int n_params, double *nut, void *stream) {
+  if (!cells || !cell_dofs || !uab || !params || !nut || !cells->geom) OX_FAIL("ox_viscosity_law: null argument");
+  const int want = law == OX_NUT_CARREAU_YASUDA ? 5 : ((law == OX_NUT_CROSS || law == OX_NUT_POWER_LAW) ? 4 : -1);
+  if (want < 0) OX_FAIL("ox_viscosity_law: law=%d (2: Carreau-Yasuda, 3: Cross, 4: power law)", law);
+  if (n_params != want) OX_FAIL("ox_viscosity_law: law %d takes %d parameters (got %d)", law, want, n_params);
+  for (int k = 0; k < n_params; ++k)
+    if (!std::isfinite(params[k])) OX_FAIL("ox_viscosity_law: parameter %d is not finite", k);
+  LawParams P{};
+  if (law == OX_NUT_POWER_LAW) {
+    const double k = params[0], n = params[1], nu_min = params[2], nu_max = params[3];
+    if (k < 0.0 || n <= 0.0 || nu_min <= 0.0 || nu_min > nu_max)
+      OX_FAIL("ox_viscosity_law: power law k=%g n=%g nu_min=%g nu_max=%g", k, n, nu_min, nu_max);
+    P.c0 = k, P.c1 = n - 1.0, P.c2 = nu_min, P.c3 = nu_max, P.base = nu_min;
+  } else {
+    const double nu0 = params[0], nu_inf = params[1], lam = params[2], e = params[3];
+    if (nu0 < 0.0 || nu_inf < 0.0 || lam < 0.0 || e <= 0.0)
+      OX_FAIL("ox_viscosity_law: law %d nu0=%g nu_inf=%g lam=%g exponent=%g", law, nu0, nu_inf, lam, e);
+    P.c0 = nu_inf, P.c1 = nu0 - nu_inf, P.c2 = lam, P.base = nu0 < nu_inf ? nu0 : nu_inf;
+    if (law == OX_NUT_CARREAU_YASUDA) {
+      const double a = params[4];
+      if (a <= 0.0) OX_FAIL("ox_viscosity_law: Carreau-Yasuda a=%g", a);
+      P.c3 = a, P.c4 = (e - 1.0) / a;
+    } else {
+      P.c3 = e;
+    }
+  }
+  if (cells->n_cells <= 0) return 0;
+  if (cells->n_cells > (int64_t)0x7fffffff) OX_FAIL("ox_viscosity_law: %lld cells", (long long)cells->n_cells);
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const unsigned nblk = (unsigned)((cells->n_cells + 255) / 256);
+#define OX_LAW_CASE(GD, DG, MD)                                                                                       \
+  if (g == GD && degree == DG && law == MD) {                                                                         \
+    if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                         \
+    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, P, nut); \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                 \
+    OX_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                         \
+  }
+#define OX_LAW_ALL(MD) \
+  OX_LAW_CASE(2, 1, MD) OX_LAW_CASE(2, 2, MD) OX_LAW_CASE(2, 3, MD) OX_LAW_CASE(3, 1, MD) OX_LAW_CASE(3, 2, MD) OX_LAW_CASE(3, 3, MD)
+  OX_LAW_ALL(2) OX_LAW_ALL(3) OX_LAW_ALL(4)
+#undef OX_LAW_ALL
+#undef OX_LAW_CASE
+  OX_FAIL("ox_viscosity_law: unsupported gdim=%d degree=%d", g, degree);
 }

@@ -107,12 +107,24 @@ class FractionalStep_AB_CN:
         viscosity_model: :class:`oasisx_amd.Smagorinsky`, :class:`oasisx_amd.Wale` or :class:`oasisx_amd.CellViscosity`:
             an additional viscosity per cell, ``div(nut grad u)``, evaluated per step from the extrapolated velocity and
             added by the fused assembly kernel (:mod:`oasisx_amd.viscosity`); ``None``: the constant-viscosity step,
-            unchanged.  One GPU only; not with ``rotational=True`` or ``scalars=``
+            unchanged.  One GPU only; not with ``rotational=True`` or ``scalars=``.  :class:`oasisx_amd.CarreauYasuda`,
+            :class:`oasisx_amd.Cross` and :class:`oasisx_amd.PowerLaw` are shear-dependent laws ``nu(gd)``: the step is run at
+            ``nu = viscosity_model.base_viscosity`` and ``nut = nu(gd) - base_viscosity`` (``effective_viscosity()``)
+        stress_form: ``"laplacian"`` (default): ``div(nut grad u)``, today's path; ``"full"``: ``div(nut (grad u + grad u^T))``,
+            the transposed term explicit in ``u_ab`` on the right-hand side (``ox_assemble_stress_transpose``); needs a
+            ``viscosity_model``
     """
 
     def __init__(self, mesh, u_element, p_element, bcs_u, bcs_p, rotational: bool = False,
                  solver_options: dict | None = None, jit_options: dict | None = None,
-                 body_force=None, options: dict | None = None, scalars=None, viscosity_model=None):
+                 body_force=None, options: dict | None = None, scalars=None, viscosity_model=None,
+                 stress_form: str = "laplacian"):
+        if stress_form not in ("laplacian", "full"):
+            raise ValueError(f'stress_form: "laplacian" or "full" is expected (got {stress_form!r})')
+        if stress_form == "full" and viscosity_model is None:
+            raise ValueError('stress_form="full" without a viscosity_model: with a constant viscosity the transposed term '
+                             "div(nu grad u^T) = nu grad(div u) belongs to the pressure; there is nothing to add")
+        self._stress_form = stress_form
         if viscosity_model is not None:  # the scope guards need neither the library nor a GPU
             from .viscosity import check_model
 
@@ -415,9 +427,15 @@ class FractionalStep_AB_CN:
         want_au = bool(self._solver_u._options.get("ksp_initial_guess_nonzero", False)) and \
             str(self._solver_u._options.get("ksp_type", "")).lower() != "preonly"
         if self._viscosity_model is not None:
+            base = getattr(self._viscosity_model, "base_viscosity", None)
+            if base is not None and float(nu) != base:
+                raise ValueError(f"assemble_first: nu = {nu} with {self._viscosity_model!r}: the law's nut is nu(gd) - "
+                                 f"base_viscosity, so the step runs at nu = base_viscosity = {base}")
             # nut per cell from u_ab, then the fused kernel with nut K_c added to the convection rows of every cell
             self.viscosity_assemble()
             self._assemble_first_nut(dt, nu, want_au)
+            if self._stress_form == "full":
+                self.stress_transpose_assemble()
         elif self._row_blocks and Vi.pattern.n_row_blocks > 0:
             # ONE launch over the slices in storage order (round 5): the rows of a cell meet in one L2 instead of being
             # torn apart into the launches of up to ten width bins (options["assemble_row_blocks"]; bit-identical)
@@ -461,6 +479,19 @@ class FractionalStep_AB_CN:
             raise RuntimeError("viscosity_assemble: the solver was built without a viscosity_model")
         self._viscosity_model.evaluate(self, self._nut)
 
+    @_phase
+    def stress_transpose_assemble(self):
+        """``b_first[r][i] -= sum_c nut_c int_c sum_j d(u_ab)_j/dx_i d(phi_r)/dx_j``: the transposed term of the full stress
+        form, explicit in ``u_ab`` with the ``nut`` of this step (``ox_assemble_stress_transpose``).  ``A`` and the ``A u1``
+        by-product are not touched."""
+        if self._viscosity_model is None:
+            raise RuntimeError("stress_transpose_assemble: the solver was built without a viscosity_model")
+        Vi = self._Vi[0][0]
+        _lib.check(self._lib.ox_assemble_stress_transpose(Vi.degree, C.byref(self._cells), _lib.ptr(Vi.cell_dofs),
+                                                          C.byref(self._adj_u), Vi.n_owned, self._UAB.rptr(),
+                                                          _lib.ptr(self._nut), -1.0, self._BFIRST.ptr(),
+                                                          _lib.current_stream()), "ox_assemble_stress_transpose")
+
     def _assemble_first_nut(self, dt, nu, want_au):
         lib, st = self._lib, _lib.current_stream()
         Vi = self._Vi[0][0]
@@ -482,6 +513,15 @@ class FractionalStep_AB_CN:
         out = torch.zeros(int(self._mesh.num_cells), dtype=torch.float64, device=self._nut.device)
         out[self._Vi[0][0].local_cells.to(torch.int64)] = self._nut
         return out
+
+    def effective_viscosity(self) -> torch.Tensor:
+        """``base_viscosity + nut`` per cell of the last ``assemble_first`` -- the law's ``nu(gd)`` -- in the MESH's cell
+        order.  Defined for the generalised-Newtonian laws (CarreauYasuda, Cross, PowerLaw)."""
+        base = getattr(self._viscosity_model, "base_viscosity", None)
+        if base is None:
+            raise RuntimeError("effective_viscosity: the solver was built without a generalised-Newtonian law "
+                               "(CarreauYasuda, Cross, PowerLaw)")
+        return self.eddy_viscosity() + base
 
     @_phase
     def velocity_tentative_assemble(self):

@@ -1,10 +1,22 @@
-"""Eddy-viscosity (LES) models and per-cell viscosities for ``FractionalStep_AB_CN(..., viscosity_model=...)``.
+"""Eddy-viscosity (LES) models, generalised-Newtonian laws and per-cell viscosities for ``FractionalStep_AB_CN(..., viscosity_model=...)``.
 
 With a model the step's diffusion operator is ``nu K + K_nut``, ``K_nut = sum_c nut_c K_c`` (``K_c``: the stiffness
-matrix of cell ``c``): the Laplacian form ``div(nut grad u)`` of a viscosity that is constant per cell.  The transposed
-term ``div(nut grad u^T)`` is left out, as in Oasis's default (DESIGN.md sections 4 and 14)::
+matrix of cell ``c``): the Laplacian form ``div(nut grad u)`` of a viscosity that is constant per cell (DESIGN.md
+sections 4 and 14)::
 
     A = M/dt + C/2 + (nu K + K_nut)/2          b = (M/dt - C/2 - (nu K + K_nut)/2) u_1 + b0
+
+The transposed term ``div(nut grad u^T)`` of the full stress ``nut (grad u + grad u^T)`` is an option of the solver:
+``stress_form="laplacian"`` (the default) leaves it out, ``stress_form="full"`` subtracts it from ``b``, explicit in
+``u_ab`` as Oasis does, with one row-centric vector kernel after the fused one (``ox_assemble_stress_transpose``,
+DESIGN.md section 16); ``A`` stays component-decoupled::
+
+    b[r][i] -= sum_c nut_c int_c sum_j d(u_ab)_j/dx_i d(phi_r)/dx_j
+
+The generalised-Newtonian laws (:class:`CarreauYasuda`, :class:`Cross`, :class:`PowerLaw`) are functions of the shear rate
+``gd = sqrt(2 S:S)``, ``S = sym(grad u_ab)`` at the cell centroid.  Each has a ``base_viscosity`` (its smallest value); the
+kernel writes ``nut_c = nu(gd_c) - base_viscosity >= 0`` and the caller runs the step at ``nu = base_viscosity``, so
+everything downstream of ``nut`` -- the fused kernel, ``eddy_viscosity()``, :class:`oasisx_amd.WallStress` -- is unchanged.
 
 Per ``assemble_first``: one kernel writes ``nut_c`` from ``grad u_ab`` at the cell centroids (``ox_eddy_viscosity``,
 csrc/ox_viscosity.hip; :class:`CellViscosity` has nothing to evaluate), then the fused assembly kernel adds
@@ -18,7 +30,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["Smagorinsky", "Wale", "CellViscosity"]
+__all__ = ["Smagorinsky", "Wale", "CellViscosity", "CarreauYasuda", "Cross", "PowerLaw"]
 
 
 def _coefficient(what, v):
@@ -78,6 +90,88 @@ class Wale(_KernelModel):
 
     def __repr__(self):
         return f"Wale(Cw={self.coefficient})"
+
+
+def _law_parameter(what, name, v, positive=False):
+    v = float(v)
+    if not np.isfinite(v):
+        raise ValueError(f"{what}: {name} must be finite (got {v})")
+    if positive and v <= 0.0:
+        raise ValueError(f"{what}: {name} must be > 0 (got {v})")
+    if not positive and v < 0.0:
+        raise ValueError(f"{what}: {name} must be >= 0 (got {v})")
+    return v
+
+
+class _LawModel(_KernelModel):
+    """A generalised-Newtonian law ``nu(gd)``, ``gd = sqrt(2 S:S)`` at the cell centroid: ``nut_c = nu(gd_c) -
+    base_viscosity`` (``ox_viscosity_law``).  ``params``: the law's parameters in the order of include/oasisx_hip.h."""
+
+    base_viscosity = None
+    params = ()
+
+    def evaluate(self, solver, nut: torch.Tensor):
+        Vi = solver._Vi[0][0]
+        import ctypes as C
+
+        par = (C.c_double * len(self.params))(*self.params)
+        _lib.check(solver._lib.ox_viscosity_law(self.model_id, Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
+                                                solver._UAB.rptr(), par, len(self.params), _lib.ptr(nut),
+                                                _lib.current_stream()), "ox_viscosity_law")
+
+
+class CarreauYasuda(_LawModel):
+    """``nu(gd) = nu_inf + (nu0 - nu_inf) (1 + (lam gd)^a)^((n - 1)/a)``; ``a = 2``: the Carreau law.
+    ``base_viscosity = min(nu0, nu_inf)``.  2-D and 3-D, P1 / P2 / P3."""
+
+    model_id = 2
+
+    def __init__(self, nu0: float, nu_inf: float, lam: float, n: float, a: float = 2.0):
+        w = "CarreauYasuda"
+        self.nu0, self.nu_inf = _law_parameter(w, "nu0", nu0), _law_parameter(w, "nu_inf", nu_inf)
+        self.lam = _law_parameter(w, "lam", lam)
+        self.n, self.a = _law_parameter(w, "n", n, positive=True), _law_parameter(w, "a", a, positive=True)
+        self.params = (self.nu0, self.nu_inf, self.lam, self.n, self.a)
+        self.base_viscosity = min(self.nu0, self.nu_inf)
+
+    def __repr__(self):
+        return f"CarreauYasuda(nu0={self.nu0}, nu_inf={self.nu_inf}, lam={self.lam}, n={self.n}, a={self.a})"
+
+
+class Cross(_LawModel):
+    """``nu(gd) = nu_inf + (nu0 - nu_inf) / (1 + (lam gd)^m)``.  ``base_viscosity = min(nu0, nu_inf)``."""
+
+    model_id = 3
+
+    def __init__(self, nu0: float, nu_inf: float, lam: float, m: float):
+        w = "Cross"
+        self.nu0, self.nu_inf = _law_parameter(w, "nu0", nu0), _law_parameter(w, "nu_inf", nu_inf)
+        self.lam, self.m = _law_parameter(w, "lam", lam), _law_parameter(w, "m", m, positive=True)
+        self.params = (self.nu0, self.nu_inf, self.lam, self.m)
+        self.base_viscosity = min(self.nu0, self.nu_inf)
+
+    def __repr__(self):
+        return f"Cross(nu0={self.nu0}, nu_inf={self.nu_inf}, lam={self.lam}, m={self.m})"
+
+
+class PowerLaw(_LawModel):
+    """``nu(gd) = min(max(k gd^(n - 1), nu_min), nu_max)``; at ``gd == 0``: ``nu_max`` for ``n < 1``, ``nu_min`` for
+    ``n > 1``, the clipped ``k`` for ``n == 1``.  ``base_viscosity = nu_min`` (> 0: the step needs a viscosity)."""
+
+    model_id = 4
+
+    def __init__(self, k: float, n: float, nu_min: float, nu_max: float):
+        w = "PowerLaw"
+        self.k, self.n = _law_parameter(w, "k", k), _law_parameter(w, "n", n, positive=True)
+        self.nu_min = _law_parameter(w, "nu_min", nu_min, positive=True)
+        self.nu_max = _law_parameter(w, "nu_max", nu_max)
+        if self.nu_min > self.nu_max:
+            raise ValueError(f"PowerLaw: nu_min = {self.nu_min} > nu_max = {self.nu_max}")
+        self.params = (self.k, self.n, self.nu_min, self.nu_max)
+        self.base_viscosity = self.nu_min
+
+    def __repr__(self):
+        return f"PowerLaw(k={self.k}, n={self.n}, nu_min={self.nu_min}, nu_max={self.nu_max})"
 
 
 class CellViscosity:
@@ -144,7 +238,8 @@ class CellViscosity:
 def check_model(model, mesh, rotational: bool, scalars) -> None:
     """The scope guards of ``viscosity_model=``; run before anything is built (and before the HIP library is loaded)."""
     if not isinstance(model, (_KernelModel, CellViscosity)):
-        raise TypeError("viscosity_model: a Smagorinsky, Wale or CellViscosity object is expected "
+        raise TypeError("viscosity_model: a Smagorinsky, Wale, CarreauYasuda, Cross, PowerLaw or CellViscosity object is "
+                        "expected "
                         f"(got {type(model).__name__})")
     if rotational:
         raise NotImplementedError("viscosity_model with rotational=True: the xi nu div(u) term of the rotational pressure "
