@@ -208,11 +208,8 @@ class IPCS:
         return built
 
     def _assemble(self, kind, sv, A):
-        p = sv.pattern
-        self.L.check(self.lib.ox_assemble_matrix(kind, sv.degree, C.byref(self.mv.cells_struct), sv.cell_dofs, C.byref(sv.adj),
-                                                 sv.adj_pos, sv.pw, C.byref(A), p.n_bins,
-                                                 C.cast(p.bin_ptr_host, C.POINTER(C.c_int64)), p.bin_slices,
-                                                 C.cast(p.bin_width_host, C.POINTER(C.c_int32)), None), "ox_assemble_matrix")
+        self.L.check(self.lib.ox_assemble_matrix(kind, C.byref(self.mv.cells_struct), C.byref(sv), C.byref(A), 0, None),
+                     "ox_assemble_matrix")
 
     def set_field(self, dev_ptr, values):  # values: (n, ncomp) or (n,)
         self.dev.set(dev_ptr, np.ascontiguousarray(values, dtype=np.float64))
@@ -230,13 +227,11 @@ class IPCS:
         lib, ck, d = self.lib, self.L.check, self.gdim
         vv, qv, cs = self.vv, self.qv, C.byref(self.mv.cells_struct)
         n, nq, nvec = self.n_u, self.n_q, self.n_u * d
-        pv = vv.pattern
         ck(lib.ox_axpby(nq, 1.0, self.P, 0.0, None, self.PS, None), "ps = p")
         ck(lib.ox_axpby(nvec, 1.5, self.U1, -0.5, self.U2, self.UAB, None), "u_ab")  # :432-434
-        ck(lib.ox_assemble_first(vv.degree, cs, vv.cell_dofs, C.byref(vv.adj), vv.adj_pos, vv.pw, C.byref(self.A),
-                                 C.byref(self.M), C.byref(self.K), self.UAB, self.U1, self.B0, self.BFIRST, dt, nu,
-                                 pv.n_bins, C.cast(pv.bin_ptr_host, C.POINTER(C.c_int64)), pv.bin_slices,
-                                 C.cast(pv.bin_width_host, C.POINTER(C.c_int32)), None), "ox_assemble_first")  # :435-469
+        first = self.L.ox_first_args(self.UAB, self.U1, self.B0, self.BFIRST, dt, nu, None, None)  # no a_u1, no nut
+        ck(lib.ox_assemble_first(cs, C.byref(vv), C.byref(self.A), C.byref(self.M), C.byref(self.K), C.byref(first), 0, None),
+           "ox_assemble_first")  # :435-469
         ck(lib.ox_zero_rows(C.byref(self.A), self.bc_dofs_dev, self.bc_dofs.shape[0], 1.0, None), "ox_zero_rows")  # :470-472
         ck(lib.ox_assemble_grad_vector(0, vv.degree, 1, cs, qv.cell_dofs, C.byref(vv.adj), n, self.PS, self.BFIRST, 1.0,
                                        self.RHS1, None), "rhs1")  # :487-506

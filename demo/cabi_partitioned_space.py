@@ -88,16 +88,14 @@ class Dev:
         return out
 
 
-def mass_rows(L, lib, dev, mesh_view, space_view, degree):
+def mass_rows(L, lib, dev, mesh_view, space_view):
     """Assemble the mass matrix on the space's pattern; return (x, n_rows, {row: {col: value}})."""
     pat = space_view.pattern
     A = L.ox_sell()
     C.memmove(C.byref(A), C.byref(pat.sell), C.sizeof(A))
     A.vals = dev.zeros(int(pat.size)).value
-    L.check(lib.ox_assemble_matrix(0, degree, C.byref(mesh_view.cells_struct), space_view.cell_dofs, C.byref(space_view.adj),
-                                   space_view.adj_pos, space_view.pw, C.byref(A), pat.n_bins,
-                                   C.cast(pat.bin_ptr_host, C.POINTER(C.c_int64)), pat.bin_slices,
-                                   C.cast(pat.bin_width_host, C.POINTER(C.c_int32)), None), "ox_assemble_matrix")
+    L.check(lib.ox_assemble_matrix(0, C.byref(mesh_view.cells_struct), C.byref(space_view), C.byref(A), 0, None),
+            "ox_assemble_matrix")
     L.check(lib.ox_synchronize(None), "ox_synchronize")
     n_rows, ns, size = int(pat.sell.n_rows), int(pat.sell.n_slices), int(pat.size)
     sp = dev.download(pat.sell.slice_ptr, (ns + 1,), np.int64)
@@ -150,7 +148,7 @@ def main():
     ck(lib.ox_space_create(mesh, deg, 0, C.byref(V)), "ox_space_create")
     vv = L.ox_space_info()
     ck(lib.ox_space_view(V, C.byref(vv)), "ox_space_view")
-    xg, ng, rows_g = mass_rows(L, lib, dev, mv, vv, deg)
+    xg, ng, rows_g = mass_rows(L, lib, dev, mv, vv)
     kg = key(xg)
     og = np.argsort(kg)
 
@@ -204,7 +202,7 @@ def main():
            "ox_space_create_part")
         wv = L.ox_space_info()
         ck(lib.ox_space_view(W, C.byref(wv)), "ox_space_view")
-        xp, n_own, rows_p = mass_rows(L, lib, dev, sv, wv, deg)
+        xp, n_own, rows_p = mass_rows(L, lib, dev, sv, wv)
         n_loc = xp.shape[0]
         assert n_own == int((owner == r).sum()) and n_loc == owner.shape[0]
         g_of = og[np.searchsorted(kg[og], key(xp))]  # global dof of every local dof, through the coordinates

@@ -225,7 +225,7 @@ typedef struct {
   const int32_t *bin_width_host;
   const int32_t *bin_slices; /* device [n_slices]                                           */
   const int32_t *widths_host;/* host [n_slices]                                             */
-  /* row blocks of the one-launch assembly (ox_assemble_first_blocks / ox_assemble_matrix_blocks): block b owns the
+  /* row blocks of the one-launch assembly (ox_assemble_first / ox_assemble_matrix, row_blocks = 1): block b owns the
    * CONSECUTIVE slices [row_blk_ptr[b], row_blk_ptr[b+1]) -- at most OX_ROW_BLOCK_WAVES of them, their storage slots
    * together at most OX_ROW_BLOCK_LDS / 8 (greedy, in storage order); row_blk_entries = the largest block's slots
    * (sizes the launch's LDS).  n_row_blocks = 0: a slice is wider than the budget, use the width bins. */
@@ -397,7 +397,7 @@ int ox_scatter_add(double *b, const int32_t *rows, const double *y, int64_t n, i
 /* ---- S4: Mat.zeroRowsLocal(rows, diag) (fracstep.py:471-472); keeps columns -------- */
 int ox_zero_rows(const ox_sell *A, const int32_t *rows, int64_t n, double diag, void *stream);
 /* The same, and au[row][c] = diag * u1[row][c] for the zeroed rows (au may be NULL): the identity rows of the
- * product A u1 that ox_assemble_first_au hands to the tentative-velocity solve (fracstep.py:470-472 + :521). */
+ * product A u1 that ox_assemble_first (args.a_u1) hands to the tentative-velocity solve (fracstep.py:470-472 + :521). */
 int ox_zero_rows_au(const ox_sell *A, const int32_t *rows, int64_t n, double diag, double *au,
                     const double *u1, int ncomp, void *stream);
 /* DOLFINx assemble_matrix(..., bcs) on the pressure Laplacian (fracstep.py:379):
@@ -405,15 +405,21 @@ int ox_zero_rows_au(const ox_sell *A, const int32_t *rows, int64_t n, double dia
 int ox_zero_rows_cols(const ox_sell *A, const uint8_t *is_bc, double diag, void *stream);
 
 /* ---- A1/A2/A3: one-off assemble_matrix of mass / stiffness (fracstep.py:373-380) ---- */
-/* kind 0: u*v*dx, kind 1: inner(grad u, grad v)*dx.  Square Lagrange space of `degree`
- * on `cells`; cell_dofs [n_cells][nd]; adj_pos [pairs][pw] gives, per (row, cell) pair,
- * the in-row index k of every cell dof.  Overwrites A->vals.  Slices are launched per width
- * bin: bin b covers bin_slices[bin_ptr_host[b] .. bin_ptr_host[b+1]) (device list) whose rows
- * are at most bin_width_host[b] entries wide (sizes the per-wave LDS accumulator). */
-int ox_assemble_matrix(int kind, int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                       const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                       int n_bins, const int64_t *bin_ptr_host, const int32_t *bin_slices,
-                       const int32_t *bin_width_host, void *stream);
+/* kind 0: u*v*dx, kind 1: inner(grad u, grad v)*dx on the square Lagrange space `space` over `cells`.  Overwrites A->vals.
+ * `space` is the view ox_space_view filled (or a caller's own struct); the row-assembly entry points read ONLY
+ *   degree, pw, cell_dofs ([n_cells][nd]), adj, adj_pos ([pairs][pw]: per (row, cell) pair the in-row index k of every
+ *   cell dof), pattern.{n_bins, bin_ptr_host, bin_slices, bin_width_host, n_row_blocks, row_blk_ptr, row_blk_entries}.
+ * row_blocks = 0: one launch per width bin -- bin b covers bin_slices[bin_ptr_host[b] .. bin_ptr_host[b+1]) (device
+ *   list) whose rows are at most bin_width_host[b] entries wide (sizes the per-wave LDS accumulator).
+ * row_blocks = 1: ONE launch over the slices in storage order (round 5): row block b = the consecutive slices
+ *   [row_blk_ptr[b], row_blk_ptr[b+1]), one per wave of a 512-thread block, accumulators for row_blk_entries storage
+ *   slots per block.  An error on a pattern with n_row_blocks == 0: the caller chooses the form.  The width bins send
+ *   the slices of one length-sort window -- one compact region of the mesh -- to up to ten launches, each of which
+ *   fetches that region's cell records and coefficients again (refined Delaunay mesh: 95.9 GB of HBM traffic per call
+ *   for ~22 GB of streams); in storage order the rows of a cell meet in one L2.  Per slice the same operations in the
+ *   same order: bit-identical results. */
+int ox_assemble_matrix(int kind, const ox_cells *cells, const ox_space_info *space, const ox_sell *A, int row_blocks,
+                       void *stream);
 /* w[row] = int phi_row dx (body-force vector for constant f: fracstep.py:387-390, and
  * the weights of assemble_scalar(phi*dx): fracstep.py:585-590). */
 int ox_assemble_weights(int degree, const ox_cells *cells, const ox_adj *adj, int64_t n_rows,
@@ -433,43 +439,27 @@ int ox_assemble_load_vector(const ox_cells *cells, const ox_adj *adj, int64_t n_
  *   Ar  = -0.5*C + (1/dt)*M - 0.5*nu*K                                     (:438-442)
  *   b_first[:, i] = Ar @ u1[:, i] + b0[:, i]                               (:449-458)
  *   A   = -Ar + (2/dt)*M                                                   (:468-469)
- * M, K, A share one SELL pattern (fracstep.py:293-294).  Slices are launched per
- * width bin (bin_ptr/bin_slices/bin_width from the host) so each launch sizes its
- * LDS accumulator for the widest row of the bin. */
-int ox_assemble_first(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                      const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                      const ox_sell *M, const ox_sell *K, const double *uab,
-                      const double *u1, const double *b0, double *b_first, double dt, double nu,
-                      int n_bins, const int64_t *bin_ptr_host, const int32_t *bin_slices,
-                      const int32_t *bin_width_host, void *stream);
+ * M, K, A share one SELL pattern (fracstep.py:293-294).  space, row_blocks: as for ox_assemble_matrix.
+ * a_u1 (device [n_rows][gdim]) = (the assembled A) @ u1 row by row, with the entry order and operations of ox_spmv:
+ * where u1 is also the initial guess of the tentative-velocity solve (fracstep.py:521 with
+ * -ksp_initial_guess_nonzero) it is that solve's first mat-vec (ox_ksp_options.ax0), once the rows ox_zero_rows_au
+ * turns into identity rows have been set to u1.
+ * nut (device [n_cells], kernel cell order: ox_eddy_viscosity / ox_viscosity_law): C is replaced by
+ * C + sum_e nut[e] K_e (K_e: the stiffness matrix of cell e), i.e. A = M/dt + C/2 + (nu K + K_nut)/2 and b_first to
+ * match: the Laplacian form div(nut grad u) of a viscosity that varies per cell.  Same launch forms, same epilogue;
+ * nut = 0 everywhere gives the bits of nut == NULL. */
+typedef struct {
+  const double *uab, *u1, *b0;  /* device, interleaved [n][gdim]                                          */
+  double *b_first;
+  double dt, nu;
+  double *a_u1;                 /* optional: (assembled A) @ u1, NULL = not formed                         */
+  const double *nut;            /* optional: per-cell viscosity, kernel cell order; NULL = the
+                                   constant-viscosity instantiations (not "nut = 0")                       */
+} ox_first_args;
+int ox_assemble_first(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
+                      const ox_sell *K, const ox_first_args *args, int row_blocks, void *stream);
 
-/* The same, and a_u1 (device [n_rows][gdim], may be NULL) = (the assembled A) @ u1 row by row, with the
- * entry order and operations of ox_spmv: where u1 is also the initial guess of the tentative-velocity
- * solve (fracstep.py:521 with -ksp_initial_guess_nonzero) it is that solve's first mat-vec
- * (ox_ksp_solve_ax0), once the rows ox_zero_rows turns into identity rows have been set to u1. */
-int ox_assemble_first_au(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                         const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                         const ox_sell *M, const ox_sell *K, const double *uab,
-                         const double *u1, const double *b0, double *b_first, double dt, double nu,
-                         int n_bins, const int64_t *bin_ptr_host, const int32_t *bin_slices,
-                         const int32_t *bin_width_host, void *stream, double *a_u1);
-
-/* The same two in ONE launch over the slices in storage order (round 5): row block b = the consecutive slices
- * [blk_ptr[b], blk_ptr[b+1]), one per wave of a 512-thread block, accumulators for lds_entries storage slots per block
- * (ox_pattern_info.n_row_blocks / row_blk_ptr / row_blk_entries).  The width bins send the slices of one length-sort
- * window -- one compact region of the mesh -- to up to ten launches, each of which fetches that region's cell records
- * and coefficients again (refined Delaunay mesh: 95.9 GB of HBM traffic per call for ~22 GB of streams); in storage
- * order the rows of a cell meet in one L2.  Per slice the same operations in the same order: bit-identical results. */
-int ox_assemble_matrix_blocks(int kind, int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                              const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A, int n_blocks,
-                              const int32_t *blk_ptr, int64_t lds_entries, void *stream);
-int ox_assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                             const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
-                             const double *uab, const double *u1, const double *b0, double *b_first, double dt,
-                             double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
-                             double *a_u1);
-
-/* ---- eddy-viscosity models: a viscosity per cell in the fused assemble_first ---- */
+/* ---- eddy-viscosity models: a viscosity per cell for ox_first_args.nut ---- */
 /* nut[e], e in kernel cell order (the order of cells->geom and cell_dofs), from grad uab at the cell's centroid:
  * model 0, Smagorinsky: (coefficient Delta)^2 sqrt(2 S:S); model 1, WALE (gdim = 3 only):
  * (coefficient Delta)^2 (Sd:Sd)^(3/2) / ((S:S)^(5/2) + (Sd:Sd)^(5/4)), 0 where the denominator is 0; S = sym(grad uab),
@@ -477,22 +467,6 @@ int ox_assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *c
  * [n_cells][nd] of the velocity component space of `degree` (1, 2, 3).  One lane per cell. */
 int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
                       double coefficient, double *nut, void *stream);
-/* ox_assemble_first_au / ox_assemble_first_blocks with C replaced by C + sum_e nut[e] K_e (K_e: the stiffness matrix of
- * cell e), i.e. A = M/dt + C/2 + (nu K + K_nut)/2 and b_first to match: the Laplacian form div(nut grad u) of a viscosity
- * that varies per cell.  nut: device [n_cells], kernel cell order, not NULL.  Same launch forms, same epilogue, a_u1 as
- * there; nut = 0 everywhere gives the bits of the plain entry points. */
-int ox_assemble_first_au_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                             const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                             const ox_sell *M, const ox_sell *K, const double *uab,
-                             const double *u1, const double *b0, double *b_first, double dt, double nu,
-                             int n_bins, const int64_t *bin_ptr_host, const int32_t *bin_slices,
-                             const int32_t *bin_width_host, void *stream, double *a_u1, const double *nut);
-int ox_assemble_first_blocks_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                                 const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
-                                 const double *uab, const double *u1, const double *b0, double *b_first, double dt,
-                                 double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
-                                 double *a_u1, const double *nut);
-
 /* ---- generalised-Newtonian laws and the full stress form ---- */
 /* nut[e] = max(nu(gd_e) - base, 0), gd = sqrt(2 S:S) with S = sym(grad uab) at the cell's centroid (the quantity of
  * ox_eddy_viscosity's Smagorinsky model), arguments as there.  law 2, Carreau-Yasuda, params = {nu0, nu_inf, lam, n, a}:
@@ -723,7 +697,7 @@ int ox_probe_sample(int degree, int gdim, const int32_t *cell_dofs, int64_t n_ce
 /* ---- Passive scalar transport (ox_scalar.hip) ------------------------------------------------------------------------
  * The Crank-Nicolson system of a group of 1..OX_MAXC scalars (same diffusivity kappa, same Dirichlet rows) from the
  * matrices of the velocity step, in ONE pass over the shared SELL-64 pattern -- no element loop:
- *   A   : the velocity matrix as ox_assemble_first* leaves it, M/dt + C(u_ab)/2 + nu K/2, BEFORE ox_zero_rows* on it
+ *   A   : the velocity matrix as ox_assemble_first leaves it, M/dt + C(u_ab)/2 + nu K/2, BEFORE ox_zero_rows* on it
  *   A_c = A + s K                           (s = (kappa - nu)/2; written to Ac->vals, padding slots stay 0)
  *   b   = (2/dt) M c1 - A_c c1 + b0         (= (M/dt - C/2 - kappa K/2) c1 + b0; rows < n_rows)
  *   a_c1 = A_c c1                            (optional, may be NULL: bit-identical to ox_spmv(Ac, c1), the solver's ax0)

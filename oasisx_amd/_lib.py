@@ -158,6 +158,19 @@ class ox_rect_info(C.Structure):
     ]
 
 
+class ox_first_args(C.Structure):
+    _fields_ = [
+        ("uab", C.c_void_p),
+        ("u1", C.c_void_p),
+        ("b0", C.c_void_p),
+        ("b_first", C.c_void_p),
+        ("dt", C.c_double),
+        ("nu", C.c_double),
+        ("a_u1", C.c_void_p),
+        ("nut", C.c_void_p),
+    ]
+
+
 class ox_mg_level(C.Structure):
     _fields_ = [
         ("A", ox_sell),
@@ -243,28 +256,12 @@ SIGNATURES = {
     "ox_zero_rows": (_I, [C.POINTER(ox_sell), _P, _L, _D, _P]),
     "ox_zero_rows_au": (_I, [C.POINTER(ox_sell), _P, _L, _D, _P, _P, _I, _P]),
     "ox_zero_rows_cols": (_I, [C.POINTER(ox_sell), _P, _D, _P]),
-    "ox_assemble_matrix": (_I, [_I, _I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _P, _I,
-                                C.POINTER(ox_sell), _I, C.POINTER(_L), _P, C.POINTER(C.c_int32), _P]),
+    "ox_assemble_matrix": (_I, [_I, C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), _I, _P]),
     "ox_assemble_weights": (_I, [_I, C.POINTER(ox_cells), C.POINTER(ox_adj), _L, _P, _P]),
     "ox_assemble_load_vector": (_I, [C.POINTER(ox_cells), C.POINTER(ox_adj), _L, _I, _I, _P, _P, _P, _P]),
-    "ox_assemble_first": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _P, _I,
-                               C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _P, _P, _P, _D,
-                               _D, _I, C.POINTER(_L), _P, C.POINTER(C.c_int32), _P]),
-    "ox_assemble_first_au": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _P, _I,
-                                  C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _P, _P, _P, _D,
-                                  _D, _I, C.POINTER(_L), _P, C.POINTER(C.c_int32), _P, _P]),
-    "ox_assemble_matrix_blocks": (_I, [_I, _I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _P, _I, C.POINTER(ox_sell), _I, _P,
-                                       _L, _P]),
-    "ox_assemble_first_blocks": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _P, _I,
-                                      C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _P, _P, _P, _D,
-                                      _D, _I, _P, _L, _P, _P]),
+    "ox_assemble_first": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), C.POINTER(ox_sell),
+                               C.POINTER(ox_sell), C.POINTER(ox_first_args), _I, _P]),
     "ox_eddy_viscosity": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, _P, _P]),
-    "ox_assemble_first_au_nut": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _P, _I,
-                                      C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _P, _P, _P, _D,
-                                      _D, _I, C.POINTER(_L), _P, C.POINTER(C.c_int32), _P, _P, _P]),
-    "ox_assemble_first_blocks_nut": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _P, _I,
-                                          C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _P, _P, _P, _D,
-                                          _D, _I, _P, _L, _P, _P, _P]),
     "ox_viscosity_law": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, C.POINTER(_D), _I, _P, _P]),
     "ox_assemble_stress_transpose": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P, _P, _D, _P, _P]),
     "ox_assemble_grad_vector": (_I, [_I, _I, _I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P,

@@ -697,128 +697,110 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_assemble_rows(ox_cells cell
   }
 }
 
-template <int GDIM, int DEG, int KIND, int PW, bool DICT = false, bool NUT = false>
-static int launch_rows_t(const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                         const uint8_t *adj_pos, const ox_sell *A, const FirstArgsT<NUT> &F, int n_bins,
-                         const int64_t *bin_ptr, const int32_t *bin_slices, const int32_t *bin_width,
-                         hipStream_t st) {
-  if constexpr (KIND == OX_KIND_CONV && !DICT) {
-    if (F.Mc && F.Kc && F.Md && F.Kd && F.nMd >= 1 && F.nMd <= 256 && F.nKd >= 1 && F.nKd <= 256)
-      return launch_rows_t<GDIM, DEG, KIND, PW, true, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_bins, bin_ptr,
-                                                      bin_slices, bin_width, st);
-  }
-  for (int b = 0; b < n_bins; ++b) {
-    const int64_t cnt = bin_ptr[b + 1] - bin_ptr[b];
-    if (cnt <= 0) continue;
-    // wave-private accumulators [width][64]; 4 waves per block unless the rows are so wide (unstructured
-    // meshes: > 70 entries) that fewer fit beside the 17 KB of tables
-    // (NUT: 134 KB, the row blocks' budget -- the stiffness tensor takes up to 5 KB of LDS more)
-    constexpr size_t CAP = NUT ? OX_ROW_BLOCK_LDS : 140 * 1024;
-    int nw = 4;
-    while (nw > 1 && (size_t)nw * bin_width[b] * 64 * sizeof(double) > CAP) nw >>= 1;
-    const size_t lds = (size_t)nw * bin_width[b] * 64 * sizeof(double);
-    if (lds > CAP) OX_FAIL("assemble: row width %d needs %zu B of LDS", bin_width[b], lds);
-    // (U = 2 / 3 (row, cell) pairs in flight per lane were measured at 128^3 -- 9.0 / 9.3 ms against 7.7 with one: the
-    // pair loop is bound by the texture path, every lane gathering from another cell, not by latency -- and their
-    // instantiations and the OX_ASSEMBLE_U / OX_ASSEMBLE_NW tuning switches removed in round 5)
-    auto go = [&](auto kern) -> int {
-      if (lds > 32 * 1024)
-        OX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kern, dim3((unsigned)((cnt + nw - 1) / nw)), dim3(64 * nw), lds, st, *cells, cell_dofs, *adj,
-                         adj_pos, *A, F, bin_slices + bin_ptr[b], (int)cnt, (int)bin_width[b]);
-      OX_LAUNCH_CHECK();
-      return 0;
-    };
-    const int rc = go(k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1, false, NUT>);
-    if (rc) return rc;
+// One row launch on the host: what it reads of the space (include/oasisx_hip.h: ox_assemble_matrix) and its form --
+// one launch per width bin, or ONE launch over the row blocks (k_assemble_rows<..., BLK = true>, 8 waves per block).
+struct RowLaunch {
+  const ox_cells *cells;
+  const ox_space_info *V;
+  bool blocks;
+  hipStream_t st;
+};
+
+static int row_launch_check(const char *who, const ox_space_info *V, int row_blocks) {
+  const ox_pattern_info &P = V->pattern;
+  if (!V->cell_dofs || !V->adj_pos) OX_FAIL("%s: null argument", who);
+  if (row_blocks == 0) {
+    if (P.n_bins > 0 && (!P.bin_ptr_host || !P.bin_slices || !P.bin_width_host)) OX_FAIL("%s: null argument", who);
+  } else if (row_blocks == 1) {
+    if (P.n_row_blocks <= 0)
+      OX_FAIL("%s: row_blocks=1 on a pattern without row blocks (n_row_blocks=%d): launch it per width bin", who,
+              (int)P.n_row_blocks);
+    if (!P.row_blk_ptr) OX_FAIL("%s: null argument", who);
+  } else {
+    OX_FAIL("%s: row_blocks=%d", who, row_blocks);
   }
   return 0;
 }
 
-// row-block launch (k_assemble_rows<..., BLK = true>): one launch, 8 waves per block
 template <int GDIM, int DEG, int KIND, int PW, bool DICT = false, bool NUT = false>
-static int launch_row_blocks_t(const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj, const uint8_t *adj_pos,
-                               const ox_sell *A, const FirstArgsT<NUT> &F, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries,
-                               hipStream_t st) {
+static int launch_rows_t(const RowLaunch &L, const ox_sell *A, const FirstArgsT<NUT> &F) {
   if constexpr (KIND == OX_KIND_CONV && !DICT) {
     if (F.Mc && F.Kc && F.Md && F.Kd && F.nMd >= 1 && F.nMd <= 256 && F.nKd >= 1 && F.nKd <= 256)
-      return launch_row_blocks_t<GDIM, DEG, KIND, PW, true, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_blocks, blk_ptr, lds_entries, st);
+      return launch_rows_t<GDIM, DEG, KIND, PW, true, NUT>(L, A, F);
   }
-  if (n_blocks <= 0) return 0;
-  const size_t lds = (size_t)lds_entries * sizeof(double);
+  const ox_space_info &V = *L.V;
+  const ox_pattern_info &P = V.pattern;
+  auto go = [&](auto kern, unsigned grid, unsigned block, size_t lds, const int32_t *list, int n_list, int width) -> int {
+    if (lds > 32 * 1024)
+      OX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, L.st, *L.cells, V.cell_dofs, V.adj, V.adj_pos, *A, F, list,
+                       n_list, width);
+    OX_LAUNCH_CHECK();
+    return 0;
+  };
+  if (!L.blocks) {
+    for (int b = 0; b < P.n_bins; ++b) {
+      const int64_t cnt = P.bin_ptr_host[b + 1] - P.bin_ptr_host[b];
+      if (cnt <= 0) continue;
+      const int width = P.bin_width_host[b];
+      // wave-private accumulators [width][64]; 4 waves per block unless the rows are so wide (unstructured
+      // meshes: > 70 entries) that fewer fit beside the 17 KB of tables
+      // (NUT: 134 KB, the row blocks' budget -- the stiffness tensor takes up to 5 KB of LDS more)
+      constexpr size_t CAP = NUT ? OX_ROW_BLOCK_LDS : 140 * 1024;
+      int nw = 4;
+      while (nw > 1 && (size_t)nw * width * 64 * sizeof(double) > CAP) nw >>= 1;
+      const size_t lds = (size_t)nw * width * 64 * sizeof(double);
+      if (lds > CAP) OX_FAIL("assemble: row width %d needs %zu B of LDS", width, lds);
+      // (U = 2 / 3 (row, cell) pairs in flight per lane were measured at 128^3 -- 9.0 / 9.3 ms against 7.7 with one: the
+      // pair loop is bound by the texture path, every lane gathering from another cell, not by latency -- and their
+      // instantiations and the OX_ASSEMBLE_U / OX_ASSEMBLE_NW tuning switches removed in round 5)
+      const int rc = go(k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1, false, NUT>, (unsigned)((cnt + nw - 1) / nw), 64u * nw,
+                        lds, P.bin_slices + P.bin_ptr_host[b], (int)cnt, width);
+      if (rc) return rc;
+    }
+    return 0;
+  }
+  const size_t lds = (size_t)P.row_blk_entries * sizeof(double);
   if (lds > OX_ROW_BLOCK_LDS) OX_FAIL("assemble: a row block needs %zu B of LDS (limit %d)", lds, OX_ROW_BLOCK_LDS);
-  auto kern = k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1, true, NUT>;
-  if (lds > 32 * 1024)
-    OX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)n_blocks), dim3(512), lds, st, *cells, cell_dofs, *adj, adj_pos, *A, F, blk_ptr,
-                     n_blocks, 0);
-  OX_LAUNCH_CHECK();
-  return 0;
+  return go(k_assemble_rows<GDIM, DEG, KIND, PW, DICT, 1, true, NUT>, (unsigned)P.n_row_blocks, 512u, lds, P.row_blk_ptr,
+            (int)P.n_row_blocks, 0);
 }
+
 template <int KIND, bool NUT = false>
-static int launch_row_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                             const uint8_t *adj_pos, int pw, const ox_sell *A, const FirstArgsT<NUT> &F, int n_blocks,
-                             const int32_t *blk_ptr, int64_t lds_entries, hipStream_t st) {
-  const int g = cells->gdim;
-#define OX_ROWS_CASE(GD, DG, P)                                                                                       \
-  if (g == GD && degree == DG) {                                                                                      \
-    if (pw != P) OX_FAIL("assemble: adj_pos stride %d, expected %d", pw, P);                                          \
-    return launch_row_blocks_t<GD, DG, KIND, P, false, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_blocks, blk_ptr, lds_entries, st); \
+static int launch_rows(const RowLaunch &L, const ox_sell *A, const FirstArgsT<NUT> &F) {
+  const int g = L.cells->gdim, degree = L.V->degree, pw = L.V->pw;
+#define OX_ROWS_CASE(GD, DG, P)                                              \
+  if (g == GD && degree == DG) {                                             \
+    if (pw != P) OX_FAIL("assemble: adj_pos stride %d, expected %d", pw, P); \
+    return launch_rows_t<GD, DG, KIND, P, false, NUT>(L, A, F);              \
   }
   OX_ROWS_CASE(2, 1, 4) OX_ROWS_CASE(2, 2, 8) OX_ROWS_CASE(3, 1, 4) OX_ROWS_CASE(3, 2, 16) OX_ROWS_CASE(2, 3, 16) OX_ROWS_CASE(3, 3, 32)
 #undef OX_ROWS_CASE
   OX_FAIL("assemble: unsupported gdim=%d degree=%d", g, degree);
 }
 
-template <int KIND, bool NUT = false>
-static int launch_rows(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                       const uint8_t *adj_pos, int pw, const ox_sell *A, const FirstArgsT<NUT> &F,
-                       int n_bins, const int64_t *bin_ptr, const int32_t *bin_slices,
-                       const int32_t *bin_width, hipStream_t st) {
-  const int g = cells->gdim;
-#define OX_ROWS_CASE(GD, DG, P)                                                               \
-  if (g == GD && degree == DG) {                                                              \
-    if (pw != P) OX_FAIL("assemble: adj_pos stride %d, expected %d", pw, P);                  \
-    return launch_rows_t<GD, DG, KIND, P, false, NUT>(cells, cell_dofs, adj, adj_pos, A, F, n_bins, bin_ptr, \
-                                          bin_slices, bin_width, st);                         \
-  }
-  OX_ROWS_CASE(2, 1, 4) OX_ROWS_CASE(2, 2, 8) OX_ROWS_CASE(3, 1, 4) OX_ROWS_CASE(3, 2, 16) OX_ROWS_CASE(2, 3, 16) OX_ROWS_CASE(3, 3, 32)
-#undef OX_ROWS_CASE
-  OX_FAIL("assemble: unsupported gdim=%d degree=%d", g, degree);
-}
-
-extern "C" int ox_assemble_matrix(int kind, int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                                  const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                                  int n_bins, const int64_t *bin_ptr_host, const int32_t *bin_slices,
-                                  const int32_t *bin_width_host, void *stream) {
-  if (!cells || !cell_dofs || !adj || !adj_pos || !A) OX_FAIL("ox_assemble_matrix: null argument");
+extern "C" int ox_assemble_matrix(int kind, const ox_cells *cells, const ox_space_info *space, const ox_sell *A,
+                                  int row_blocks, void *stream) {
+  if (!cells || !space || !A) OX_FAIL("ox_assemble_matrix: null argument");
+  if (kind != OX_KIND_MASS && kind != OX_KIND_STIFF) OX_FAIL("ox_assemble_matrix: kind=%d", kind);
+  if (row_launch_check("ox_assemble_matrix", space, row_blocks)) return -1;
+  const RowLaunch L{cells, space, row_blocks == 1, ox_stream(stream)};
   FirstArgsT<false> F{};
-  hipStream_t st = ox_stream(stream);
-  if (kind == OX_KIND_MASS)
-    return launch_rows<OX_KIND_MASS>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_bins,
-                                     bin_ptr_host, bin_slices, bin_width_host, st);
-  if (kind == OX_KIND_STIFF)
-    return launch_rows<OX_KIND_STIFF>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_bins,
-                                      bin_ptr_host, bin_slices, bin_width_host, st);
-  OX_FAIL("ox_assemble_matrix: kind=%d", kind);
+  return kind == OX_KIND_MASS ? launch_rows<OX_KIND_MASS>(L, A, F) : launch_rows<OX_KIND_STIFF>(L, A, F);
 }
 
 // nut == nullptr: the constant-viscosity form, the instantiations and argument blocks of before
-static int assemble_first_bins(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                               const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                               const ox_sell *M, const ox_sell *K, const double *uab,
-                               const double *u1, const double *b0, double *b_first, double dt,
-                               double nu, int n_bins, const int64_t *bin_ptr_host,
-                               const int32_t *bin_slices, const int32_t *bin_width_host,
-                               void *stream, double *a_u1, const double *nut) {
-  if (!cells || !cell_dofs || !adj || !adj_pos || !A || !M || !K || !M->vals || !K->vals || !uab || !u1 ||
-      !b0 || !b_first)
+extern "C" int ox_assemble_first(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
+                                 const ox_sell *K, const ox_first_args *args, int row_blocks, void *stream) {
+  if (!cells || !space || !A || !M || !K || !args || !M->vals || !K->vals || !args->uab || !args->u1 || !args->b0 ||
+      !args->b_first)
     OX_FAIL("ox_assemble_first: null argument");
+  if (row_launch_check("ox_assemble_first", space, row_blocks)) return -1;
   if (M->slice_ptr != A->slice_ptr || K->slice_ptr != A->slice_ptr)
     OX_FAIL("ox_assemble_first: M, K and A must share one sparsity pattern");
-  if (!(dt > 0.0)) OX_FAIL("ox_assemble_first: dt=%g", dt);
-  FirstArgs F{M->vals, K->vals, uab, u1, b0, b_first, a_u1, 1.0 / dt, nu,
+  if (!(args->dt > 0.0)) OX_FAIL("ox_assemble_first: dt=%g", args->dt);
+  const RowLaunch L{cells, space, row_blocks == 1, ox_stream(stream)};
+  FirstArgs F{M->vals, K->vals, args->uab, args->u1, args->b0, args->b_first, args->a_u1, 1.0 / args->dt, args->nu,
               M->vcode, K->vcode, M->vdict, K->vdict, M->n_dict, K->n_dict};
 #ifdef OX_DIAG
   {
@@ -826,125 +808,20 @@ static int assemble_first_bins(int degree, const ox_cells *cells, const int32_t 
     F.dbg = e ? atoi(e) : 0;
   }
 #endif
-  if (ox_prof_on) ox_prof_start(OX_TAG_ASSEMBLE_FIRST, ox_stream(stream));
+  if (ox_prof_on) ox_prof_start(OX_TAG_ASSEMBLE_FIRST, L.st);
   int rc;
-  if (nut) {
+  if (args->nut) {
     FirstArgsT<true> Fn{};
     static_cast<FirstArgs &>(Fn) = F;
-    Fn.nut = nut;
-    rc = launch_rows<OX_KIND_CONV, true>(degree, cells, cell_dofs, adj, adj_pos, pw, A, Fn, n_bins, bin_ptr_host, bin_slices,
-                                         bin_width_host, ox_stream(stream));
+    Fn.nut = args->nut;
+    rc = launch_rows<OX_KIND_CONV, true>(L, A, Fn);
   } else {
     FirstArgsT<false> F0{};
     static_cast<FirstArgs &>(F0) = F;
-    rc = launch_rows<OX_KIND_CONV>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F0, n_bins,
-                                   bin_ptr_host, bin_slices, bin_width_host, ox_stream(stream));
+    rc = launch_rows<OX_KIND_CONV>(L, A, F0);
   }
-  if (ox_prof_on) ox_prof_stop(ox_stream(stream));
+  if (ox_prof_on) ox_prof_stop(L.st);
   return rc;
-}
-
-extern "C" int ox_assemble_first_au(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                                    const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                                    const ox_sell *M, const ox_sell *K, const double *uab,
-                                    const double *u1, const double *b0, double *b_first, double dt,
-                                    double nu, int n_bins, const int64_t *bin_ptr_host,
-                                    const int32_t *bin_slices, const int32_t *bin_width_host,
-                                    void *stream, double *a_u1) {
-  return assemble_first_bins(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_bins,
-                             bin_ptr_host, bin_slices, bin_width_host, stream, a_u1, nullptr);
-}
-
-extern "C" int ox_assemble_first_au_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                                        const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                                        const ox_sell *M, const ox_sell *K, const double *uab,
-                                        const double *u1, const double *b0, double *b_first, double dt,
-                                        double nu, int n_bins, const int64_t *bin_ptr_host,
-                                        const int32_t *bin_slices, const int32_t *bin_width_host,
-                                        void *stream, double *a_u1, const double *nut) {
-  if (!nut) OX_FAIL("ox_assemble_first_au_nut: null nut (the constant-viscosity form is ox_assemble_first_au)");
-  return assemble_first_bins(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_bins,
-                             bin_ptr_host, bin_slices, bin_width_host, stream, a_u1, nut);
-}
-
-extern "C" int ox_assemble_first(int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                                 const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A,
-                                 const ox_sell *M, const ox_sell *K, const double *uab,
-                                 const double *u1, const double *b0, double *b_first, double dt,
-                                 double nu, int n_bins, const int64_t *bin_ptr_host,
-                                 const int32_t *bin_slices, const int32_t *bin_width_host,
-                                 void *stream) {
-  return ox_assemble_first_au(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_bins,
-                              bin_ptr_host, bin_slices, bin_width_host, stream, nullptr);
-}
-
-extern "C" int ox_assemble_matrix_blocks(int kind, int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                                         const ox_adj *adj, const uint8_t *adj_pos, int pw, const ox_sell *A, int n_blocks,
-                                         const int32_t *blk_ptr, int64_t lds_entries, void *stream) {
-  if (!cells || !cell_dofs || !adj || !adj_pos || !A || (n_blocks > 0 && !blk_ptr)) OX_FAIL("ox_assemble_matrix_blocks: null argument");
-  FirstArgsT<false> F{};
-  hipStream_t st = ox_stream(stream);
-  if (kind == OX_KIND_MASS)
-    return launch_row_blocks<OX_KIND_MASS>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_blocks, blk_ptr, lds_entries, st);
-  if (kind == OX_KIND_STIFF)
-    return launch_row_blocks<OX_KIND_STIFF>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F, n_blocks, blk_ptr, lds_entries, st);
-  OX_FAIL("ox_assemble_matrix_blocks: kind=%d", kind);
-}
-
-static int assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                                 const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
-                                 const double *uab, const double *u1, const double *b0, double *b_first, double dt,
-                                 double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
-                                 double *a_u1, const double *nut) {
-  if (!cells || !cell_dofs || !adj || !adj_pos || !A || !M || !K || !M->vals || !K->vals || !uab || !u1 || !b0 ||
-      !b_first || (n_blocks > 0 && !blk_ptr))
-    OX_FAIL("ox_assemble_first_blocks: null argument");
-  if (M->slice_ptr != A->slice_ptr || K->slice_ptr != A->slice_ptr)
-    OX_FAIL("ox_assemble_first: M, K and A must share one sparsity pattern");
-  if (!(dt > 0.0)) OX_FAIL("ox_assemble_first: dt=%g", dt);
-  FirstArgs F{M->vals, K->vals, uab, u1, b0, b_first, a_u1, 1.0 / dt, nu,
-              M->vcode, K->vcode, M->vdict, K->vdict, M->n_dict, K->n_dict};
-#ifdef OX_DIAG
-  {
-    const char *e = getenv("OX_AF_DBG");
-    F.dbg = e ? atoi(e) : 0;
-  }
-#endif
-  if (ox_prof_on) ox_prof_start(OX_TAG_ASSEMBLE_FIRST, ox_stream(stream));
-  int rc;
-  if (nut) {
-    FirstArgsT<true> Fn{};
-    static_cast<FirstArgs &>(Fn) = F;
-    Fn.nut = nut;
-    rc = launch_row_blocks<OX_KIND_CONV, true>(degree, cells, cell_dofs, adj, adj_pos, pw, A, Fn, n_blocks, blk_ptr, lds_entries,
-                                               ox_stream(stream));
-  } else {
-    FirstArgsT<false> F0{};
-    static_cast<FirstArgs &>(F0) = F;
-    rc = launch_row_blocks<OX_KIND_CONV>(degree, cells, cell_dofs, adj, adj_pos, pw, A, F0, n_blocks, blk_ptr, lds_entries,
-                                         ox_stream(stream));
-  }
-  if (ox_prof_on) ox_prof_stop(ox_stream(stream));
-  return rc;
-}
-
-extern "C" int ox_assemble_first_blocks(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                                        const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M, const ox_sell *K,
-                                        const double *uab, const double *u1, const double *b0, double *b_first, double dt,
-                                        double nu, int n_blocks, const int32_t *blk_ptr, int64_t lds_entries, void *stream,
-                                        double *a_u1) {
-  return assemble_first_blocks(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_blocks,
-                               blk_ptr, lds_entries, stream, a_u1, nullptr);
-}
-
-extern "C" int ox_assemble_first_blocks_nut(int degree, const ox_cells *cells, const int32_t *cell_dofs, const ox_adj *adj,
-                                            const uint8_t *adj_pos, int pw, const ox_sell *A, const ox_sell *M,
-                                            const ox_sell *K, const double *uab, const double *u1, const double *b0,
-                                            double *b_first, double dt, double nu, int n_blocks, const int32_t *blk_ptr,
-                                            int64_t lds_entries, void *stream, double *a_u1, const double *nut) {
-  if (!nut) OX_FAIL("ox_assemble_first_blocks_nut: null nut (the constant-viscosity form is ox_assemble_first_blocks)");
-  return assemble_first_blocks(degree, cells, cell_dofs, adj, adj_pos, pw, A, M, K, uab, u1, b0, b_first, dt, nu, n_blocks,
-                               blk_ptr, lds_entries, stream, a_u1, nut);
 }
 
 // ---------------------------------------------------------------------------------------

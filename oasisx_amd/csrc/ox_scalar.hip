@@ -1,7 +1,7 @@
 // Passive scalar transport: the Crank-Nicolson operator and right-hand side of a scalar group from the matrices the
 // velocity step has at hand.
 //
-//   A   = M/dt + C(u_ab)/2 + nu K/2        what ox_assemble_first* leaves in the velocity matrix BEFORE its Dirichlet rows
+//   A   = M/dt + C(u_ab)/2 + nu K/2        what ox_assemble_first leaves in the velocity matrix BEFORE its Dirichlet rows
 //   A_c = A + s K,  s = (kappa - nu)/2     the scalar's operator: same convection, its own diffusivity
 //   b_c = (2/dt) M c_1 - A_c c_1 + b0_c    = (M/dt - C/2 - kappa K/2) c_1 + b0_c
 //

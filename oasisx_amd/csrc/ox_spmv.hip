@@ -1156,7 +1156,7 @@ __device__ __forceinline__ int64_t ox_entry(const int64_t base, int k, int lane)
 
 // One wave per 64 listed rows, each lane its row: the (k, k+1) pairs of a row are 16 B apart-aligned, so a lane
 // stores 16 B at a time.  au (optional): the identity row's product with u1, (A u1)[row] = u1[row], for the
-// mat-vec the fused assembly hands to the tentative-velocity solve (ox_assemble_first_au) -- one launch instead
+// mat-vec the fused assembly hands to the tentative-velocity solve (ox_assemble_first, args.a_u1) -- one launch instead
 // of a zero-rows launch plus two indexed copies per boundary condition.
 __global__ __launch_bounds__(64) void k_zero_rows(ox_sell A, const int32_t *__restrict__ rows, int64_t n, double diag,
                                                   double *__restrict__ au, const double *__restrict__ u1, int ncomp) {

@@ -1,5 +1,5 @@
 // Eddy viscosity per cell: nut[e] from grad u_ab at the cell's centroid, for the fused
-// assemble_first with a per-cell viscosity (ox_assemble_first_*_nut).
+// assemble_first with a per-cell viscosity (ox_assemble_first with ox_first_args.nut).
 //
 //   g[d][k] = d(u_ab)_d / dx_k = sum_i u_ab[dof_i][d] sum_b dphi_i/dlambda_b (centroid) G[b][k]
 //   S       = (g + g^T)/2,   Delta^2 = |cell|^(2/gdim),  |cell| = |det J| / gdim!

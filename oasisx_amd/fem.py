@@ -195,7 +195,7 @@ def merge_small_bins(bin_width: np.ndarray, bin_ptr: np.ndarray):
 
 
 def row_blocks(widths: np.ndarray):
-    """Row blocks of the one-launch assembly kernels (``ox_assemble_first_blocks``; the library's twin: finish_pattern):
+    """Row blocks of the one-launch assembly kernels (``ox_assemble_first`` with ``row_blocks = 1``; the library's twin: finish_pattern):
     consecutive slices in storage order, greedily, at most ROW_BLOCK_WAVES per block and ROW_BLOCK_LDS bytes of LDS
     accumulators (width * 64 doubles per slice).  Returns (blk_ptr int32 [n_blocks + 1], entries of the largest block);
     no blocks at all when one slice alone exceeds the budget (the width bins serve such a pattern)."""
@@ -247,10 +247,6 @@ class SellPattern:
             row_blk = (torch.from_numpy(bp).to(self.device), big)
         self.row_blk_ptr, self.row_blk_entries = row_blk
         self.n_row_blocks = int(self.row_blk_ptr.shape[0]) - 1
-
-    def blocks_args(self):
-        """(n_blocks, blk_ptr, lds_entries) of ``ox_assemble_first_blocks`` / ``ox_assemble_matrix_blocks``."""
-        return self.n_row_blocks, _lib.ptr(self.row_blk_ptr), int(self.row_blk_entries)
 
     def split_interior(self, n_owned: int):
         """Mesh-partitioned operators: list the slices with the interior ones first (no ghost column,
@@ -425,10 +421,6 @@ class SellPattern:
             S.wt_ptr = self.wt_ptr.data_ptr()
             S.n_wb_interior = int(getattr(self, "n_wb_interior", None) or 0)
         return S
-
-    def bins_args(self):
-        return (int(self.bin_width.shape[0]), self.bin_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                _lib.ptr(self.bin_slices), self.bin_width.ctypes.data_as(C.POINTER(C.c_int32)))
 
     # ---- host-side conversions (tests / diagnostics, small sizes) ----------------------
     def slot_rows_k(self):
@@ -1002,6 +994,21 @@ class FunctionSpace:
             adj_pos[off[sl], :nd] = k.to(torch.uint8)
         self.adj = AdjTable(n_slices, nd, adj_ptr, adj_cell, adj_loc, adj_pos, pw)
         self.adj_count = cnt
+
+    def assembly_info(self) -> _lib.ox_space_info:
+        """The ``ox_space_info`` that ``ox_assemble_matrix`` / ``ox_assemble_first`` take: the fields they read (header), over
+        this space's own tensors -- library-built or not.  Built once; the space keeps it and the arrays it points to."""
+        if getattr(self, "_assembly_info", None) is None:
+            P, A = self.pattern, self.adj
+            keep = (self.cell_dofs, A.adj_ptr, A.adj_cell, A.adj_loc, A.adj_pos, P.bin_ptr, P.bin_width, P.bin_slices, P.row_blk_ptr)
+            v = _lib.ox_space_info(degree=self.degree, nd=A.nd, pw=A.pw, gdim=self.mesh.gdim, cell_dofs=self.cell_dofs.data_ptr(),
+                                   adj=A.struct(), adj_pos=A.adj_pos.data_ptr())
+            v.pattern.n_bins, v.pattern.bin_slices = int(P.bin_width.shape[0]), P.bin_slices.data_ptr()
+            v.pattern.bin_ptr_host, v.pattern.bin_width_host = P.bin_ptr.ctypes.data, P.bin_width.ctypes.data
+            v.pattern.n_row_blocks, v.pattern.row_blk_entries = P.n_row_blocks, int(P.row_blk_entries)
+            v.pattern.row_blk_ptr = P.row_blk_ptr.data_ptr()
+            self._assembly_info = (v, keep)
+        return self._assembly_info[0]
 
     def cells_in_kernel_order(self) -> np.ndarray:
         """Vertex ids of the cells in the order every per-cell device array uses (host copy)."""

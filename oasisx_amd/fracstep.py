@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from .fem import FieldStorage, Function, FunctionSpace, VectorFunctionSpace, cell_geometry
 from .ksp import KSPSolver
-from .la import MultiSellMatrix, SellMatrix
+from .la import MultiSellMatrix, SellMatrix, assemble_matrix
 
 __all__ = ["FractionalStep_AB_CN"]
 
@@ -169,7 +169,7 @@ class FractionalStep_AB_CN:
         self._spmv_windows = windows
         self._lattice = lattice
         # options["assemble_row_blocks"]: the row kernels -- assemble_first, M, K, Ap -- run as ONE launch over the slices in
-        # storage order (ox_assemble_first_blocks) instead of one launch per width bin; bit-identical either way.
+        # storage order (ox_assemble_first with row_blocks = 1) instead of one launch per width bin; bit-identical either way.
         # Default: on for meshes that are not lattices (refined Delaunay mesh at the bench size: nine bins, 95.9 GB of
         # HBM traffic and 18.3 ms per assemble_first -> one launch, 31.9 GB, 13.5 ms); off on lattice meshes, whose
         # three bins re-fetch little (24.6 GB) and whose LDS-filling blocks pay the dispatch gap between row blocks
@@ -331,29 +331,17 @@ class FractionalStep_AB_CN:
         self._A = SellMatrix(Vi.pattern, symmetric=False, name="A")
         self._Ap = SellMatrix(Q.pattern, symmetric=True, name="Ap")
 
-    def _assemble_matrix(self, kind, V: FunctionSpace, adj_struct, Mat: SellMatrix):
-        if self._row_blocks and V.pattern.n_row_blocks > 0:  # one launch over the slices in storage order
-            nblk, bptr, ent = V.pattern.blocks_args()
-            _lib.check(self._lib.ox_assemble_matrix_blocks(kind, V.degree, C.byref(self._cells), _lib.ptr(V.cell_dofs),
-                                                           C.byref(adj_struct), _lib.ptr(V.adj.adj_pos), V.adj.pw,
-                                                           Mat.ref(), nblk, bptr, ent, _lib.current_stream()),
-                       "ox_assemble_matrix_blocks")
-        else:
-            nb, bptr, bsl, bw = V.pattern.bins_args()
-            _lib.check(self._lib.ox_assemble_matrix(kind, V.degree, C.byref(self._cells), _lib.ptr(V.cell_dofs),
-                                                    C.byref(adj_struct), _lib.ptr(V.adj.adj_pos), V.adj.pw,
-                                                    Mat.ref(), nb, bptr, bsl, bw, _lib.current_stream()),
-                       "ox_assemble_matrix")
-        Mat.version += 1
+    def _assemble_matrix(self, kind, V: FunctionSpace, Mat: SellMatrix):
+        assemble_matrix(kind, V, self._cells, Mat, row_blocks=self._row_blocks and V.pattern.n_row_blocks > 0)
 
     def _preassemble(self):
         """Time-independent operators (reference fracstep.py:360-409)."""
         lib, st = self._lib, _lib.current_stream()
         Vi, Q = self._Vi[0][0], self._Q
         dev = self._mesh.device
-        self._assemble_matrix(0, Vi, self._adj_u, self._M)  # mass        (:373)
-        self._assemble_matrix(1, Vi, self._adj_u, self._K)  # stiffness   (:375)
-        self._assemble_matrix(1, Q, self._adj_q, self._Ap)  # pressure Laplacian (:379)
+        self._assemble_matrix(0, Vi, self._M)  # mass        (:373)
+        self._assemble_matrix(1, Vi, self._K)  # stiffness   (:375)
+        self._assemble_matrix(1, Q, self._Ap)  # pressure Laplacian (:379)
         if len(self._bcs_p) > 0:  # assemble_matrix(..., bcs): BC rows and columns -> identity
             is_bc = torch.zeros(Q.n_local, dtype=torch.uint8, device=dev)
             for bcp in self._bcs_p:
@@ -418,7 +406,6 @@ class FractionalStep_AB_CN:
         n = self._n_u * self._gdim
         # u_ab = 1.5 u_1 - 0.5 u_2 (:432-434)
         _lib.check(lib.ox_axpby(n, 1.5, self._U1.rptr(), -0.5, self._U2.rptr(), self._UAB.ptr(), st), "ox_axpby")
-        Vi = self._Vi[0][0]
         # With a nonzero initial guess the tentative solve starts from u (= u1 bit for bit unless someone
         # wrote to it since the last step): its first mat-vec A @ u1 falls out of the fused kernel's
         # epilogue (same entry order and operations as the SpMV).  Kept in the block of b3, free until
@@ -433,27 +420,9 @@ class FractionalStep_AB_CN:
                                  f"base_viscosity, so the step runs at nu = base_viscosity = {base}")
             # nut per cell from u_ab, then the fused kernel with nut K_c added to the convection rows of every cell
             self.viscosity_assemble()
-            self._assemble_first_nut(dt, nu, want_au)
-            if self._stress_form == "full":
-                self.stress_transpose_assemble()
-        elif self._row_blocks and Vi.pattern.n_row_blocks > 0:
-            # ONE launch over the slices in storage order (round 5): the rows of a cell meet in one L2 instead of being
-            # torn apart into the launches of up to ten width bins (options["assemble_row_blocks"]; bit-identical)
-            nblk, bptr, ent = Vi.pattern.blocks_args()
-            _lib.check(lib.ox_assemble_first_blocks(Vi.degree, C.byref(self._cells), _lib.ptr(Vi.cell_dofs),
-                                                    C.byref(self._adj_u), _lib.ptr(Vi.adj.adj_pos), Vi.adj.pw,
-                                                    self._A.ref(), self._M.ref(), self._K.ref(),
-                                                    self._UAB.rptr(), self._U1.rptr(), self._B0.rptr(), self._BFIRST.ptr(),
-                                                    float(dt), float(nu), nblk, bptr, ent, st,
-                                                    self._B3.ptr() if want_au else None), "ox_assemble_first_blocks")
-        else:
-            nb, bptr, bsl, bw = Vi.pattern.bins_args()
-            _lib.check(lib.ox_assemble_first_au(Vi.degree, C.byref(self._cells), _lib.ptr(Vi.cell_dofs),
-                                                C.byref(self._adj_u), _lib.ptr(Vi.adj.adj_pos), Vi.adj.pw,
-                                                self._A.ref(), self._M.ref(), self._K.ref(),
-                                                self._UAB.rptr(), self._U1.rptr(), self._B0.rptr(), self._BFIRST.ptr(),
-                                                float(dt), float(nu), nb, bptr, bsl, bw, st,
-                                                self._B3.ptr() if want_au else None), "ox_assemble_first")
+        self._assemble_first_rows(dt, nu, want_au)
+        if self._viscosity_model is not None and self._stress_form == "full":
+            self.stress_transpose_assemble()
         self._A.version += 1
         if self._scalar_groups:  # A still is M/dt + C/2 + nu K/2 on EVERY row: the scalars' operators come from it
             self._A_pre_bc = True
@@ -492,18 +461,16 @@ class FractionalStep_AB_CN:
                                                           _lib.ptr(self._nut), -1.0, self._BFIRST.ptr(),
                                                           _lib.current_stream()), "ox_assemble_stress_transpose")
 
-    def _assemble_first_nut(self, dt, nu, want_au):
-        lib, st = self._lib, _lib.current_stream()
+    def _assemble_first_rows(self, dt, nu, want_au):
+        """The fused row kernel alone (``ox_assemble_first``), with the ``nut`` of a viscosity model where there is one."""
         Vi = self._Vi[0][0]
-        head = (Vi.degree, C.byref(self._cells), _lib.ptr(Vi.cell_dofs), C.byref(self._adj_u), _lib.ptr(Vi.adj.adj_pos),
-                Vi.adj.pw, self._A.ref(), self._M.ref(), self._K.ref(), self._UAB.rptr(), self._U1.rptr(), self._B0.rptr(),
-                self._BFIRST.ptr(), float(dt), float(nu))
-        tail = (st, self._B3.ptr() if want_au else None, _lib.ptr(self._nut))
-        if self._row_blocks and Vi.pattern.n_row_blocks > 0:
-            _lib.check(lib.ox_assemble_first_blocks_nut(*head, *Vi.pattern.blocks_args(), *tail),
-                       "ox_assemble_first_blocks_nut")
-        else:
-            _lib.check(lib.ox_assemble_first_au_nut(*head, *Vi.pattern.bins_args(), *tail), "ox_assemble_first_au_nut")
+        args = _lib.ox_first_args(self._UAB.rptr(), self._U1.rptr(), self._B0.rptr(), self._BFIRST.ptr(), float(dt), float(nu),
+                                  self._B3.ptr() if want_au else None, _lib.ptr(self._nut))
+        # row blocks: ONE launch over the slices in storage order (round 5): the rows of a cell meet in one L2 instead of
+        # being torn apart into the launches of up to ten width bins (options["assemble_row_blocks"]; bit-identical)
+        _lib.check(self._lib.ox_assemble_first(C.byref(self._cells), C.byref(Vi.assembly_info()), self._A.ref(), self._M.ref(),
+                                               self._K.ref(), C.byref(args), int(self._row_blocks and Vi.pattern.n_row_blocks > 0),
+                                               _lib.current_stream()), "ox_assemble_first")
 
     def eddy_viscosity(self) -> torch.Tensor:
         """``nut`` per cell of the last ``assemble_first``: a device tensor ``(num_cells,)`` in the MESH's cell order (the

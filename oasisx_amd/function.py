@@ -28,7 +28,7 @@ import torch
 from .fem import (DGSpace, FieldStorage, Function, FunctionSpace, VectorFunctionSpace, _simplex_rule, cell_geometry,
                   lagrange_basis, lagrange_basis_derivs)
 from .ksp import KSPSolver
-from .la import SellMatrix
+from .la import SellMatrix, assemble_matrix
 
 __all__ = ["Projector", "LumpedProject", "grad", "Expression"]
 
@@ -166,12 +166,7 @@ class Projector:
         cells = _lib.ox_cells(mesh.gdim, 0, int(self._geom.shape[0]), self._geom.data_ptr())
         # the mass matrix, assembled once (function.py:62-71)
         self._A = SellMatrix(space.pattern, symmetric=True, name="projector_mass")
-        adj = space.adj.struct()
-        nb, bptr, bsl, bw = space.pattern.bins_args()
-        _lib.check(lib.ox_assemble_matrix(0, space.degree, C.byref(cells), _lib.ptr(space.cell_dofs), C.byref(adj),
-                                          _lib.ptr(space.adj.adj_pos), space.adj.pw, self._A.ref(), nb, bptr, bsl, bw,
-                                          _lib.current_stream()), "ox_assemble_matrix")
-        self._A.version += 1
+        assemble_matrix(0, space, cells, self._A)
         dev = mesh.device
         if self._bcs:
             # assemble_matrix(lhs, bcs=bcs) (function.py:69-70): rows AND columns of the constrained dofs -> identity;

@@ -149,6 +149,14 @@ class SellMatrix:
         self.version += 1
 
 
+def assemble_matrix(kind: int, V, cells, Mat: SellMatrix, row_blocks: bool = False):
+    """``Mat`` = the mass (kind 0) or stiffness (kind 1) matrix of the space ``V`` over ``cells`` (``ox_cells``), one launch
+    per width bin or, with ``row_blocks``, one launch over the pattern's row blocks (``ox_assemble_matrix``)."""
+    _lib.check(_lib.load().ox_assemble_matrix(int(kind), C.byref(cells), C.byref(V.assembly_info()), Mat.ref(),
+                                              int(bool(row_blocks)), _lib.current_stream()), "ox_assemble_matrix")
+    Mat.version += 1
+
+
 class MultiSellMatrix:
     """Rectangular operator with ``gdim`` values per entry on one SELL-64 pattern: the reference's
     pre-assembled ``p*v.dx(i)*dx`` / ``p.dx(i)*v*dx`` / ``u.dx(i)*q*dx`` matrices for all i

@@ -20,7 +20,7 @@ everything downstream of ``nut`` -- the fused kernel, ``eddy_viscosity()``, :cla
 
 Per ``assemble_first``: one kernel writes ``nut_c`` from ``grad u_ab`` at the cell centroids (``ox_eddy_viscosity``,
 csrc/ox_viscosity.hip; :class:`CellViscosity` has nothing to evaluate), then the fused assembly kernel adds
-``nut_c K_c`` to the convection rows it forms anyway (``ox_assemble_first_*_nut``): no second pass over the pattern, no
+``nut_c K_c`` to the convection rows it forms anyway (``ox_assemble_first`` with ``ox_first_args.nut``): no second pass over the pattern, no
 second matrix.  ``Delta_c = |cell|^(1/gdim)``.
 """
 from __future__ import annotations

@@ -190,24 +190,17 @@ def test_pair_slot_stream_decodes_to_the_entries_and_spmv_is_bit_identical(dim, 
     entries (col, vdict[a]) and (col + 1, vdict[b]); in stored order they are the row's entries, zeros
     apart.  The mat-vec from the stream equals the entry-stream one bit for bit, for 1..3 columns and
     through the Krylov epilogues."""
-    import ctypes as C
-
     from oasisx_amd import _lib, fem, mesh as M
     from oasisx_amd.fem import cell_geometry
-    from oasisx_amd.la import SellMatrix
+    from oasisx_amd.la import SellMatrix, assemble_matrix
 
     lo, hi = [-1.0] * dim, [1.0] * dim
     mesh = M.create_box(None, [lo, hi], [N] * dim) if dim == 3 else M.create_rectangle(None, [lo, hi], [N] * dim)
     V = fem.FunctionSpace(mesh, deg)
     A = SellMatrix(V.pattern)
-    lib = _lib.load()
     geom = V.native.nmesh.geom if getattr(V, "native", None) is not None else cell_geometry(mesh, V.local_cells)
     cells = _lib.ox_cells(mesh.gdim, 0, int(geom.shape[0]), geom.data_ptr())
-    adj = V.adj.struct()
-    nb, bptr, bsl, bw = V.pattern.bins_args()
-    _lib.check(lib.ox_assemble_matrix(0, V.degree, C.byref(cells), _lib.ptr(V.cell_dofs), C.byref(adj), _lib.ptr(V.adj.adj_pos),
-                                      V.adj.pw, A.ref(), nb, bptr, bsl, bw, _lib.current_stream()), "ox_assemble_matrix")  # mass: SPD
-    A.version += 1
+    assemble_matrix(0, V, cells, A)  # mass: SPD
     assert A.freeze(pairs="always" if force else "auto")
     assert A.ps_code is not None
     P = V.pattern

@@ -123,7 +123,7 @@ def test_supplied_first_matvec_gives_the_same_iterates(hip, kind, single):
 
 
 def test_fused_assembly_returns_the_first_matvec_of_the_tentative_solve(hip):
-    """ox_assemble_first_au: (A @ u1) from the epilogue of the fused kernel equals A.mult(u1) bit for
+    """ox_assemble_first with a_u1: (A @ u1) from the epilogue of the fused kernel equals A.mult(u1) bit for
     bit (identity rows included), and the time step that uses it equals the one that does not."""
     from tests.helpers import KRYLOV, make_hip_problem
 

@@ -62,20 +62,14 @@ def test_p3_space_against_the_oracle_on_its_own_numbering(hip):
     u.interpolate(f)
     assert fem.assemble_l2_error_sq(u, f) < 1e-26
     # operators of the library (own numbering) against the oracle's (its numbering), matched through coordinates
-    import ctypes as C
-
     from oasisx_amd import _lib
-    from oasisx_amd.la import SellMatrix
+    from oasisx_amd.la import SellMatrix, assemble_matrix
 
-    lib = _lib.load()
     geom = V.native.nmesh.geom
     cs = _lib.ox_cells(2, 0, int(geom.shape[0]), geom.data_ptr())
-    adj = V.adj.struct()
-    nb, bptr, bsl, bw = V.pattern.bins_args()
     for kind, ref in ((0, F.mass_v()), (1, F.stiffness_v())):
         A = SellMatrix(V.pattern)
-        _lib.check(lib.ox_assemble_matrix(kind, 3, C.byref(cs), _lib.ptr(V.cell_dofs), C.byref(adj), _lib.ptr(V.adj.adj_pos),
-                                          V.adj.pw, A.ref(), nb, bptr, bsl, bw, _lib.current_stream()), "ox_assemble_matrix")
+        assemble_matrix(kind, V, cs, A)
         Ah = A.to_scipy()[perm][:, perm]
         assert Ah.nnz == ref.nnz and abs(Ah - ref).max() < 1e-13 * abs(ref).max()
 

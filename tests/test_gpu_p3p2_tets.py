@@ -48,10 +48,8 @@ def _twin(S, mesh, nu, dt, solver_options=None, low_memory=True):
 
 
 def test_p3_space_on_tetrahedra_against_the_oracle_on_its_own_numbering(hip):
-    import ctypes as C
-
     from oasisx_amd import _lib, fem
-    from oasisx_amd.la import SellMatrix
+    from oasisx_amd.la import SellMatrix, assemble_matrix
     from oracle import ipcs_oracle as O
     from oracle.cpu_baseline import match_by_coordinates
     from tests.helpers import tg_mesh
@@ -71,22 +69,12 @@ def test_p3_space_on_tetrahedra_against_the_oracle_on_its_own_numbering(hip):
     u = fem.Function(V)
     u.interpolate(f)
     assert fem.assemble_l2_error_sq(u, f) < 1e-25
-    lib = _lib.load()
     geom = V.native.nmesh.geom
     cs = _lib.ox_cells(3, 0, int(geom.shape[0]), geom.data_ptr())
-    adj = V.adj.struct()
-    nb, bptr, bsl, bw = V.pattern.bins_args()
     for kind, ref in ((0, F.mass_v()), (1, F.stiffness_v())):
         for blocks in (False, True):
             A = SellMatrix(V.pattern)
-            if blocks:
-                nblk, bp, ent = V.pattern.blocks_args()
-                _lib.check(lib.ox_assemble_matrix_blocks(kind, 3, C.byref(cs), _lib.ptr(V.cell_dofs), C.byref(adj),
-                                                         _lib.ptr(V.adj.adj_pos), V.adj.pw, A.ref(), nblk, bp, ent,
-                                                         _lib.current_stream()), "ox_assemble_matrix_blocks")
-            else:
-                _lib.check(lib.ox_assemble_matrix(kind, 3, C.byref(cs), _lib.ptr(V.cell_dofs), C.byref(adj), _lib.ptr(V.adj.adj_pos),
-                                                  V.adj.pw, A.ref(), nb, bptr, bsl, bw, _lib.current_stream()), "ox_assemble_matrix")
+            assemble_matrix(kind, V, cs, A, row_blocks=blocks)
             Ah = A.to_scipy()[perm][:, perm]
             assert Ah.nnz == ref.nnz and abs(Ah - ref).max() < 1e-12 * abs(ref).max(), (kind, blocks)
     # entity closures: the dofs on the boundary faces found topologically = those found geometrically

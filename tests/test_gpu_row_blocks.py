@@ -1,4 +1,4 @@
-"""GPU: the one-launch row-block form of the row kernels (``ox_assemble_first_blocks`` / ``ox_assemble_matrix_blocks``,
+"""GPU: the one-launch row-block form of the row kernels (``ox_assemble_first`` / ``ox_assemble_matrix`` with ``row_blocks = 1``,
 round 5; reference fracstep.py:373-380,432-469 -> ``assemble_matrix`` + ``Mat`` passes) against the width-bin launches:
 the same per-slice arithmetic in the same order, so every matrix value, b_first and the ``A u1`` by-product are
 BIT-identical -- box meshes (three widths), Delaunay meshes (dozens), 2-D, P1, P3, mesh-partitioned row spaces; and the

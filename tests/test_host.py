@@ -30,6 +30,67 @@ def test_library_exports_every_declared_symbol():
     assert L.ox_version() >= 100 and L.ox_sell_kv() == fem.KV
 
 
+def test_row_assembly_has_two_entry_points():
+    """Row assembly is ``ox_assemble_matrix`` and ``ox_assemble_first`` alone: the launch form is an argument and ``a_u1`` /
+    ``nut`` are optional fields of ``ox_first_args``, so none of the per-form, per-option names is declared, bound or
+    exported any more."""
+    from oasisx_amd import _lib
+
+    forms = ("_au", "_blocks", "_au_nut", "_blocks_nut")  # one name per launch form and option, before
+    removed = ["ox_assemble_matrix" + forms[1]] + ["ox_assemble_first" + f for f in forms]
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "oasisx_hip.h")).read(), flags=re.S)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in removed:
+        assert not re.search(r"\b%s\b" % name, hdr) and name not in _lib.SIGNATURES and not hasattr(lib, name), name
+    for name, arity in (("ox_assemble_matrix", 6), ("ox_assemble_first", 8)):
+        decl = re.search(r"\bint %s\s*\(([^)]*)\)" % name, hdr)
+        assert decl and len(decl.group(1).split(",")) == arity, name
+        assert len(_lib.SIGNATURES[name][1]) == arity and hasattr(lib, name), name
+    assert [f for f, _ in _lib.ox_first_args._fields_] == ["uab", "u1", "b0", "b_first", "dt", "nu", "a_u1", "nut"]
+
+
+def test_row_assembly_checks_its_arguments_before_any_device_call():
+    """``ox_assemble_matrix`` / ``ox_assemble_first`` refuse a NULL space, NULL args, dt = 0, an unknown kind and
+    ``row_blocks = 1`` on a pattern without row blocks with a message that names the problem -- on the host, before the
+    first HIP call (this test runs without a device)."""
+    import ctypes as C
+
+    from oasisx_amd import _lib
+    from oasisx_amd.la import SellMatrix
+
+    lib = _lib.load()
+    m = M.create_unit_square(None, 3, 3, device="cpu")
+    V = fem.FunctionSpace(m, 1, window=64)
+    geom = fem.cell_geometry(m, V.local_cells)
+    cells = _lib.ox_cells(2, 0, int(geom.shape[0]), geom.data_ptr())
+    A, Mm, K = (SellMatrix(V.pattern) for _ in range(3))
+    space = V.assembly_info()
+    assert space.pattern.n_row_blocks > 0 and space.pattern.n_bins > 0
+    no_blocks = _lib.ox_space_info.from_buffer_copy(space)
+    no_blocks.pattern.n_row_blocks = 0
+    v = torch.zeros(V.num_dofs, 2, dtype=torch.float64)
+
+    def first_args(dt=0.01):
+        return _lib.ox_first_args(v.data_ptr(), v.data_ptr(), v.data_ptr(), v.data_ptr(), dt, 0.01, None, None)
+
+    def refused(rc, *words):
+        msg = lib.ox_last_error().decode()
+        assert rc != 0 and all(w in msg for w in words), (rc, msg)
+
+    cs, sp, st = C.byref(cells), C.byref(space), None
+    refused(lib.ox_assemble_matrix(0, cs, None, A.ref(), 0, st), "ox_assemble_matrix", "null argument")
+    refused(lib.ox_assemble_matrix(2, cs, sp, A.ref(), 0, st), "ox_assemble_matrix", "kind=2")
+    refused(lib.ox_assemble_matrix(0, cs, C.byref(no_blocks), A.ref(), 1, st), "ox_assemble_matrix", "row_blocks=1",
+            "n_row_blocks=0")
+    fa = first_args()
+    refused(lib.ox_assemble_first(cs, None, A.ref(), Mm.ref(), K.ref(), C.byref(fa), 0, st), "ox_assemble_first", "null argument")
+    refused(lib.ox_assemble_first(cs, sp, A.ref(), Mm.ref(), K.ref(), None, 0, st), "ox_assemble_first", "null argument")
+    f0 = first_args(dt=0.0)
+    refused(lib.ox_assemble_first(cs, sp, A.ref(), Mm.ref(), K.ref(), C.byref(f0), 0, st), "ox_assemble_first", "dt=0")
+    refused(lib.ox_assemble_first(cs, C.byref(no_blocks), A.ref(), Mm.ref(), K.ref(), C.byref(fa), 1, st), "ox_assemble_first",
+            "row_blocks=1", "n_row_blocks=0")
+
+
 def test_product_fails_loudly_without_gpu():
     """No CPU fallback: a compute call on a machine without a GPU raises, it does not emulate."""
     if torch.cuda.is_available():

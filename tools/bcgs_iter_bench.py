@@ -2,25 +2,21 @@
 (what velocity_tentative_solve runs): a fixed number of iterations (rtol 0), wall time of the solve / iterations; the
 matrix is M/dt-like plus a non-symmetric perturbation.  With OX_LIB_PATH a tuning build of the library is timed.
     python tools/bcgs_iter_bench.py [N] [iterations]"""
-import ctypes as C, os, sys, time
+import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from oasisx_amd import fem, _lib, mesh as M
 from oasisx_amd.fem import FieldStorage
 from oasisx_amd.ksp import KSPSolver
-from oasisx_amd.la import SellMatrix
+from oasisx_amd.la import SellMatrix, assemble_matrix
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 ITS = int(sys.argv[2]) if len(sys.argv) > 2 else 12
 mesh = M.create_box(None, [[-1., -1., -1.], [1., 1., 1.]], [N, N, N])
 V = fem.FunctionSpace(mesh, 2)
 A = SellMatrix(V.pattern)
-lib = _lib.load()
 geom = V.native.nmesh.geom
 cells = _lib.ox_cells(3, 0, int(geom.shape[0]), geom.data_ptr())
-adj = V.adj.struct()
-nb, bptr, bsl, bw = V.pattern.bins_args()
-_lib.check(lib.ox_assemble_matrix(0, 2, C.byref(cells), _lib.ptr(V.cell_dofs), C.byref(adj), _lib.ptr(V.adj.adj_pos), V.adj.pw,
-                                  A.ref(), nb, bptr, bsl, bw, _lib.current_stream()), "ox_assemble_matrix")
+assemble_matrix(0, V, cells, A)
 A.vals.mul_(1.0 + 0.05 * torch.sin(torch.arange(A.vals.numel(), device="cuda", dtype=torch.float64)))
 A.version += 1
 n = V.num_dofs

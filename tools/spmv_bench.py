@@ -6,7 +6,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from oasisx_amd import fem, _lib, mesh as M
-from oasisx_amd.la import SellMatrix
+from oasisx_amd.la import SellMatrix, assemble_matrix
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 which = sys.argv[2] if len(sys.argv) > 2 else "p"
 mesh = M.create_box(None, [[-1.,-1.,-1.],[1.,1.,1.]], [N,N,N])
@@ -17,17 +17,10 @@ if os.environ.get("WIN") == "1":  # LDS-window stream of the pattern (variant bi
 A = SellMatrix(V.pattern); A.vals.uniform_(0.5, 1.5)
 real = os.environ.get("REAL", "")  # "stiff" / "mass": the mesh's real stiffness / mass matrix, frozen
 if real:
-    import ctypes as C
     from oasisx_amd.fem import cell_geometry
-    lib0 = _lib.load()
     geom = V.native.nmesh.geom if getattr(V, "native", None) is not None else cell_geometry(mesh, V.local_cells)
     cells = _lib.ox_cells(mesh.gdim, 0, int(geom.shape[0]), geom.data_ptr())
-    adj = V.adj.struct()
-    nb, bptr, bsl, bw = V.pattern.bins_args()
-    _lib.check(lib0.ox_assemble_matrix({"mass": 0, "stiff": 1}[real], V.degree, C.byref(cells), _lib.ptr(V.cell_dofs),
-                                       C.byref(adj), _lib.ptr(V.adj.adj_pos), V.adj.pw, A.ref(), nb, bptr, bsl, bw,
-                                       _lib.current_stream()), "ox_assemble_matrix")
-    A.version += 1
+    assemble_matrix({"mass": 0, "stiff": 1}[real], V, cells, A)
     print("value dictionary built:", A.freeze(pairs=os.environ.get("PAIRS", "auto")), "entries", A._struct.n_dict)
 npal = int(os.environ.get("PALETTE", "0"))  # > 0: values drawn from that many distinct numbers (mass /
 if npal:                                   # stiffness matrices on box meshes have 49 / 14)

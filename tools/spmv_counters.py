@@ -5,27 +5,21 @@ the bench workload once and runs, a few repetitions each,
 HIP-event times are printed beside (python tools/spmv_counters.py [N])."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ctypes as C
 import torch
 from oasisx_amd import fem, _lib, mesh as M
-from oasisx_amd.la import SellMatrix
+from oasisx_amd.la import SellMatrix, assemble_matrix
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 reps = int(os.environ.get("REPS", "3"))
 mesh = M.create_box(None, [[-1., -1., -1.], [1., 1., 1.]], [N, N, N])
 V = fem.FunctionSpace(mesh, 2)
 P = V.pattern
-lib = _lib.load()
 A = SellMatrix(P)
 A.vals.uniform_(0.5, 1.5)
 Mm = SellMatrix(P)
 geom = V.native.nmesh.geom
 cells = _lib.ox_cells(mesh.gdim, 0, int(geom.shape[0]), geom.data_ptr())
-adj = V.adj.struct()
-nb, bptr, bsl, bw = P.bins_args()
-_lib.check(lib.ox_assemble_matrix(0, V.degree, C.byref(cells), _lib.ptr(V.cell_dofs), C.byref(adj), _lib.ptr(V.adj.adj_pos),
-                                  V.adj.pw, Mm.ref(), nb, bptr, bsl, bw, _lib.current_stream()), "ox_assemble_matrix")
-Mm.version += 1
+assemble_matrix(0, V, cells, Mm)
 print("mass matrix dictionary:", Mm.freeze(), Mm._struct.n_dict, flush=True)
 for nc in (3, 1):
     x = (torch.sin(torch.arange(P.n_cols * nc, device="cuda", dtype=torch.float64) * 1e-3) + 1).reshape(P.n_cols, nc).contiguous()

@@ -2,7 +2,6 @@
 256 MB Infinity Cache) time 64 us in one run and 74 us in the next?  One process: the same matrix
 is re-created at different device addresses (a dummy allocation of varying size is made first and kept) and timed
 (a) back to back, (b) interleaved with a pass over 140 MB of vectors, as inside a CG iteration."""
-import ctypes as C
 import os
 import sys
 
@@ -11,16 +10,13 @@ import torch
 
 from oasisx_amd import _lib, fem
 from oasisx_amd import mesh as M
-from oasisx_amd.la import SellMatrix
+from oasisx_amd.la import SellMatrix, assemble_matrix
 
-lib = _lib.load()
 mesh = M.create_box(None, [[-1., -1., -1.], [1., 1., 1.]], [128, 128, 128])
 V = fem.FunctionSpace(mesh, 1)
 P = V.pattern
 geom = V.native.nmesh.geom
 cells = _lib.ox_cells(3, 0, int(geom.shape[0]), geom.data_ptr())
-adj = V.adj.struct()
-nb, bptr, bsl, bw = P.bins_args()
 x = (torch.sin(torch.arange(P.n_cols, device="cuda", dtype=torch.float64) * 1e-3) + 1).reshape(-1, 1).contiguous()
 y = torch.zeros_like(x)
 vec = torch.zeros(int(140e6 / 8), dtype=torch.float64, device="cuda")
@@ -29,9 +25,7 @@ for trial, pad_mb in enumerate((0, 37, 101, 256, 300, 517, 1024, 2048)):
     if pad_mb:
         keep.append(torch.empty(pad_mb << 20, dtype=torch.uint8, device="cuda"))
     A = SellMatrix(P, symmetric=True)  # a fresh value array at a new address
-    _lib.check(lib.ox_assemble_matrix(1, 1, C.byref(cells), _lib.ptr(V.cell_dofs), C.byref(adj), _lib.ptr(V.adj.adj_pos), V.adj.pw,
-                                      A.ref(), nb, bptr, bsl, bw, _lib.current_stream()), "ox_assemble_matrix")
-    A.version += 1
+    assemble_matrix(1, V, cells, A)
     out = []
     for interleave in (False, True):
         for _ in range(10):

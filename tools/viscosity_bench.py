@@ -141,8 +141,8 @@ def main():
     variants = {
         "assemble_first_constant_nu": lambda: S0.assemble_first(dt, nu),
         "assemble_first_with_model": lambda: S1.assemble_first(dt, nu),
-        "fused_nut_kernel_alone": lambda: S1._assemble_first_nut(dt, nu, want_au),
-        "stiffness_pass": lambda: S1._assemble_matrix(1, Vi, S1._adj_u, scratch),
+        "fused_nut_kernel_alone": lambda: S1._assemble_first_rows(dt, nu, want_au),
+        "stiffness_pass": lambda: S1._assemble_matrix(1, Vi, scratch),
         "nut_wale": lambda: nut_kernel(1, 0.325),
         "nut_smagorinsky": lambda: nut_kernel(0, 0.1677),
     }

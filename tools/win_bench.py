@@ -4,7 +4,6 @@ right-hand sides, line order (OX_BRICK=0) and brick order of the P2 numbering.  
 every pair; times are HIP-event medians, interleaved in one process.
 
     python tools/win_bench.py [N] [delaunay|box] [refine]"""
-import ctypes as C
 import os
 import statistics
 import sys
@@ -15,12 +14,11 @@ import torch
 
 from oasisx_amd import _lib, fem
 from oasisx_amd import mesh as M
-from oasisx_amd.la import SellMatrix
+from oasisx_amd.la import SellMatrix, assemble_matrix
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 kind = sys.argv[2] if len(sys.argv) > 2 else "box"
 refine = int(sys.argv[3]) if len(sys.argv) > 3 else 0
-lib = _lib.load()
 REPS = int(os.environ.get("REPS", "30"))
 ROUNDS = int(os.environ.get("ROUNDS", "5"))
 WINDOW = int(os.environ.get("WINDOW", "4096"))
@@ -53,11 +51,7 @@ for brick in ([int(b) for b in os.environ.get("BRICKS", "1,0").split(",")] if ki
     Mm = SellMatrix(P, symmetric=True, name="M")
     geom = V.native.nmesh.geom
     cells = _lib.ox_cells(mesh.gdim, 0, int(geom.shape[0]), geom.data_ptr())
-    adj = V.adj.struct()
-    nb, bptr, bsl, bw = P.bins_args()
-    _lib.check(lib.ox_assemble_matrix(0, 2, C.byref(cells), _lib.ptr(V.cell_dofs), C.byref(adj), _lib.ptr(V.adj.adj_pos),
-                                      V.adj.pw, Mm.ref(), nb, bptr, bsl, bw, _lib.current_stream()), "ox_assemble_matrix")
-    Mm.version += 1
+    assemble_matrix(0, V, cells, Mm)
     Am = SellMatrix(P, name="A")
     Am.vals.copy_(Mm.vals * (1.0 + 0.25 * torch.sin(torch.arange(P.size, device="cuda", dtype=torch.float64))))
     Am.version += 1
