@@ -728,6 +728,35 @@ int ox_wall_stress(int u_degree, int p_degree, const ox_cells *cells, const int3
 int ox_wall_forces(int gdim, int n_tags, const int64_t *tag_ptr, const double *ft, double rho, double *ring,
                    int64_t capacity, int64_t slot, void *stream);
 
+/* ---- Outlet models on exterior facets: flow rates, resistance / RCR Windkessel, backflow (ox_outlet.hip, DESIGN.md
+ * section 17).  Facets and records as for ox_wall_stress: sorted by tag, facet_rec[2 i] the kernel position of the cell,
+ * facet_rec[2 i + 1] the opposite local vertex (a record outside the tables leaves NaN in flux[i]).
+ *   flux[i] = |f| n . ubar,  ubar the facet mean of u (exact: compile-time facet means of the P1 / P2 / P3 basis), n outward:
+ * a positive flux leaves the domain.  u interleaved [n_u][gdim].  One lane per facet. */
+int ox_outlet_flux(int u_degree, const ox_cells *cells, const int32_t *cell_vdofs, int64_t n_facets,
+                   const int32_t *facet_rec, const double *u, double *flux, void *stream);
+/* One block per tag k: Q = sum_{tag_ptr[k] <= i < tag_ptr[k+1]} flux[i] (lane-strided partial sums, a fixed tree) goes to
+ * ring[slot][k] (device [capacity][n_tags]).  params == NULL: nothing else.  Otherwise params: device [n_tags][8] =
+ * (kind, Rp, C, Rd, p_distal, rho, -, -), kind 0 none / 1 resistance / 2 RCR; state: device [n_tags], the pressure Pc of
+ * the capacitor; kind 2 advances it by backward Euler with this Q,
+ *   Pc <- (Pc + (dt/C)(Q + p_distal/Rd)) / (1 + dt/(Rd C))       (Rd = 0: Pc <- p_distal),
+ * P = Pc + Rp Q, hist[slot][k] = (Q, P, Pc) (device [capacity][n_tags][3]) and h[k * h_stride + dofs[j]] = P / rho for
+ * dof_ptr[k] <= j < dof_ptr[k+1]; no other entry of h is written. */
+int ox_outlet_update(int n_tags, const int64_t *tag_ptr, const double *flux, double *ring, int64_t capacity, int64_t slot,
+                     const double *params, double dt, double *state, double *hist, const int64_t *dof_ptr,
+                     const int32_t *dofs, double *h, int64_t h_stride, void *stream);
+/* Backflow stabilisation -beta int_Gamma min(u_ab . n, 0) u . v ds, Crank-Nicolson: for row rows[i], over its pairs
+ * row_ptr[i] <= k < row_ptr[i+1] -- facet pair_facet[k] (an index into facet_rec / beta, pairs in ascending facet id) on
+ * which the row is dof number pair_loc[k] of the facet's dofs (the cell's dofs that live on the facet, ascending) -- and
+ * the facet's dofs s:   e = (beta/2) |f| sum_q w_q max(-u_ab(x_q) . n, 0) phi_r(x_q) phi_s(x_q)   (the facet rule: 2 / 4 /
+ * 5 Gauss-Legendre points on an edge, that many squared collapsed Gauss-Jacobi points on a triangle, for P1 / P2 / P3),
+ *   a_vals[pair_off[k * nfd + s]] += e  (a negative slot is skipped),   b_first[rows[i]][:] -= e u1[dof_s][:].
+ * One lane per row, which owns that row of the matrix and of b_first: no atomics, a fixed order of sums. */
+int ox_outlet_backflow(int u_degree, const ox_cells *cells, const int32_t *cell_vdofs, int64_t n_rows, const int32_t *rows,
+                       const int64_t *row_ptr, const int32_t *pair_facet, const int32_t *pair_loc, const int64_t *pair_off,
+                       int64_t n_facets, const int32_t *facet_rec, const double *beta, const double *uab, const double *u1,
+                       double *a_vals, int64_t a_size, double *b_first, void *stream);
+
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */
 int ox_comm_create(const char *id128, int rank, int nranks, void **comm_out); /* ncclCommInitRank */

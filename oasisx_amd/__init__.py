@@ -11,6 +11,7 @@ from .fracstep import FractionalStep_AB_CN
 from .function import Projector
 from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
+from .outlet import FlowRate, Resistance, Windkessel
 from .scalar import ScalarTransport
 from .viscosity import CarreauYasuda, CellViscosity, Cross, PowerLaw, Smagorinsky, Wale
 from .wall import WallStress
@@ -33,4 +34,7 @@ __all__ = [
     "Cross",
     "PowerLaw",
     "WallStress",
+    "FlowRate",
+    "Resistance",
+    "Windkessel",
 ]

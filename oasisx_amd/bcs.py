@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from .fem import Constant, FunctionSpace, Vector, locate_dofs_geometrical, locate_dofs_topological
+from .outlet import OutletModel
 
 __all__ = ["DirichletBC", "PressureBC", "LocatorMethod"]
 
@@ -157,11 +158,21 @@ class PressureBC:
 
     Device form: the term is linear in the nodal values of h, so ``create_bcs`` builds, once,
     one small SELL-64 operator per component on the rows (velocity dofs) of the cells behind the
-    facets; per step the term is d tiny SpMVs plus a scatter-add -- no atomics."""
+    facets; per step the term is d tiny SpMVs plus a scatter-add -- no atomics.
 
-    def __init__(self, value, marker):
+    ``value`` may also be a lumped outlet model, :class:`oasisx_amd.Resistance` or :class:`oasisx_amd.Windkessel`: the solver
+    then advances it once per ``assemble_first`` and a kernel writes ``h`` (:mod:`oasisx_amd.outlet`).  ``backflow = beta``
+    in (0, 1] adds the backflow stabilisation ``-beta int_Gamma min(u_ab . n, 0) u . v ds`` on these facets (0.5 cancels the
+    incoming kinetic-energy flux of the convective form); 0, the default, adds nothing."""
+
+    def __init__(self, value, marker, backflow: float = 0.0):
         self._subdomain_data, self._subdomain_id = marker
         self._value = value
+        self._model = value if isinstance(value, OutletModel) else None
+        beta = float(backflow)
+        if not 0.0 <= beta <= 1.0:  # (NaN too)
+            raise ValueError(f"PressureBC: backflow = {backflow}: a coefficient in [0, 1] is expected")
+        self.backflow = beta
 
     def create_bcs(self, V, Q):
         import itertools
@@ -281,8 +292,13 @@ class PressureBC:
         self.update_bc(force=True)
 
     def update_bc(self, force: bool = False):
-        """Re-evaluate h (reference bcs.py:255-260 re-interpolates a callable value)."""
-        if callable(self._value):
+        """Re-evaluate h (reference bcs.py:255-260 re-interpolates a callable value).  The h of an outlet model belongs to
+        the solver's ``assemble_first``, which advances the model and writes it: nothing happens here (``force``, at
+        set-up: the model's initial value)."""
+        if self._model is not None:
+            if force:
+                self._h[self._dofs_dev.to(torch.int64)] = self._model.initial_h()
+        elif callable(self._value):
             if hasattr(self, "_u") or force:
                 g = np.asarray(self._value(self._xq), dtype=np.float64).reshape(-1)
                 self._h[self._dofs_dev.to(torch.int64)] = torch.from_numpy(np.ascontiguousarray(g)).to(self._h.device)
@@ -292,7 +308,7 @@ class PressureBC:
 
     def add_surface_terms(self, B):
         """B[:, i] += int_Gamma h n_i dv/dx_i ds for every component (fracstep.py:461-465)."""
-        if not callable(self._value):
+        if not callable(self._value) and self._model is None:
             self.update_bc()  # Constants are tracked by reference
         lib = _lib.load()
         st = _lib.current_stream()

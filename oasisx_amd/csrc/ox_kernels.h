@@ -140,6 +140,9 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_STRESS_TRANSPOSE 161 // ox_assemble_stress_transpose
 #define OX_TAG_WALL_STRESS 170     // ox_wall_stress (key = facets)
 #define OX_TAG_WALL_FORCES 171     // ox_wall_forces (key = tags)
+#define OX_TAG_OUTLET_FLUX 180     // ox_outlet_flux (key = facets)
+#define OX_TAG_OUTLET_UPDATE 181   // ox_outlet_update (key = tags)
+#define OX_TAG_OUTLET_BACKFLOW 182 // ox_outlet_backflow (key = rows)
 extern bool ox_prof_on;
 void ox_prof_start(int tag, hipStream_t st, long long key = 0);
 void ox_prof_stop(hipStream_t st);

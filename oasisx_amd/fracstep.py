@@ -125,6 +125,12 @@ class FractionalStep_AB_CN:
             raise ValueError('stress_form="full" without a viscosity_model: with a constant viscosity the transposed term '
                              "div(nu grad u^T) = nu grad(div u) belongs to the pressure; there is nothing to add")
         self._stress_form = stress_form
+        # outlet models and backflow stabilisation of the pressure boundaries (outlet.py): one GPU
+        with_model = [b for b in bcs_p if getattr(b, "_model", None) is not None]
+        with_backflow = [b for b in bcs_p if getattr(b, "backflow", 0.0) > 0.0]
+        if (with_model or with_backflow) and getattr(getattr(mesh, "comm", None), "size", 1) > 1:
+            raise NotImplementedError("a PressureBC with an outlet model or backflow > 0 on a mesh-partitioned solver "
+                                      "(comm.size > 1): the facet sums and the backflow pass are built for one GPU")
         if viscosity_model is not None:  # the scope guards need neither the library nor a GPU
             from .viscosity import check_model
 
@@ -258,6 +264,14 @@ class FractionalStep_AB_CN:
 
         self._compile_and_allocate_forms()
         self._preassemble()
+        self._outlet_models = self._outlet_backflow = None
+        if with_model or with_backflow:
+            from .outlet import Backflow, OutletGroup
+
+            if with_model:
+                self._outlet_models = OutletGroup(self, with_model)
+            if with_backflow:
+                self._outlet_backflow = Backflow(self, with_backflow)
         self._nut = None
         if viscosity_model is not None:  # nut per cell, in the kernels' cell order
             self._nut = torch.zeros(int(self._geom.shape[0]), dtype=torch.float64, device=dev)
@@ -413,6 +427,8 @@ class FractionalStep_AB_CN:
         self._AU1_valid = False
         want_au = bool(self._solver_u._options.get("ksp_initial_guess_nonzero", False)) and \
             str(self._solver_u._options.get("ksp_type", "")).lower() != "preonly"
+        if self._outlet_backflow is not None:  # A changes after the fused kernel: its A u1 by-product is not asked for
+            want_au = False
         if self._viscosity_model is not None:
             base = getattr(self._viscosity_model, "base_viscosity", None)
             if base is not None and float(nu) != base:
@@ -430,15 +446,37 @@ class FractionalStep_AB_CN:
                 self.scalar_assemble(dt, nu)
             finally:
                 self._A_pre_bc = False
+        if self._outlet_models is not None:  # Q of u1, the models' Pc and h: once per assemble_first
+            self.outlet_assemble(dt)
         # outlet terms int h n_i dv/dx_i ds (:445-446, :461-465)
         for bcp in self._bcs_p:
             bcp.update_bc()
             bcp.add_surface_terms(self._BFIRST)
+        if self._outlet_backflow is not None:  # before the identity rows: Dirichlet rows win on rim dofs
+            self.backflow_assemble()
         # NOTE (reference :470): rows of the FIRST component's BCs only
         for bcu in self._bcs_u[0]:  # identity rows; (A @ u1)[row] = u1[row] there, in the same launch
             self._A.zero_rows(bcu._rows_dev, 1.0, self._B3.ptr() if want_au else None,
                               self._U1.rptr() if want_au else None, self._gdim)
         self._AU1_valid = want_au
+
+    @_phase
+    def outlet_assemble(self, dt: float):
+        """The lumped outlet models of the pressure boundaries: flow rates of ``u1`` through their facets
+        (``ox_outlet_flux``), then ``Pc``, the history and ``h = P / rho`` on the outlets' pressure dofs
+        (``ox_outlet_update``).  Advances every model by ``dt``: ``assemble_first`` calls it once."""
+        if self._outlet_models is None:
+            raise RuntimeError("outlet_assemble: no PressureBC of the solver has an outlet model")
+        self._outlet_models.advance(dt)
+
+    @_phase
+    def backflow_assemble(self):
+        """``A += (beta/2) B``, ``b_first -= (beta/2) B u1`` on the facets of the pressure boundaries with ``backflow > 0``
+        (``ox_outlet_backflow``), with the ``u_ab`` block ``assemble_first`` has just formed; runs inside
+        ``assemble_first``, before the velocity's identity rows."""
+        if self._outlet_backflow is None:
+            raise RuntimeError("backflow_assemble: no PressureBC of the solver has backflow > 0")
+        self._outlet_backflow.add()
 
     @_phase
     def viscosity_assemble(self):

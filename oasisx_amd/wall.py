@@ -27,26 +27,26 @@ import torch
 
 from . import _lib
 
-__all__ = ["WallStress", "facet_table"]
+__all__ = ["WallStress", "facet_table", "select_facets", "FacetSet"]
 
 
-def facet_table(mesh, facets):
+def facet_table(mesh, facets, who: str = "WallStress", what: str = "wall stresses"):
     """(cell, opposite local vertex) of exterior facets: mesh cell ids and local vertex indices, in the order of
-    ``facets``.  A facet that two cells share (or no cell has) raises ``ValueError``."""
+    ``facets``.  A facet that two cells share (or no cell has) raises ``ValueError`` (in the name of ``who``)."""
     import itertools
 
     d = mesh.gdim
     facets = np.asarray(facets, dtype=np.int64).reshape(-1)
     _, cf = mesh._entities(d - 1)
     if facets.size and (facets.min() < 0 or facets.max() > cf.max()):
-        raise ValueError("WallStress: facet ids are indices of the mesh's facets")
+        raise ValueError(f"{who}: facet ids are indices of the mesh's facets")
     if np.unique(facets).shape[0] != facets.shape[0]:
-        raise ValueError("WallStress: a facet is listed twice")
+        raise ValueError(f"{who}: a facet is listed twice")
     counts = np.bincount(cf.ravel(), minlength=int(cf.max()) + 1)
     interior = facets[counts[facets] != 1]
     if interior.size:
-        raise ValueError(f"WallStress: {interior.size} of the facets are interior facets (the first: {int(interior[0])}); "
-                         "wall stresses are evaluated on exterior facets")
+        raise ValueError(f"{who}: {interior.size} of the facets are interior facets (the first: {int(interior[0])}); "
+                         f"{what} are evaluated on exterior facets")
     combos = list(itertools.combinations(range(d + 1), d))
     opp_of_combo = np.array([[a for a in range(d + 1) if a not in c][0] for c in combos])
     fcell, fslot = np.nonzero(np.isin(cf, facets))
@@ -55,6 +55,64 @@ def facet_table(mesh, facets):
     pos = np.searchsorted(fid[order], facets)
     sel = order[pos]
     return fcell[sel], opp_of_combo[fslot[sel]]
+
+
+def select_facets(mesh, facets, who: str = "WallStress"):
+    """(facet ids, tag index per facet, tag values) of a facet selection -- ``None``: all exterior facets, one tag 0;
+    ``(meshtags, id | ids)``: one tag per id; an array of facet ids: one tag 0 -- ordered by tag, then by facet id."""
+    d = mesh.gdim
+    if facets is None:
+        ids = np.asarray(mesh.exterior_facets(), dtype=np.int64)
+        tag_of, tags = np.zeros(ids.shape[0], dtype=np.int64), np.array([0], dtype=np.int64)
+    elif isinstance(facets, tuple) and len(facets) == 2 and hasattr(facets[0], "find"):
+        mt, want = facets
+        if mt.dim != d - 1:
+            raise ValueError(f"{who}: the meshtags are of dimension {mt.dim}, facets have {d - 1}")
+        tags = np.atleast_1d(np.asarray(want, dtype=np.int64))
+        if np.unique(tags).shape[0] != tags.shape[0]:
+            raise ValueError(f"{who}: a tag is listed twice")
+        parts = [np.asarray(mt.find(np.int32(g)), dtype=np.int64) for g in tags]
+        ids = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+        tag_of = np.concatenate([np.full(p.shape[0], k, dtype=np.int64) for k, p in enumerate(parts)])
+    else:
+        ids = np.asarray(facets.cpu().numpy() if torch.is_tensor(facets) else facets, dtype=np.int64).reshape(-1)
+        tag_of, tags = np.zeros(ids.shape[0], dtype=np.int64), np.array([0], dtype=np.int64)
+    order = np.lexsort((ids, tag_of))  # by tag, then by facet id
+    return ids[order], tag_of[order], tags
+
+
+class FacetSet:
+    """Exterior facets of a solver's mesh, given sorted by tag: what the facet kernels read (``rec``: (kernel cell, local
+    facet) per facet, ``tag_ptr``: the tags' segments; device tensors) and the host geometry from the same records
+    (``normals`` outward, ``areas``, ``midpoints``).  Shared by ``WallStress`` and :mod:`oasisx_amd.outlet`."""
+
+    def __init__(self, solver, ids, tag_of, n_tags, who: str = "WallStress", what: str = "wall stresses"):
+        mesh = solver._mesh
+        d = mesh.gdim
+        fcell, fopp = facet_table(mesh, ids, who, what)
+        kpos = solver._Vi[0][0].kernel_cell_index(fcell)
+        if (kpos < 0).any():
+            raise ValueError(f"{who}: a facet's cell is not among the cells of the solver's spaces")
+        dev = mesh.device
+        nf = int(ids.shape[0])
+        self.facets, self.cells, self.local_facets, self.kpos = ids, fcell, fopp, kpos
+        self.n_facets, self.n_tags = nf, int(n_tags)
+        # geometry on the host, from the records the kernel reads
+        geom = solver._geom[torch.from_numpy(kpos).to(dev)].cpu().numpy()  # (nf, gs)
+        G = geom[:, : d * d].reshape(-1, d, d)
+        G = np.concatenate([-G.sum(axis=1, keepdims=True), G], axis=1)
+        Ga = G[np.arange(nf), fopp]
+        ga = np.linalg.norm(Ga, axis=1)
+        self.normals = -Ga / ga[:, None]
+        self.areas = geom[:, d * d] * ga * (0.5 if d == 3 else 1.0)
+        fv, _ = mesh._entities(d - 1)
+        self.midpoints = mesh.coords.cpu().numpy()[fv[ids]].mean(axis=1)
+        # device tables
+        rec = np.stack([kpos, fopp], axis=1).astype(np.int32)
+        self.rec = torch.from_numpy(np.ascontiguousarray(rec)).to(dev)
+        ptr = np.zeros(self.n_tags + 1, dtype=np.int64)
+        ptr[1:] = np.cumsum(np.bincount(tag_of, minlength=self.n_tags))
+        self.tag_ptr = torch.from_numpy(ptr).to(dev)
 
 
 class WallStress:
@@ -81,54 +139,19 @@ class WallStress:
         if int(capacity) < 1:
             raise ValueError(f"WallStress: capacity = {capacity}")
         d = mesh.gdim
-        if facets is None:
-            ids = np.asarray(mesh.exterior_facets(), dtype=np.int64)
-            tag_of, tags = np.zeros(ids.shape[0], dtype=np.int64), np.array([0], dtype=np.int64)
-        elif isinstance(facets, tuple) and len(facets) == 2 and hasattr(facets[0], "find"):
-            mt, want = facets
-            if mt.dim != d - 1:
-                raise ValueError(f"WallStress: the meshtags are of dimension {mt.dim}, facets have {d - 1}")
-            tags = np.atleast_1d(np.asarray(want, dtype=np.int64))
-            if np.unique(tags).shape[0] != tags.shape[0]:
-                raise ValueError("WallStress: a tag is listed twice")
-            parts = [np.asarray(mt.find(np.int32(g)), dtype=np.int64) for g in tags]
-            ids = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
-            tag_of = np.concatenate([np.full(p.shape[0], k, dtype=np.int64) for k, p in enumerate(parts)])
-        else:
-            ids = np.asarray(facets.cpu().numpy() if torch.is_tensor(facets) else facets, dtype=np.int64).reshape(-1)
-            tag_of, tags = np.zeros(ids.shape[0], dtype=np.int64), np.array([0], dtype=np.int64)
-        order = np.lexsort((ids, tag_of))  # by tag, then by facet id
-        ids, tag_of = ids[order], tag_of[order]
-        fcell, fopp = facet_table(mesh, ids)
-        Vi, Q = solver._Vi[0][0], solver._Q
-        kpos = Vi.kernel_cell_index(fcell)
-        if (kpos < 0).any():
-            raise ValueError("WallStress: a facet's cell is not among the cells of the solver's spaces")
+        ids, tag_of, tags = select_facets(mesh, facets)
+        fs = FacetSet(solver, ids, tag_of, tags.shape[0])
         self._solver = solver
         self.rho = float(rho)
         self.gdim = d
         self.facets = ids
         self.tags = tags
         self.facet_tags = tags[tag_of] if ids.size else tag_of
-        self.cells, self.local_facets = fcell, fopp
-        self.n_facets, self.n_tags = int(ids.shape[0]), int(tags.shape[0])
+        self.cells, self.local_facets = fs.cells, fs.local_facets
+        self.n_facets, self.n_tags = fs.n_facets, fs.n_tags
         dev = mesh.device
-        # geometry on the host, from the records the kernel reads
-        geom = solver._geom[torch.from_numpy(kpos).to(dev)].cpu().numpy()  # (nf, gs)
-        G = geom[:, : d * d].reshape(-1, d, d)
-        G = np.concatenate([-G.sum(axis=1, keepdims=True), G], axis=1)
-        Ga = G[np.arange(self.n_facets), fopp]
-        ga = np.linalg.norm(Ga, axis=1)
-        self.normals = -Ga / ga[:, None]
-        self.areas = geom[:, d * d] * ga * (0.5 if d == 3 else 1.0)
-        fv, _ = mesh._entities(d - 1)
-        self.midpoints = mesh.coords.cpu().numpy()[fv[ids]].mean(axis=1)
-        # device tables
-        rec = np.stack([kpos, fopp], axis=1).astype(np.int32)
-        self._rec = torch.from_numpy(np.ascontiguousarray(rec)).to(dev)
-        ptr = np.zeros(self.n_tags + 1, dtype=np.int64)
-        ptr[1:] = np.cumsum(np.bincount(tag_of, minlength=self.n_tags))
-        self._tag_ptr = torch.from_numpy(ptr).to(dev)
+        self.normals, self.areas, self.midpoints = fs.normals, fs.areas, fs.midpoints
+        self._rec, self._tag_ptr = fs.rec, fs.tag_ptr
 
         def rows(*shape):
             return torch.zeros(shape, dtype=torch.float64, device=dev)
