@@ -61,6 +61,66 @@ def signed_unit_vectors(n: int, nc: int, seed: int):
     return (0.5 + rng.random((n, nc))) * np.where(rng.random((n, nc)) < 0.5, -1.0, 1.0)
 
 
+# ---- the same systems as the local matrix of a one-rank plan whose only peer is the rank itself -----------------------
+def ghosted(Acsr, r0: int, perm_seed: int, m: int | None = None):
+    """(A_loc, send): ``Acsr`` (n x n, far lower band at offset ``m``, default ``band_offset(n)``) as the n x (n + ng)
+    local matrix of a partitioned operator, ng = n - r0.  In every row r >= r0 the entry of column r - m moves to ghost
+    column n + j, j a fixed pseudo-random permutation of r - r0 (the send list is not monotone: a pack-order error
+    shows), and ``send[j] = r - m``: with ghost j receiving owned row send[j] the matrix acts on owned vectors as
+    ``folded(A_loc, send)``, which is ``Acsr`` entry for entry.  r0 > m (every row from r0 on has the band entry) and
+    r0 % 64 not in (0, 63): the slice of r0 mixes rows with and without ghost columns and must count as a boundary
+    slice.  scipy CSR with sorted indices."""
+    import scipy.sparse as sp
+
+    n = Acsr.shape[0]
+    m = band_offset(n) if m is None else int(m)
+    assert Acsr.shape == (n, n) and m < r0 < n and r0 % 64 not in (0, 63)
+    ng = n - r0
+    perm = np.random.default_rng(4000 + perm_seed).permutation(ng)
+    assert ng < 3 or (np.diff(perm) < 0).any()
+    coo = Acsr.tocoo()
+    row, col = coo.row.astype(np.int64), coo.col.astype(np.int64)
+    move = (row >= r0) & (col == row - m)
+    col[move] = n + perm[row[move] - r0]
+    send = np.empty(ng, dtype=np.int64)
+    send[perm] = np.arange(r0, n) - m
+    A_loc = sp.csr_matrix((coo.data, (row, col)), shape=(n, n + ng))
+    A_loc.sort_indices()
+    assert A_loc.nnz == Acsr.nnz
+    return A_loc, send
+
+
+def folded(A_loc, send):
+    """A_eff = A_loc[:, :n] + A_loc[:, n:] S with S[j, send[j]] = 1: what the ghosted matrix does to owned vectors."""
+    import scipy.sparse as sp
+
+    n, ng = A_loc.shape[0], A_loc.shape[1] - A_loc.shape[0]
+    S = sp.csr_matrix((np.ones(ng), (np.arange(ng), np.asarray(send))), shape=(ng, n))
+    A = sp.csr_matrix(A_loc[:, :n] + A_loc[:, n:] @ S)
+    A.sort_indices()
+    return A
+
+
+def slice_kinds(A_loc):
+    """(interior, boundary) 64-row slices of a ghosted matrix: boundary = some row of the slice has a ghost column (as
+    SellPattern.split_interior lists them)."""
+    n = A_loc.shape[0]
+    coo = A_loc.tocoo()
+    boundary = np.unique(coo.row[coo.col >= n] // 64).size
+    return (n + 63) // 64 - boundary, boundary
+
+
+def ghost_start(n: int, m: int | None = None) -> int:
+    """r0 of the larger cases: about n / 3 and beyond the far band, r0 % 64 == 21, with a number of interior slices that
+    is 2 or 3 mod 4 (n_slices % 4 == 1 in these systems: the boundary slices are then no multiple of 4 either, and both
+    grids end in a partly filled block)."""
+    m = band_offset(n) if m is None else m
+    ni = max(n // 3, m) // 64
+    while ni % 4 not in (2, 3) or ni * 64 + 21 <= m:
+        ni += 1
+    return ni * 64 + 21
+
+
 # ---- partial-row counts (the formulas of csrc/ox_kernels.h) --------------------------------------------------------
 def spmv_parts(n_rows: int) -> int:
     """Partial rows the lane = row mat-vec writes: round8(ceil(n_slices / 4)) (ox_spmv_blocks_n)."""
@@ -77,6 +137,13 @@ def vec_blocks(n: int, cap_small: int = 2048, cap_large: int = 1024) -> int:
 def vec_parts(n_rows: int) -> int:
     """Partial rows the Krylov vector kernels write: ox_vec_blocks(2 n_rows) (one row per thread)."""
     return vec_blocks(2 * max(n_rows, 1))
+
+
+def split_parts(n_interior_slices: int, n_boundary_slices: int) -> int:
+    """Partial rows the overlapped mat-vec of a partitioned operator writes: the interior and the boundary launch each
+    round their own grid to 8 (ox_spmv_dist_nparts)."""
+    r8 = lambda n_slices: (((n_slices + 3) // 4) + 7) & ~7
+    return r8(n_interior_slices) + r8(n_boundary_slices)
 
 
 def rows_for_parts(nparts: int) -> int:

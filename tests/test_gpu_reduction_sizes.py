@@ -42,8 +42,10 @@ rounding --, and for the merged-reduction BiCGStab the recurrence norm sqrt(s.s 
 (csrc/ox_ksp_dev.h, PH_BCGSM_B: ``double rr = fma(om, fma(om, tt, -2.0 * ts), ss)``; the stored residual is tested only
 for columns that norm declared converged, PH_BCGSM_FIN), which is compared with the same expression of the model.
 
-Known uncovered branches: the merged CG's own pre-reduction (PH_CGM_IT: from 4 * 16384 sums, i.e. more than 8 M rows),
-and the partitioned synchronisation points (k_ksp_reduce + k_ksp_logic, k_ksp_scalar_p2p) at these sizes.
+Known uncovered branches: the merged CG's own pre-reduction (PH_CGM_IT: from 4 * 16384 sums, i.e. more than 8 M rows).
+The partitioned synchronisation points (k_ksp_reduce + k_ksp_logic, k_ksp_scalar_p2p) are cut at 776, 1096 and 4104
+partial rows on one-rank plans by tests/test_gpu_partitioned_cuts.py, which shares this file's helpers through
+tests/cut_solves.py; sums over more than one rank's contribution remain with the multi-rank rehearsals.
 
 Mutation check.  Run once on an MI355X, never committed: five mutant libraries built from scratch copies of the sources,
 each making ONE gather loop skip one partial row, each run against the cases below and the 760-row control.  Every
@@ -60,33 +62,16 @@ mutant left the control (760-sym, 760-nonsym) passing and made the cases of its 
     ksp_fold_point, the np_ > U * T loop (thread 2 drops its 1st row)   10248-sym and 10248-dict, cg_fold and cg_fold1 only
         (the unfolded methods of the same cases passed)
 """
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
-from tests import krylov_steps_model as K
 from tests import reduction_systems as RS
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL = 1e-12  # the bound test_single_reduction_cg_nonzero_guess_and_max_it puts on a cut solve
-PRE = 1e-13  # float64 run of the recurrence against the extended one: the systems themselves allow TOL
+from tests.cut_solves import METHODS, PRE, TOL, _check_cuts, _Reference, _sell, _thresholds  # noqa: F401
 
 CONTROL, IN_FLIGHT, ROUND2, WIDE, ROUND2_WIDE = 760, 776, 2568, 4104, 10248
 PRERED_MBCGS3, PRERED_BCGS3, PRERED_CG3 = 1096, 2736, 5464
 
-METHODS = {
-    "cg": {"ksp_type": "cg", "ksp_cg_single_reduction": False, "ksp_cg_merged_reduction": False, "ksp_cg_fold_blocks": 0},
-    "cg_fold1": {"ksp_type": "cg", "ksp_cg_single_reduction": False, "ksp_cg_merged_reduction": False, "ksp_cg_fold_blocks": 1},
-    "cg_fold": {"ksp_type": "cg", "ksp_cg_single_reduction": False, "ksp_cg_merged_reduction": False},
-    "cg_single": {"ksp_type": "cg", "ksp_cg_single_reduction": True, "ksp_cg_merged_reduction": False},
-    "cg_merged": {"ksp_type": "cg", "ksp_cg_single_reduction": False, "ksp_cg_merged_reduction": True, "ksp_cg_fold_blocks": 0},
-    "cg_merged_fold": {"ksp_type": "cg", "ksp_cg_single_reduction": False, "ksp_cg_merged_reduction": True},
-    "bcgs": {"ksp_type": "bcgs", "ksp_bcgs_merged_reduction": False},
-    "bcgs_merged": {"ksp_type": "bcgs", "ksp_bcgs_merged_reduction": True},
-}
 CG_1 = [(m, 1) for m in ("cg", "cg_fold1", "cg_fold", "cg_single", "cg_merged", "cg_merged_fold")]
 CG_ALL = CG_1 + [("cg", 3), ("cg_single", 3)]  # (with 3 columns the fold setting and the merged form do not apply)
 BCGS_1 = [("bcgs", 1), ("bcgs_merged", 1)]
@@ -103,42 +88,6 @@ CASES = [
     (ROUND2_WIDE, "sym", CG_1), (ROUND2_WIDE, "dict", [("cg_fold", 1), ("cg_fold1", 1), ("cg", 1)]),
     (ROUND2_WIDE, "nonsym", BCGS_1),
 ]
-
-
-def _sources():
-    rd = lambda *p: open(os.path.join(ROOT, *p)).read()
-    return rd("oasisx_amd", "csrc", "ox_kernels.h"), rd("oasisx_amd", "csrc", "ox_ksp.hip")
-
-
-def _thresholds():
-    """The numbers the second stage branches on, as the sources state them."""
-    kh, ksp = _sources()
-
-    def one(pattern, text, what):
-        found = set(re.findall(pattern, text))
-        assert len(found) == 1, f"{what}: {sorted(found)} -- the sources no longer read as this test expects"
-        return int(found.pop())
-
-    T = {
-        "red_small": one(r"#define OX_RED_THREADS_SMALL (\d+)", kh, "OX_RED_THREADS_SMALL"),
-        "red_wide": one(r"#define OX_RED_THREADS (\d+)", kh, "OX_RED_THREADS"),
-        "wide_from": one(r"ox_red_threads\(int nparts\) \{ return nparts > (\d+) \? OX_RED_THREADS : OX_RED_THREADS_SMALL", kh,
-                         "ox_red_threads"),
-        "max_nv": one(r"#define OX_MAX_NV (\d+)", kh, "OX_MAX_NV"),
-        "chunk": one(r"#define OX_PRERED_CHUNK (\d+)", ksp, "OX_PRERED_CHUNK"),
-        "prered_min": one(r"#define OX_PRERED_MIN (\d+)", ksp, "OX_PRERED_MIN"),
-        "fold_t": one(r"#define OX_FOLD_T (\d+)", ksp, "OX_FOLD_T"),
-        "rows_u": one(r"ksp_gather_rows<[^;]*?, (\d+)>\(partial", ksp, "rows per thread of ksp_gather_rows"),
-        "fold_u": one(r"ksp_fold_point<1, (\d+), PH_CG_A", ksp, "U of the folded CG's first point"),
-        "cgm_prered": one(r"PH == PH_CGM_IT \? (\d+) \* OX_PRERED_MIN", ksp, "merged CG's pre-reduction factor"),
-        "cgm_fold_rows": one(r"nbs1 <= (\d+) \* OX_FOLD_T", ksp, "folded merged CG's row limit"),
-    }
-    # the branch conditions themselves
-    assert len(re.findall(r"for \(; p \+ 3 \* T < nparts; p \+= 4 \* T\)", kh + ksp)) == 2  # ox_gather_partials, ksp_gather_t
-    assert re.search(r"for \(int p0 = threadIdx\.x; p0 < nparts; p0 \+= U \* T\)", ksp)  # ksp_gather_rows
-    assert re.search(r"if \(np_ > U \* T\)", ksp) and re.search(r"if \(\(int64_t\)nparts \* nv >= prered_min\)", ksp)
-    assert re.search(r"if \(npin >= OX_PRERED_MIN\)", ksp)
-    return T
 
 
 def test_the_sizes_cross_the_thresholds_the_sources_state():
@@ -168,84 +117,6 @@ def test_the_sizes_cross_the_thresholds_the_sources_state():
     assert ROUND2_WIDE * 2 < T["cgm_prered"] * T["prered_min"]
     # the vector kernels' rows: capped at 2048 (no second round in a 256-thread block, never the wide block)
     assert RS.vec_parts(RS.rows_for_parts(ROUND2_WIDE)) == 2048 <= min(U * small, T["wide_from"])
-
-
-def _sell(Acsr, symmetric):
-    """SellMatrix of a scipy CSR matrix with sorted indices, without a mesh."""
-    from oasisx_amd import fem
-    from oasisx_amd.la import SellMatrix
-
-    n = Acsr.shape[0]
-    rl = np.diff(Acsr.indptr).astype(np.int64)
-    keys = np.repeat(np.arange(n, dtype=np.int64), rl) * n + Acsr.indices
-    P = fem.build_sell(n, n, torch.from_numpy(keys).cuda(), torch.from_numpy(rl).cuda(),
-                       torch.from_numpy(Acsr.indptr.astype(np.int64)).cuda())
-    A = SellMatrix(P, symmetric=symmetric)
-    A.vals.copy_(P.values_from_csr(Acsr))
-    A.version += 1
-    return A
-
-
-class _Reference:
-    """Extended-precision traces of one system, column by column, computed once and kept unchanged; the float64 run of
-    the same recurrence is held to PRE first (a device miss cannot be blamed on the system)."""
-
-    def __init__(self, Acsr, b, x0, bicgstab):
-        self.A, self.b, self.x0 = Acsr, b, x0
-        self.trace = K.jacobi_bicgstab_trace if bicgstab else K.jacobi_cg_trace
-        self._t = {}
-
-    def get(self, c, guess):
-        key = (c, guess)
-        if key not in self._t:
-            kmax, x0 = (2, self.x0[:, c]) if guess else (3, None)
-            hi = self.trace(self.A, self.b[:, c], x0, kmax)
-            lo = self.trace(self.A, self.b[:, c], x0, kmax, dtype=np.float64)
-            for k, (h, l) in enumerate(zip(hi, lo)):
-                ex = float(np.abs(h[0] - l[0]).max() / max(np.abs(h[0]).max(), np.finfo(np.float64).tiny))
-                er = float(abs(h[2] - l[2]) / h[1])
-                assert ex <= PRE and er <= PRE, f"the system does not allow {PRE:g} on the CPU: column {c}, k = {k}: {ex:.2e}, {er:.2e}"
-            self._t[key] = [(np.asarray(h[0], dtype=np.float64), float(h[1]), float(h[2]), float(h[-1])) for h in hi]
-        return self._t[key]
-
-
-def _check_cuts(A, ref, runs, n, dict_dinv=False):
-    """Every (method, columns) of ``runs``: k = 1, 2, 3 from a zero guess and k = 2 from a nonzero one; returns the list of
-    misses (empty: all within TOL) and prints every figure."""
-    from oasisx_amd import _lib
-    from oasisx_amd.fem import FieldStorage
-    from oasisx_amd.ksp import KSPSolver
-
-    misses = []
-    for method, nc in runs:
-        B = FieldStorage(n, nc, "cuda")
-        B.dev()[:] = torch.from_numpy(ref.b[:, :nc]).cuda()
-        x0 = torch.from_numpy(np.ascontiguousarray(ref.x0[:, :nc])).cuda()
-        ksp = KSPSolver(None, dict(METHODS[method], pc_type="jacobi", ksp_rtol=1e-30))
-        ksp.setOperators(A)
-        recurrence_norm = method == "bcgs_merged"
-        for k, guess in ((1, False), (2, False), (3, False), (2, True)):
-            ksp.updateOptions({"ksp_max_it": k, "ksp_initial_guess_nonzero": guess})
-            X = FieldStorage(n, nc, "cuda")
-            if guess:
-                X.dev().copy_(x0)
-            reasons = ksp.solve_block(B, X)
-            if dict_dinv:
-                assert ksp._dcode is not None, "the dictionary of dinv was not built: CODE = true is not what runs"
-            res, xs = ksp.last_result, X.dev().cpu().numpy()
-            for c in range(nc):
-                xr, bn, rn_true, rn_rec = ref.get(c, guess)[k]
-                rn = rn_rec if recurrence_norm else rn_true
-                ex = float(np.abs(xs[:, c] - xr).max() / np.abs(xr).max())
-                eb = abs(res.bnorm[c] - bn) / bn
-                er = abs(res.rnorm[c] - rn) / bn
-                tag = f"{method} nc={nc} c={c} k={k} guess={int(guess)}"
-                print(f"  {tag}: reason {reasons[c]} its {res.its[c]}  x {ex:.2e}  bnorm {eb:.2e}  rnorm {er:.2e}")
-                if reasons[c] != _lib.DIVERGED_ITS or res.its[c] != k:
-                    misses.append(f"{tag}: reason {reasons[c]}, {res.its[c]} iterations")
-                if not (ex <= TOL and eb <= TOL and er <= TOL):
-                    misses.append(f"{tag}: x {ex:.2e} bnorm {eb:.2e} rnorm {er:.2e}")
-    return misses
 
 
 @pytest.mark.gpu
