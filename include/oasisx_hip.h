@@ -693,6 +693,42 @@ int ox_eval_points(int degree, int gdim, const int32_t *cell_dofs, int64_t n_cel
 int ox_probe_sample(int degree, int gdim, const int32_t *cell_dofs, int64_t n_cells, int64_t n_rows, int64_t n_points,
                     const int64_t *cell_pos, const double *bary, const int64_t *perm, const double *field, int nc, int col,
                     double *ring, int64_t capacity, int64_t slot, int64_t ld, int64_t off, void *stream);
+/* Lagrangian tracers: every live particle (status 0) moves from t to t + dt through the velocity
+ * v(x, theta) = fma(theta, u_b(x) - u_a(x), u_a(x)), theta in [0, 1] across the step, in `substeps` substeps of h = dt /
+ * substeps by explicit Euler, the midpoint rule or classical RK4 -- one kernel, one lane per particle, nothing read back.
+ * Substep s starts at theta_s = s / substeps; a stage at the local fraction c evaluates at theta = (s + c) / substeps.
+ * Location: the substep's start lies in cell[i]; every later stage point and the end point take cell[i] again when
+ * use_hint is set and all barycentric coordinates there are >= 0, else the LOWEST containing cell of the locator
+ * (lambda >= -tol, as ox_locator_find).  A substep one of whose points lies in no cell leaves the particle at that
+ * substep's start with status 1, t_exit = t + theta_s dt, cell -1; a non-finite velocity or an index out of range does the
+ * same with status 2.  A completed substep adds h to age and |x_new - x_old| to path.
+ *   loc: a whole-mesh locator (created with cell_ids == NULL) of the same gdim; n_mesh_cells == its cell count.
+ *   cell_dofs [n_cells][nd]: the scalar space's table in kernel cell order (as ox_eval_points); cell_inv [n_mesh_cells]:
+ *   mesh cell id -> kernel cell position; u_a, u_b: interleaved blocks [n_rows][nc], nc >= gdim, at theta = 0 and 1 (the
+ *   same pointer twice: a steady field).  x [n][gdim], cell, status, age, path, t_exit [n]: the particles, read and
+ *   written.  Arguments are checked on the host before the first device call; n == 0 launches nothing. */
+#define OX_TRACER_EULER 0
+#define OX_TRACER_RK2 1
+#define OX_TRACER_RK4 2
+#define OX_TRACER_MAX_SUBSTEPS 1024
+typedef struct ox_tracer_args {
+  const ox_locator *loc;
+  int degree, gdim, nc;
+  const int32_t *cell_dofs;
+  int64_t n_cells, n_rows;
+  const int64_t *cell_inv;
+  int64_t n_mesh_cells;
+  const double *u_a, *u_b;
+  double t, dt;
+  int substeps, scheme, use_hint;
+  double tol;
+  int64_t n;
+  double *x;
+  int64_t *cell;
+  int32_t *status;
+  double *age, *path, *t_exit;
+} ox_tracer_args;
+int ox_tracer_advance(const ox_tracer_args *args, void *stream);
 
 /* ---- Passive scalar transport (ox_scalar.hip) ------------------------------------------------------------------------
  * The Crank-Nicolson system of a group of 1..OX_MAXC scalars (same diffusivity kappa, same Dirichlet rows) from the

@@ -13,6 +13,7 @@ from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
 from .scalar import ScalarTransport
+from .tracers import Tracers
 from .viscosity import CarreauYasuda, CellViscosity, Cross, PowerLaw, Smagorinsky, Wale
 from .wall import WallStress
 
@@ -37,4 +38,5 @@ __all__ = [
     "FlowRate",
     "Resistance",
     "Windkessel",
+    "Tracers",
 ]

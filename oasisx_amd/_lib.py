@@ -213,6 +213,39 @@ class ox_ksp_options(C.Structure):
     ]
 
 
+TRACER_SCHEMES = {"euler": 0, "rk2": 1, "rk4": 2}  # OX_TRACER_EULER / _RK2 / _RK4
+TRACER_MAX_SUBSTEPS = 1024  # OX_TRACER_MAX_SUBSTEPS
+
+
+class ox_tracer_args(C.Structure):
+    _fields_ = [
+        ("loc", C.c_void_p),
+        ("degree", C.c_int),
+        ("gdim", C.c_int),
+        ("nc", C.c_int),
+        ("cell_dofs", C.c_void_p),
+        ("n_cells", C.c_int64),
+        ("n_rows", C.c_int64),
+        ("cell_inv", C.c_void_p),
+        ("n_mesh_cells", C.c_int64),
+        ("u_a", C.c_void_p),
+        ("u_b", C.c_void_p),
+        ("t", C.c_double),
+        ("dt", C.c_double),
+        ("substeps", C.c_int),
+        ("scheme", C.c_int),
+        ("use_hint", C.c_int),
+        ("tol", C.c_double),
+        ("n", C.c_int64),
+        ("x", C.c_void_p),
+        ("cell", C.c_void_p),
+        ("status", C.c_void_p),
+        ("age", C.c_void_p),
+        ("path", C.c_void_p),
+        ("t_exit", C.c_void_p),
+    ]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -308,6 +341,7 @@ SIGNATURES = {
     "ox_locator_bary": (_I, [_P, _L, _P, _P, _P, _P]),
     "ox_eval_points": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P]),
     "ox_probe_sample": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _L, _L, _P]),
+    "ox_tracer_advance": (_I, [C.POINTER(ox_tracer_args), _P]),
     "ox_scalar_rows": (_I, [C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _D, _D, _I,
                             _P, _P, _P, _P, _P]),
     "ox_wall_stress": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _L, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P]),

@@ -449,6 +449,173 @@ __global__ __launch_bounds__(256) void k_eval_points(int64_t n, const int32_t *_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Lagrangian tracers: one lane carries one particle through a whole time step (all substeps, all Runge-Kutta stages) in
+// registers.  Per stage: the cached cell is tested (hint) or the point walks its bin's list exactly as k_loc_find does;
+// the basis is formed and the dof rows of BOTH time levels are gathered in dof order; the blend
+// v = fma(theta, u_b - u_a, u_a) gives the stage velocity.  A particle whose stage point -- or whose end point, which is
+// the next substep's first stage point -- lies in no cell is frozen at the start of that substep (status 1); a non-finite
+// velocity or an index out of range freezes it the same way with status 2.  No LDS, no atomics, no cross-lane traffic;
+// every loop is bounded by substeps, the stage count or a clamped list range.
+struct TracerParams {
+  LocGrid G;
+  int64_t n_loc, n_bins, n_list;
+  const int64_t *bin_ptr;
+  const int32_t *list;
+  const double *x0, *grad;
+  const int32_t *cell_dofs;
+  int64_t n_cells, n_rows;
+  const int64_t *cell_inv;
+  const double *u_a, *u_b;
+  int nc;
+  double t, dt, tol;
+  int substeps, scheme, use_hint;
+  int64_t n;
+  double *x;
+  int64_t *cell;
+  int32_t *status;
+  double *age, *path, *t_exit;
+};
+
+// the time of the substep's start, t + theta_s dt, as a product and a sum rounded separately (the numpy model's form)
+__device__ __forceinline__ double tracer_exit_time(double t, double theta_s, double dt) {
+#pragma clang fp contract(off)
+  const double p = theta_s * dt;
+  return t + p;
+}
+
+// the cell of x: the cached `cell` when the hint is on and all its barycentric coordinates are >= 0, else the lowest
+// containing cell of the bin's list (lambda >= -tol); false: none (outside the grid's box, NaN, or in no listed cell)
+template <int D>
+__device__ __forceinline__ bool tracer_locate(const TracerParams &P, const double (&x)[D], int64_t &cell, double (&lam)[D + 1]) {
+  if (P.use_hint && cell >= 0 && cell < P.n_loc && loc_bary<D>(P.x0, P.grad, cell, x, lam) >= 0.0) return true;
+  bool inside = true;
+#pragma unroll
+  for (int k = 0; k < D; ++k) inside = inside && (x[k] >= P.G.lo[k]) && (x[k] <= P.G.hi[k]);  // (NaN: outside)
+  if (!inside) return false;
+  int64_t bin = 0;
+#pragma unroll
+  for (int k = D - 1; k >= 0; --k) bin = bin * P.G.nb[k] + loc_bin(P.G, k, x[k]);
+  if (bin < 0 || bin >= P.n_bins) return false;
+  int64_t s0 = P.bin_ptr[bin], s1 = P.bin_ptr[bin + 1];
+  if (s0 < 0) s0 = 0;
+  if (s1 > P.n_list) s1 = P.n_list;
+  for (int64_t s = s0; s < s1; ++s) {
+    const int64_t c = P.list[s];
+    if (c < 0 || c >= P.n_loc) continue;
+    if (loc_bary<D>(P.x0, P.grad, c, x, lam) >= -P.tol) {  // ascending list: the first hit is the lowest containing cell
+      cell = c;
+      return true;
+    }
+  }
+  return false;
+}
+
+// v = (1 - theta) u_a(x) + theta u_b(x) in mesh cell `cell` at the barycentric point lam; false: an index out of range or
+// a non-finite value
+template <int D, int DEG>
+__device__ __forceinline__ bool tracer_velocity(const TracerParams &P, int64_t cell, const double (&lam)[D + 1], double theta,
+                                                double (&v)[D]) {
+  constexpr int ND = probe_nd(D, DEG);
+  const int64_t kp = P.cell_inv[cell];  // (cell is in [0, n_loc) = [0, n_mesh_cells): the caller's check)
+  if (kp < 0 || kp >= P.n_cells) return false;
+  double ua[D], ub[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) ua[k] = 0.0, ub[k] = 0.0;
+  bool ok = true;
+  auto add = [&](int a, double phi_a) {
+    const int64_t r = P.cell_dofs[kp * ND + a];
+    if (r < 0 || r >= P.n_rows) {
+      ok = false;
+      return;
+    }
+    const double *ra = P.u_a + r * P.nc, *rb = P.u_b + r * P.nc;
+#pragma unroll
+    for (int k = 0; k < D; ++k) ua[k] = fma(phi_a, ra[k], ua[k]), ub[k] = fma(phi_a, rb[k], ub[k]);
+  };
+  if constexpr (DEG < 3) {
+    double phi[ND];
+    probe_basis<D, DEG>(lam, phi);
+#pragma unroll
+    for (int a = 0; a < ND; ++a) add(a, phi[a]);
+  } else {
+    double m[ND];
+    probe_mono3<D>(lam, m);
+#pragma unroll 2
+    for (int a = 0; a < ND; ++a) add(a, probe_phi3<D>(m, a));
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    v[k] = fma(theta, ub[k] - ua[k], ua[k]);
+    ok = ok && isfinite(v[k]);
+  }
+  return ok;
+}
+
+template <int D, int DEG>
+__global__ __launch_bounds__(256) void k_tracer_advance(TracerParams P) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= P.n) return;
+  if (P.status[i] != 0) return;
+  double x[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = P.x[i * D + k];
+  int64_t cell = P.cell[i];
+  double age = P.age[i], path = P.path[i], t_exit = P.t_exit[i];
+  const double m = (double)P.substeps, h = P.dt / m;
+  const int n_stages = P.scheme == 0 ? 1 : (P.scheme == 1 ? 2 : 4);
+  const double scale = P.scheme == 2 ? h / 6.0 : h;
+  int status = 0;
+  for (int s = 0; s < P.substeps && status == 0; ++s) {
+    // stage j: point x + a_j h k_{j-1} at theta = (s + a_j) / m, a = (0, 1/2, 1/2, 1); x_new = x + scale * sum_j w_j k_j with
+    // w = (1) [Euler], (0, 1) [midpoint], (1, 2, 2, 1) [RK4]
+    double ks[D], kj[D], xs[D], lam[D + 1];
+#pragma unroll
+    for (int k = 0; k < D; ++k) ks[k] = 0.0, kj[k] = 0.0, xs[k] = x[k];
+    for (int j = 0; j < n_stages && status == 0; ++j) {
+      const double a = j == 0 ? 0.0 : (j == 3 ? 1.0 : 0.5);
+      const double w = P.scheme == 0 ? 1.0 : (P.scheme == 1 ? (double)j : (j == 0 || j == 3 ? 1.0 : 2.0));
+      if (j == 0) {  // the substep's start lies in `cell`: the seed's location, or the location of the last end point
+        if (cell < 0 || cell >= P.n_loc) status = 2;
+        else loc_bary<D>(P.x0, P.grad, cell, xs, lam);
+      } else {
+#pragma unroll
+        for (int k = 0; k < D; ++k) xs[k] = fma(a * h, kj[k], x[k]);
+        if (!tracer_locate<D>(P, xs, cell, lam)) status = 1;
+      }
+      if (status == 0) {
+        if (!tracer_velocity<D, DEG>(P, cell, lam, ((double)s + a) / m, kj)) status = 2;
+#pragma unroll
+        for (int k = 0; k < D; ++k) ks[k] = fma(w, kj[k], ks[k]);
+      }
+    }
+    if (status == 0) {
+#pragma unroll
+      for (int k = 0; k < D; ++k) xs[k] = fma(scale, ks[k], x[k]);
+      if (!tracer_locate<D>(P, xs, cell, lam)) status = 1;
+    }
+    if (status == 0) {
+      double d2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const double d = xs[k] - x[k];
+        d2 = fma(d, d, d2);
+        x[k] = xs[k];
+      }
+      path += sqrt(d2);
+      age += h;
+    } else {
+      t_exit = tracer_exit_time(P.t, (double)s / m, P.dt);
+      cell = -1;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) P.x[i * D + k] = x[k];
+  P.cell[i] = cell;
+  P.status[i] = status;
+  P.age[i] = age, P.path[i] = path, P.t_exit[i] = t_exit;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 static void loc_free(ox_locator *L) {
   if (!L) return;
@@ -656,4 +823,50 @@ extern "C" int ox_probe_sample(int degree, int gdim, const int32_t *cell_dofs, i
   if (!ring || slot < 0 || slot >= capacity) OX_FAIL("ox_probe_sample: slot %lld of %lld", (long long)slot, (long long)capacity);
   return eval_launch("ox_probe_sample", degree, gdim, cell_dofs, n_cells, n_rows, n_points, cell_pos, bary, perm, field, nc,
                      col, ring + (size_t)slot * (size_t)n_points * (size_t)ld, ld, off, ox_stream(stream));
+}
+
+extern "C" int ox_tracer_advance(const ox_tracer_args *a, void *stream) {
+  if (!a) OX_FAIL("ox_tracer_advance: null argument (args)");
+  if (!a->loc) OX_FAIL("ox_tracer_advance: null argument (loc)");
+  if (a->gdim != 2 && a->gdim != 3) OX_FAIL("ox_tracer_advance: gdim=%d", a->gdim);
+  if (a->degree < 1 || a->degree > 3) OX_FAIL("ox_tracer_advance: degree %d (1..3)", a->degree);
+  if (a->nc < a->gdim || a->nc > OX_MAXC) OX_FAIL("ox_tracer_advance: nc=%d (gdim=%d..%d)", a->nc, a->gdim, OX_MAXC);
+  if (a->substeps < 1 || a->substeps > OX_TRACER_MAX_SUBSTEPS)
+    OX_FAIL("ox_tracer_advance: substeps=%d (1..%d)", a->substeps, OX_TRACER_MAX_SUBSTEPS);
+  if (a->scheme != OX_TRACER_EULER && a->scheme != OX_TRACER_RK2 && a->scheme != OX_TRACER_RK4)
+    OX_FAIL("ox_tracer_advance: scheme=%d", a->scheme);
+  if (!std::isfinite(a->dt) || !std::isfinite(a->t)) OX_FAIL("ox_tracer_advance: dt=%g at t=%g is not finite", a->dt, a->t);
+  const ox_locator *L = a->loc;
+  if (L->ids) OX_FAIL("ox_tracer_advance: a locator over a selection of cells; tracers take the whole-mesh locator");
+  if (L->gdim != a->gdim) OX_FAIL("ox_tracer_advance: loc->gdim=%d, gdim=%d", L->gdim, a->gdim);
+  if (a->n_mesh_cells != L->n_cells)
+    OX_FAIL("ox_tracer_advance: n_mesh_cells=%lld, the locator holds %lld", (long long)a->n_mesh_cells, (long long)L->n_cells);
+  if (!(a->tol >= 0.0) || a->tol > L->tol) OX_FAIL("ox_tracer_advance: tol=%g, the grid was built for tol <= %g", a->tol, L->tol);
+  if (a->n < 0) OX_FAIL("ox_tracer_advance: n=%lld", (long long)a->n);
+  if (a->n == 0) return 0;
+  if (!a->cell_dofs || !a->cell_inv || !a->u_a || !a->u_b || a->n_cells < 1 || a->n_rows < 1)
+    OX_FAIL("ox_tracer_advance: null argument (cell_dofs, cell_inv, u_a, u_b)");
+  if (!a->x || !a->cell || !a->status || !a->age || !a->path || !a->t_exit)
+    OX_FAIL("ox_tracer_advance: null argument (x, cell, status, age, path, t_exit)");
+  TracerParams P;
+  P.G = L->grid;
+  P.n_loc = L->n_cells, P.n_bins = L->n_bins, P.n_list = L->n_list;
+  P.bin_ptr = L->bin_ptr, P.list = L->list, P.x0 = L->x0, P.grad = L->grad;
+  P.cell_dofs = a->cell_dofs, P.n_cells = a->n_cells, P.n_rows = a->n_rows, P.cell_inv = a->cell_inv;
+  P.u_a = a->u_a, P.u_b = a->u_b, P.nc = a->nc;
+  P.t = a->t, P.dt = a->dt, P.tol = a->tol;
+  P.substeps = a->substeps, P.scheme = a->scheme, P.use_hint = a->use_hint ? 1 : 0;
+  P.n = a->n, P.x = a->x, P.cell = a->cell, P.status = a->status, P.age = a->age, P.path = a->path, P.t_exit = a->t_exit;
+  hipStream_t st = ox_stream(stream);
+  const dim3 grid((unsigned)((a->n + 255) / 256)), blk(256);
+  switch (a->gdim * 10 + a->degree) {
+    case 21: hipLaunchKernelGGL((k_tracer_advance<2, 1>), grid, blk, 0, st, P); break;
+    case 22: hipLaunchKernelGGL((k_tracer_advance<2, 2>), grid, blk, 0, st, P); break;
+    case 23: hipLaunchKernelGGL((k_tracer_advance<2, 3>), grid, blk, 0, st, P); break;
+    case 31: hipLaunchKernelGGL((k_tracer_advance<3, 1>), grid, blk, 0, st, P); break;
+    case 32: hipLaunchKernelGGL((k_tracer_advance<3, 2>), grid, blk, 0, st, P); break;
+    default: hipLaunchKernelGGL((k_tracer_advance<3, 3>), grid, blk, 0, st, P); break;
+  }
+  OX_LAUNCH_CHECK();
+  return 0;
 }

@@ -177,15 +177,22 @@ def space_tree(Vs: FunctionSpace, tol: float = DEFAULT_TOL) -> BoundingBoxTree:
     return tree
 
 
-def kernel_positions(Vs: FunctionSpace, cells: torch.Tensor) -> torch.Tensor:
-    """Position in the space's kernel cell order of mesh cell ids (device int64; -1 stays -1, a cell the rank does not
-    hold gives -2)."""
+def kernel_position_table(Vs: FunctionSpace) -> torch.Tensor:
+    """(num_cells,) device int64: mesh cell id -> position in the space's kernel cell order (-2: a cell the rank does not
+    hold); built once per space."""
     inv = getattr(Vs, "_probe_cell_inv", None)
     if inv is None:
         inv = torch.full((Vs.mesh.num_cells,), -2, dtype=torch.int64, device=Vs.mesh.device)
         lc = Vs.local_cells.to(torch.int64)
         inv[lc] = torch.arange(int(lc.shape[0]), dtype=torch.int64, device=inv.device)
         Vs._probe_cell_inv = inv
+    return inv
+
+
+def kernel_positions(Vs: FunctionSpace, cells: torch.Tensor) -> torch.Tensor:
+    """Position in the space's kernel cell order of mesh cell ids (device int64; -1 stays -1, a cell the rank does not
+    hold gives -2)."""
+    inv = kernel_position_table(Vs)
     ok = cells >= 0
     return torch.where(ok, inv[cells.clamp(0, Vs.mesh.num_cells - 1)], torch.full_like(cells, -1))
 
