@@ -1279,6 +1279,23 @@ extern "C" int ox_assemble_div_vector(int row_degree, int u_degree, const ox_cel
 //   FAM 1 (rows V, cols Q): G[r][c][d] = int d_d(psi_c) phi_r        (p.dx(i) * v * dx, :348-352)
 //   FAM 2 (rows Q, cols V): D[r][c][d] = int d_d(phi_c) psi_r        (u.dx(i) * q * dx, :332-336)
 // ---------------------------------------------------------------------------------------
+// P3 rows, P2 columns on tetrahedra, FAM 0: the reference tensor int psi_j d(phi_i)/d(lambda_b) itself (fe_tables_h3.h:
+// summed in 40 digits by the generator, rounded once), contracted with G -- 3 FMAs per value.  The quadrature form below
+// sums 70 terms under the Grundmann-Moeller weights, 24 of them negative (sum |w| / sum w = 25): that cancellation cost
+// these entries 1.5 digits (109 u B against 86 allowed by the entrywise criterion of tests/assembly_model.py on a
+// stretched lattice).
+struct Rect0Tab33 {
+  double t[20][10][3];
+};
+constexpr Rect0Tab33 make_r0t33() {
+  Rect0Tab33 t{};
+  for (int i = 0; i < 20; ++i)
+    for (int j = 0; j < 10; ++j)
+      for (int b = 0; b < 3; ++b) t.t[i][j][b] = OX_RECT0_3H[i][j][b];
+  return t;
+}
+__device__ const Rect0Tab33 R0T33 = make_r0t33();
+
 template <int GDIM, int RDEG, int CDEG, int FAM, int PW>
 __global__ __launch_bounds__(256) void k_assemble_rect(ox_cells cells, ox_adj adj,
                                                        const uint8_t *__restrict__ adj_pos, ox_sell A) {
@@ -1306,6 +1323,17 @@ __global__ __launch_bounds__(256) void k_assemble_rect(ox_cells cells, ox_adj ad
     for (int j = 0; j < EC::ND; ++j)
 #pragma unroll
       for (int d = 0; d < GDIM; ++d) c[j][d] = 0.0;
+    if constexpr (FAM == 0 && GDIM == 3 && RDEG == 3 && CDEG == 2) {
+#pragma unroll
+      for (int j = 0; j < EC::ND; ++j)
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) {
+          double v = 0.0;
+#pragma unroll
+          for (int b = 1; b <= GDIM; ++b) v = fma(R0T33.t[i][j][b - 1], G[b][d], v);  // (the lambda_0 column is zero)
+          c[j][d] = v;
+        }
+    } else {
 #pragma unroll
     for (int q = 0; q < ER::NQ; ++q) {
       if constexpr (FAM == 0) {  // w psi_j(q) * grad phi_i(q)
@@ -1336,6 +1364,7 @@ __global__ __launch_bounds__(256) void k_assemble_rect(ox_cells cells, ox_adj ad
             }
       }
     }
+    }  // (the quadrature forms)
 #pragma unroll
     for (int j = 0; j < EC::ND; ++j) {
       const int kk = adj_pos[pidx * PW + j];
