@@ -484,6 +484,27 @@ int ox_assemble_stress_transpose(int degree, const ox_cells *cells, const int32_
                                  int64_t n_rows, const double *uab, const double *nut, double scale, double *b,
                                  void *stream);
 
+/* ---- flow diagnostics and running statistics: read-only on the solver's fields ---- */
+/* Per cell e (kernel cell order, one lane per cell) of the velocity u (interleaved [n_u][gdim], cell_dofs [n_cells][nd] of
+ * the component space of `degree` 1, 2, 3), with g = grad u, S = sym g, W = skew g:
+ *   cell_integrals[e][7] (optional) = {|cell|, 1/2 int |u|^2, int 2 S:S, (nu + nut[e]) int 2 S:S, 1/2 int |curl u|^2,
+ *                                      int (div u)^2, int div u}, exact for the element (nut optional: NULL = nu alone);
+ *   fields[e][NF] (optional), NF = 4 + (gdim == 2 ? 1 : 3), values at the cell's centroid:
+ *                                     {dt max_a |u . grad lambda_a|, sqrt(2 S:S), tr g, 1/2 (W:W - S:S), curl u (1 | 3)};
+ *   partials[(n_cells + 255) / 256][8] = per 256-cell block the seven sums and the maximum of the first field, which is
+ *                                     NaN if any of its operands is.  Fixed reduction tree, no atomics. */
+int ox_flow_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *u, const double *nut, double dt,
+                  double nu, double *fields, double *cell_integrals, double *partials, void *stream);
+/* ring[slot][0..7] (ring: device [capacity][8]) = the seven sums and the (NaN-propagating) maximum over the n_blocks rows
+ * of partials.  One block, fixed order. */
+int ox_flow_reduce(int64_t n_blocks, const double *partials, double *ring, int64_t capacity, int64_t slot, void *stream);
+/* West's weighted incremental update per dof i < n of x (device, row i at x + i ldx, ncomp = 1, 2, 3 values):
+ *   W' = W_old + w, delta = x - mean, mean += (w / W') delta, cov[i][k] += (w W_old / W') delta_r delta_c for r <= c,
+ *   k over the upper triangle row by row (00, 01, 02, 11, 12, 22); mean [n][ncomp], cov [n][ncomp (ncomp + 1) / 2].
+ * W_old == 0: mean = x, cov = 0 (whatever they held).  w > 0.  One thread per dof, no atomics. */
+int ox_stats_accumulate(int ncomp, int64_t n, const double *x, int64_t ldx, double w, double W_old, double *mean,
+                        double *cov, void *stream);
+
 /* ---- A6 / A8: assemble_vector(p * v.dx(i) * dx) and (dp.dx(i) * v * dx), all i at once
  *      (fracstep.py:487-497 and :618).  kind 0: out[r][i] = base[r][i] + scale * int p d_i(phi_r)
  *      kind 1: out[r][i] = base[r][i] + scale * int d_i(p) phi_r.  base may be NULL (=0). */

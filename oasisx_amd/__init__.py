@@ -7,6 +7,7 @@ import logging
 
 from . import fem, geometry, io, mesh  # noqa: F401
 from .bcs import DirichletBC, LocatorMethod, PressureBC
+from .diagnostics import FlowDiagnostics, FlowStatistics
 from .fracstep import FractionalStep_AB_CN
 from .function import Projector
 from .geometry import Probes  # noqa: F401
@@ -39,4 +40,6 @@ __all__ = [
     "Resistance",
     "Windkessel",
     "Tracers",
+    "FlowDiagnostics",
+    "FlowStatistics",
 ]

@@ -297,6 +297,9 @@ SIGNATURES = {
     "ox_eddy_viscosity": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, _P, _P]),
     "ox_viscosity_law": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, C.POINTER(_D), _I, _P, _P]),
     "ox_assemble_stress_transpose": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P, _P, _D, _P, _P]),
+    "ox_flow_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _D, _D, _P, _P, _P, _P]),
+    "ox_flow_reduce": (_I, [_L, _P, _P, _L, _L, _P]),
+    "ox_stats_accumulate": (_I, [_I, _L, _P, _L, _D, _D, _P, _P, _P]),
     "ox_assemble_grad_vector": (_I, [_I, _I, _I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P,
                                      _P, _D, _P, _P]),
     "ox_assemble_div_vector": (_I, [_I, _I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P, _D,

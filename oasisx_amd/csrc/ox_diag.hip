@@ -1,0 +1,494 @@
+// Flow diagnostics and running statistics.  Nothing here writes a solver field or touches a matrix.
+//
+// ox_flow_cells: one lane per cell, in kernel cell order -- the streams of k_eddy_viscosity (the cell's dof list, its
+// geometry record, the gathered ND x GDIM coefficients) plus a quadrature loop.  With g = grad u (g[d][k] = du_d/dx_k),
+// S = sym g, W = skew g, omega = curl u:
+//
+//   cell integrals (exact for the element)                       centroid quantities (fields, optional)
+//     vol     = |cell| = |det J| / gdim!                           cfl   = dt max_a |u(x_c) . grad lambda_a|
+//     ke      = 1/2 int |u|^2      (mass table, degree 2 DEG)      shear = sqrt(2 S:S)       (gd of ox_viscosity_law)
+//     strain2 = int 2 S:S          (rule of degree 2 (DEG - 1))    divc  = tr g
+//     diss    = (nu + nut_c) strain2                               q     = 1/2 (W:W - S:S)
+//     ens     = 1/2 int |omega|^2                                  omega: g[1][0] - g[0][1]  |  the three of curl u
+//     div2    = int (div u)^2
+//     div1    = int div u
+//
+// ke contracts the dofs with the mean mass matrix of the element (compile-time constants, zero entries cost nothing);
+// the gradient forms are summed on a positive-weight rule whose tables sit in __constant__ memory and are read with a
+// lane-uniform point index (scalar loads).  Per 256-lane block the seven sums and max cfl go to partials[block][8]
+// through a fixed shuffle / LDS tree: no atomics, equal inputs give equal bits.  The maximum PROPAGATES NaN (fmax would
+// drop it): a run that has blown up shows NaN, not the largest finite value.
+//
+// ox_flow_reduce: one block, lane-strided over the partial rows in a fixed order, the same tree, ring[slot][0..7].
+//
+// ox_stats_accumulate: West's (1979) weighted incremental update of mean and upper-triangular covariance sums per dof,
+// one thread per dof (pure streaming, 16-byte accesses where the interleaved layout allows, no atomics).
+#include "fe_tables_c.h"
+#define OX_DIAG_RULE_QUAL __constant__
+#include "fe_tables_d.h"
+#include "ox_kernels.h"
+#include <cmath>
+
+namespace {
+
+template <int GDIM, int DEG>
+struct Diag {
+  static_assert(DEG >= 1 && DEG <= 3, "Lagrange degree 1, 2, 3");
+  static constexpr int ND = DEG == 1 ? GDIM + 1 : (DEG == 3 ? (GDIM == 2 ? 10 : 20) : (GDIM == 2 ? 6 : 10));
+  static constexpr int GS = GDIM == 2 ? 6 : 10;
+  static constexpr int NF = 4 + (GDIM == 2 ? 1 : 3);
+  static constexpr int B0 = DEG == 3 ? 1 : 0;  // (P3: the basis is a polynomial of lambda_1..d, column 0 is zero)
+  static constexpr int NQ = GDIM == 2 ? (DEG == 1 ? OX_NQD2_1 : (DEG == 2 ? OX_NQD2_2 : OX_NQD2_3))
+                                      : (DEG == 1 ? OX_NQD3_1 : (DEG == 2 ? OX_NQD3_2 : OX_NQD3_3));
+  __host__ __device__ static constexpr double dphic(int i, int b) {
+    if constexpr (GDIM == 2 && DEG == 1) return OX_DPHIC2_1[i][b];
+    else if constexpr (GDIM == 2 && DEG == 2) return OX_DPHIC2_2[i][b];
+    else if constexpr (GDIM == 2) return OX_DPHIC2_3[i][b];
+    else if constexpr (DEG == 1) return OX_DPHIC3_1[i][b];
+    else if constexpr (DEG == 2) return OX_DPHIC3_2[i][b];
+    else return OX_DPHIC3_3[i][b];
+  }
+  __host__ __device__ static constexpr double phic(int i) {
+    if constexpr (GDIM == 2 && DEG == 1) return OX_PHIC2_1[i];
+    else if constexpr (GDIM == 2 && DEG == 2) return OX_PHIC2_2[i];
+    else if constexpr (GDIM == 2) return OX_PHIC2_3[i];
+    else if constexpr (DEG == 1) return OX_PHIC3_1[i];
+    else if constexpr (DEG == 2) return OX_PHIC3_2[i];
+    else return OX_PHIC3_3[i];
+  }
+  __host__ __device__ static constexpr double mass(int i, int j) {
+    if constexpr (GDIM == 2 && DEG == 1) return OX_MASSD2_1[i][j];
+    else if constexpr (GDIM == 2 && DEG == 2) return OX_MASSD2_2[i][j];
+    else if constexpr (GDIM == 2) return OX_MASSD2_3[i][j];
+    else if constexpr (DEG == 1) return OX_MASSD3_1[i][j];
+    else if constexpr (DEG == 2) return OX_MASSD3_2[i][j];
+    else return OX_MASSD3_3[i][j];
+  }
+  __device__ static const double *qw() {
+    if constexpr (GDIM == 2 && DEG == 1) return OX_QWD2_1;
+    else if constexpr (GDIM == 2 && DEG == 2) return OX_QWD2_2;
+    else if constexpr (GDIM == 2) return OX_QWD2_3;
+    else if constexpr (DEG == 1) return OX_QWD3_1;
+    else if constexpr (DEG == 2) return OX_QWD3_2;
+    else return OX_QWD3_3;
+  }
+  __device__ static const double *dphiq() {  // [q][i][b], b = 0..GDIM
+    if constexpr (GDIM == 2 && DEG == 1) return &OX_DPHID2_1[0][0][0];
+    else if constexpr (GDIM == 2 && DEG == 2) return &OX_DPHID2_2[0][0][0];
+    else if constexpr (GDIM == 2) return &OX_DPHID2_3[0][0][0];
+    else if constexpr (DEG == 1) return &OX_DPHID3_1[0][0][0];
+    else if constexpr (DEG == 2) return &OX_DPHID3_2[0][0][0];
+    else return &OX_DPHID3_3[0][0][0];
+  }
+};
+
+// max that keeps a NaN (and, like fmax, prefers neither sign of zero: the operands here are >= 0 or NaN)
+__device__ __forceinline__ double nan_max(double a, double b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
+
+__device__ __forceinline__ double wave_nan_max(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = nan_max(v, __shfl_down(v, off, 64));
+  return v;  // valid in lane 0
+}
+
+// The seven sums and the maximum of a 256-lane block, valid in thread 0: wave shuffles, then the four wave results in
+// wave order.  lds: [4 * 8].
+__device__ __forceinline__ void block_reduce8(double (&v)[7], double &m, double *lds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const double s = ox_wave_sum(v[i]);
+    if (lane == 0) lds[wave * 8 + i] = s;
+  }
+  const double mm = wave_nan_max(m);
+  if (lane == 0) lds[wave * 8 + 7] = mm;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) v[i] = lds[i] + lds[8 + i] + lds[16 + i] + lds[24 + i];
+    m = nan_max(nan_max(lds[7], lds[15]), nan_max(lds[23], lds[31]));
+  }
+}
+
+// g[d][k] = sum_b t[d][b] G[b][k]
+template <int GDIM>
+__device__ __forceinline__ void grad_from_t(const double (&t)[GDIM][GDIM + 1], const double (&G)[GDIM + 1][GDIM],
+                                            double (&g)[GDIM][GDIM], int b0) {
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+    for (int k = 0; k < GDIM; ++k) {
+      double v = 0.0;
+#pragma unroll
+      for (int b = 0; b <= GDIM; ++b)
+        if (b >= b0) v = fma(t[d][b], G[b][k], v);
+      g[d][k] = v;
+    }
+}
+
+// S:S, |omega|^2 (omega: the GDIM == 2 ? 1 : 3 components of curl u) and tr g
+template <int GDIM>
+__device__ __forceinline__ void invariants(const double (&g)[GDIM][GDIM], double &ss, double (&om)[GDIM == 2 ? 1 : 3],
+                                           double &om2, double &tr) {
+  ss = 0.0;
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+    for (int k = 0; k < GDIM; ++k) {
+      const double s = 0.5 * (g[d][k] + g[k][d]);
+      ss = fma(s, s, ss);
+    }
+  if constexpr (GDIM == 2) {
+    om[0] = g[1][0] - g[0][1];
+    om2 = om[0] * om[0];
+    tr = g[0][0] + g[1][1];
+  } else {
+    om[0] = g[2][1] - g[1][2];
+    om[1] = g[0][2] - g[2][0];
+    om[2] = g[1][0] - g[0][1];
+    om2 = fma(om[2], om[2], fma(om[1], om[1], om[0] * om[0]));
+    tr = g[0][0] + g[1][1] + g[2][2];
+  }
+}
+
+template <int GDIM, int DEG>
+__global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_t *__restrict__ cell_dofs,
+                                                    const double *__restrict__ u, const double *__restrict__ nut, double dt,
+                                                    double nu, double *__restrict__ fields, double *__restrict__ cint,
+                                                    double *__restrict__ partials) {
+  using E = Diag<GDIM, DEG>;
+  constexpr int ND = E::ND, GS = E::GS, NF = E::NF, B0 = E::B0;
+  __shared__ double lds[32];
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double v[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) v[i] = 0.0;
+  double cfl = 0.0;
+  if (e < cells.n_cells) {
+    // round 1: the cell's dofs and geometry (both indexed by e); round 2: the coefficient gathers
+    int32_t dd[ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) dd[i] = cell_dofs[(size_t)e * ND + i];
+    const double *__restrict__ gp = cells.geom + (size_t)e * GS;
+    double G[GDIM + 1][GDIM];
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) G[0][d] = 0.0;
+#pragma unroll
+    for (int a = 1; a <= GDIM; ++a)
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d) {
+        G[a][d] = gp[(a - 1) * GDIM + d];
+        G[0][d] -= G[a][d];
+      }
+    const double adet = gp[GDIM * GDIM];
+    double uc[ND][GDIM];
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d) uc[i][d] = u[(size_t)dd[i] * GDIM + d];
+    const double vol = GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0);
+
+    // ---- ke = 1/2 |cell| sum_d u_d^T M u_d, M the mean mass matrix
+    double k2 = 0.0;
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+      for (int i = 0; i < ND; ++i) {
+        double r = 0.0;
+#pragma unroll
+        for (int j = 0; j < ND; ++j)
+          if (E::mass(i, j) != 0.0) r = fma(E::mass(i, j), uc[j][d], r);
+        k2 = fma(uc[i][d], r, k2);
+      }
+
+    // ---- the gradient forms on the rule of degree 2 (DEG - 1): weights sum to 1, the sums are cell MEANS
+    double s2 = 0.0, en = 0.0, d2 = 0.0, d1 = 0.0;
+    const double *__restrict__ wq = E::qw();
+    const double *__restrict__ dq = E::dphiq();
+#pragma unroll 1
+    for (int q = 0; q < E::NQ; ++q) {
+      double t[GDIM][GDIM + 1];
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+        for (int b = 0; b <= GDIM; ++b) t[d][b] = 0.0;
+#pragma unroll
+      for (int i = 0; i < ND; ++i)
+#pragma unroll
+        for (int b = B0; b <= GDIM; ++b) {
+          const double c = dq[(q * ND + i) * (GDIM + 1) + b];
+#pragma unroll
+          for (int d = 0; d < GDIM; ++d) t[d][b] = fma(uc[i][d], c, t[d][b]);
+        }
+      double g[GDIM][GDIM], om[GDIM == 2 ? 1 : 3], ss, om2, tr;
+      grad_from_t<GDIM>(t, G, g, B0);
+      invariants<GDIM>(g, ss, om, om2, tr);
+      const double w = wq[q];
+      s2 = fma(w, 2.0 * ss, s2);
+      en = fma(w, om2, en);
+      d2 = fma(w, tr * tr, d2);
+      d1 = fma(w, tr, d1);
+    }
+    v[0] = vol;
+    v[1] = (0.5 * vol) * k2;
+    v[2] = vol * s2;
+    v[3] = (nut ? nu + nut[e] : nu) * v[2];
+    v[4] = (0.5 * vol) * en;
+    v[5] = vol * d2;
+    v[6] = vol * d1;
+    if (cint) {
+#pragma unroll
+      for (int i = 0; i < 7; ++i) cint[(size_t)e * 7 + i] = v[i];
+    }
+
+    // ---- the centroid: grad u in the contraction order of k_eddy_viscosity, u(x_c) for the CFL number
+    double t[GDIM][GDIM + 1], ucen[GDIM];
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) {
+      ucen[d] = 0.0;
+#pragma unroll
+      for (int b = 0; b <= GDIM; ++b) t[d][b] = 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+#pragma unroll
+      for (int b = 0; b <= GDIM; ++b)
+        if (E::dphic(i, b) != 0.0) {
+#pragma unroll
+          for (int d = 0; d < GDIM; ++d) t[d][b] = fma(uc[i][d], E::dphic(i, b), t[d][b]);
+        }
+      if (E::phic(i) != 0.0) {
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) ucen[d] = fma(uc[i][d], E::phic(i), ucen[d]);
+      }
+    }
+    double m = 0.0;
+#pragma unroll
+    for (int a = 0; a <= GDIM; ++a) {
+      double r = 0.0;
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d) r = fma(ucen[d], G[a][d], r);
+      m = nan_max(m, fabs(r));
+    }
+    cfl = dt * m;
+    if (fields) {
+      double g[GDIM][GDIM], om[GDIM == 2 ? 1 : 3], ss, om2, tr;
+      grad_from_t<GDIM>(t, G, g, 0);
+      invariants<GDIM>(g, ss, om, om2, tr);
+      double ww = 0.0;  // W:W
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+        for (int k = 0; k < GDIM; ++k) {
+          const double a = 0.5 * (g[d][k] - g[k][d]);
+          ww = fma(a, a, ww);
+        }
+      double *__restrict__ f = fields + (size_t)e * NF;
+      f[0] = cfl;
+      f[1] = sqrt(2.0 * ss);
+      f[2] = tr;
+      f[3] = 0.5 * (ww - ss);
+#pragma unroll
+      for (int c = 0; c < NF - 4; ++c) f[4 + c] = om[c];
+    }
+  }
+  block_reduce8(v, cfl, lds);
+  if (threadIdx.x == 0) {
+    double *__restrict__ p = partials + (size_t)blockIdx.x * 8;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) p[i] = v[i];
+    p[7] = cfl;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_flow_reduce(int64_t n_blocks, const double *__restrict__ partials,
+                                                     double *__restrict__ row) {
+  __shared__ double lds[32];
+  double v[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) v[i] = 0.0;
+  double m = 0.0;
+  for (int64_t r = threadIdx.x; r < n_blocks; r += 256) {
+    const double *__restrict__ p = partials + (size_t)r * 8;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) v[i] += p[i];
+    m = nan_max(m, p[7]);
+  }
+  block_reduce8(v, m, lds);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) row[i] = v[i];
+    row[7] = m;
+  }
+}
+
+// West's update of one dof: a = w / W', b = W a = w W / W'
+template <int NC>
+__device__ __forceinline__ void west(const double (&x)[NC], double a, double b, double (&mean)[NC],
+                                     double (&cov)[NC * (NC + 1) / 2]) {
+  double dl[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) dl[c] = x[c] - mean[c];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) mean[c] = fma(a, dl[c], mean[c]);
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < NC; ++i)
+#pragma unroll
+    for (int j = i; j < NC; ++j, ++k) cov[k] = fma(b * dl[i], dl[j], cov[k]);
+}
+
+// One thread per dof.  VEC: x is dense (ldx == NC) and every pointer is 16-byte aligned -- the 16-byte-aligned groups of
+// the interleaved rows move as double2 (NC = 2: x and mean; NC = 3: cov, 48 B per dof; NC = 1: two dofs per thread).
+template <int NC, bool VEC>
+__global__ __launch_bounds__(256) void k_stats(int64_t n, const double *__restrict__ x, int64_t ldx, double a, double b,
+                                               int first, double *__restrict__ mean, double *__restrict__ cov) {
+  constexpr int NV = NC * (NC + 1) / 2;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if constexpr (NC == 1 && VEC) {
+    const int64_t np = n >> 1;
+    if (i < np) {
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      double2 mv = reinterpret_cast<double2 *>(mean)[i], cv = reinterpret_cast<double2 *>(cov)[i];
+      if (first) {
+        mv = xv;
+        cv = make_double2(0.0, 0.0);
+      } else {
+        double xs[1] = {xv.x}, ms[1] = {mv.x}, cs[1] = {cv.x};
+        west<1>(xs, a, b, ms, cs);
+        mv.x = ms[0], cv.x = cs[0];
+        xs[0] = xv.y, ms[0] = mv.y, cs[0] = cv.y;
+        west<1>(xs, a, b, ms, cs);
+        mv.y = ms[0], cv.y = cs[0];
+      }
+      reinterpret_cast<double2 *>(mean)[i] = mv;
+      reinterpret_cast<double2 *>(cov)[i] = cv;
+    } else if (i == np && (n & 1)) {
+      const int64_t k = n - 1;
+      if (first) {
+        mean[k] = x[k];
+        cov[k] = 0.0;
+      } else {
+        double xs[1] = {x[k]}, ms[1] = {mean[k]}, cs[1] = {cov[k]};
+        west<1>(xs, a, b, ms, cs);
+        mean[k] = ms[0], cov[k] = cs[0];
+      }
+    }
+  } else {
+    if (i >= n) return;
+    double xs[NC], ms[NC], cs[NV];
+    if constexpr (NC == 2 && VEC) {
+      const double2 xv = reinterpret_cast<const double2 *>(x)[i];
+      xs[0] = xv.x, xs[1] = xv.y;
+    } else {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) xs[c] = x[(size_t)i * ldx + c];
+    }
+    if (first) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) ms[c] = xs[c];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) cs[k] = 0.0;
+    } else {
+      if constexpr (NC == 2 && VEC) {
+        const double2 mv = reinterpret_cast<const double2 *>(mean)[i];
+        ms[0] = mv.x, ms[1] = mv.y;
+      } else {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) ms[c] = mean[(size_t)i * NC + c];
+      }
+      if constexpr (NC == 3 && VEC) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double2 cv = reinterpret_cast<const double2 *>(cov)[(size_t)i * 3 + k];
+          cs[2 * k] = cv.x, cs[2 * k + 1] = cv.y;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) cs[k] = cov[(size_t)i * NV + k];
+      }
+      west<NC>(xs, a, b, ms, cs);
+    }
+    if constexpr (NC == 2 && VEC) {
+      reinterpret_cast<double2 *>(mean)[i] = make_double2(ms[0], ms[1]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) mean[(size_t)i * NC + c] = ms[c];
+    }
+    if constexpr (NC == 3 && VEC) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) reinterpret_cast<double2 *>(cov)[(size_t)i * 3 + k] = make_double2(cs[2 * k], cs[2 * k + 1]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) cov[(size_t)i * NV + k] = cs[k];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int ox_flow_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *u, const double *nut,
+                             double dt, double nu, double *fields, double *cell_integrals, double *partials, void *stream) {
+  if (!cells || !cell_dofs || !u || !partials || !cells->geom) OX_FAIL("ox_flow_cells: null argument");
+  if (!(dt > 0.0) || !std::isfinite(dt)) OX_FAIL("ox_flow_cells: dt=%g", dt);
+  if (!(nu >= 0.0) || !std::isfinite(nu)) OX_FAIL("ox_flow_cells: nu=%g", nu);
+  if (cells->n_cells <= 0) OX_FAIL("ox_flow_cells: %lld cells", (long long)cells->n_cells);
+  if (cells->n_cells > (int64_t)0x7fffffff) OX_FAIL("ox_flow_cells: %lld cells", (long long)cells->n_cells);
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const unsigned nblk = (unsigned)((cells->n_cells + 255) / 256);
+#define OX_FLOW_CASE(GD, DG)                                                                                              \
+  if (g == GD && degree == DG) {                                                                                          \
+    if (ox_prof_on) ox_prof_start(OX_TAG_FLOW_CELLS, st, cells->n_cells);                                                 \
+    hipLaunchKernelGGL((k_flow_cells<GD, DG>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, u, nut, dt, nu, fields,   \
+                       cell_integrals, partials);                                                                         \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                     \
+    OX_LAUNCH_CHECK();                                                                                                    \
+    return 0;                                                                                                             \
+  }
+  OX_FLOW_CASE(2, 1) OX_FLOW_CASE(2, 2) OX_FLOW_CASE(2, 3) OX_FLOW_CASE(3, 1) OX_FLOW_CASE(3, 2) OX_FLOW_CASE(3, 3)
+#undef OX_FLOW_CASE
+  OX_FAIL("ox_flow_cells: unsupported gdim=%d degree=%d", g, degree);
+}
+
+extern "C" int ox_flow_reduce(int64_t n_blocks, const double *partials, double *ring, int64_t capacity, int64_t slot,
+                              void *stream) {
+  if (!partials || !ring) OX_FAIL("ox_flow_reduce: null argument");
+  if (n_blocks <= 0) OX_FAIL("ox_flow_reduce: n_blocks=%lld", (long long)n_blocks);
+  if (slot < 0 || slot >= capacity) OX_FAIL("ox_flow_reduce: slot %lld of %lld", (long long)slot, (long long)capacity);
+  hipStream_t st = ox_stream(stream);
+  if (ox_prof_on) ox_prof_start(OX_TAG_FLOW_REDUCE, st, n_blocks);
+  hipLaunchKernelGGL(k_flow_reduce, dim3(1), dim3(256), 0, st, n_blocks, partials, ring + (size_t)slot * 8);
+  if (ox_prof_on) ox_prof_stop(st);
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ox_stats_accumulate(int ncomp, int64_t n, const double *x, int64_t ldx, double w, double W_old, double *mean,
+                                   double *cov, void *stream) {
+  if (!x || !mean || !cov) OX_FAIL("ox_stats_accumulate: null argument");
+  if (ncomp < 1 || ncomp > 3) OX_FAIL("ox_stats_accumulate: ncomp=%d", ncomp);
+  if (!(w > 0.0) || !std::isfinite(w)) OX_FAIL("ox_stats_accumulate: w=%g", w);
+  if (!(W_old >= 0.0) || !std::isfinite(W_old)) OX_FAIL("ox_stats_accumulate: W_old=%g", W_old);
+  if (ldx < ncomp) OX_FAIL("ox_stats_accumulate: ldx=%lld < ncomp=%d", (long long)ldx, ncomp);
+  if (n <= 0) return 0;
+  if (n > (int64_t)0x7fffffff * 128) OX_FAIL("ox_stats_accumulate: n=%lld", (long long)n);
+  hipStream_t st = ox_stream(stream);
+  const double Wn = W_old + w;
+  const double a = w / Wn, b = W_old * a;
+  const int first = W_old == 0.0;
+  const bool vec = ldx == ncomp && (((uintptr_t)x | (uintptr_t)mean | (uintptr_t)cov) & 15) == 0;
+  const int64_t threads = (ncomp == 1 && vec) ? n / 2 + 1 : n;
+  const unsigned nblk = (unsigned)((threads + 255) / 256);
+  if (ox_prof_on) ox_prof_start(OX_TAG_STATS_ACCUMULATE, st, n * ncomp);
+#define OX_STATS_CASE(NC)                                                                                              \
+  if (ncomp == NC) {                                                                                                   \
+    if (vec) hipLaunchKernelGGL((k_stats<NC, true>), dim3(nblk), dim3(256), 0, st, n, x, ldx, a, b, first, mean, cov); \
+    else hipLaunchKernelGGL((k_stats<NC, false>), dim3(nblk), dim3(256), 0, st, n, x, ldx, a, b, first, mean, cov);    \
+  }
+  OX_STATS_CASE(1) OX_STATS_CASE(2) OX_STATS_CASE(3)
+#undef OX_STATS_CASE
+  if (ox_prof_on) ox_prof_stop(st);
+  OX_LAUNCH_CHECK();
+  return 0;
+}

@@ -138,6 +138,9 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_SYNC_POINT 151 // one distributed Krylov synchronisation point (reduce + all-reduce + logic)
 #define OX_TAG_EDDY_VISCOSITY 160  // ox_eddy_viscosity (key = cells)
 #define OX_TAG_STRESS_TRANSPOSE 161 // ox_assemble_stress_transpose
+#define OX_TAG_FLOW_CELLS 162       // ox_flow_cells (key = cells)
+#define OX_TAG_FLOW_REDUCE 163      // ox_flow_reduce (key = partial rows)
+#define OX_TAG_STATS_ACCUMULATE 164 // ox_stats_accumulate (key = dofs x components)
 #define OX_TAG_WALL_STRESS 170     // ox_wall_stress (key = facets)
 #define OX_TAG_WALL_FORCES 171     // ox_wall_forces (key = tags)
 #define OX_TAG_OUTLET_FLUX 180     // ox_outlet_flux (key = facets)

@@ -186,6 +186,42 @@ def write_facet_vtu(path, mesh, facets, cell_data=None, time: float = 0.0) -> No
         fh.write("".join(out))
 
 
+def write_cell_vtu(path, mesh, cell_data, time: float = 0.0) -> None:
+    """The mesh as straight VTK_TRIANGLE (5) / VTK_TETRA (10) cells on its own vertices with per-cell data ``{name:
+    (num_cells,) or (num_cells, ncomp)}`` in the MESH's cell order (host arrays or tensors, e.g.
+    ``FlowDiagnostics.cell_field``, ``solver.eddy_viscosity()``; vectors are padded to 3 components) as one ``.vtu``.
+    ``read_vtu`` reads it back (``"cell_data"``)."""
+    d = mesh.gdim
+    X = np.zeros((int(mesh.coords.shape[0]), 3))
+    X[:, :d] = mesh.coords.cpu().numpy()
+    conn = mesh.cells.cpu().numpy().astype(np.int64)
+    nc = conn.shape[0]
+    out = ['<?xml version="1.0"?>\n<VTKFile type="UnstructuredGrid" version="1.0" byte_order="LittleEndian" '
+           'header_type="UInt64">\n<UnstructuredGrid>\n',
+           f'<FieldData><DataArray type="Float64" Name="TimeValue" NumberOfTuples="1" format="ascii">{float(time)!r}'
+           '</DataArray></FieldData>\n',
+           f'<Piece NumberOfPoints="{X.shape[0]}" NumberOfCells="{nc}">\n<PointData>\n</PointData>\n<CellData>\n']
+    for name, a in (cell_data or {}).items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape[0] != nc or a.ndim > 2:
+            raise ValueError(f"write_cell_vtu: {name!r} has shape {a.shape} for {nc} cells")
+        if a.ndim == 2 and a.shape[1] > 1:
+            v = np.zeros((nc, 3))
+            v[:, : a.shape[1]] = a
+            out.append(_data_array(name, v, 3))
+        else:
+            out.append(_data_array(name, a.reshape(-1)))
+    out.append("</CellData>\n<Points>\n" + _data_array("Points", X, 3) + "</Points>\n<Cells>\n")
+    out.append(_data_array("connectivity", conn.reshape(-1))
+               + _data_array("offsets", (np.arange(nc, dtype=np.int64) + 1) * (d + 1))
+               + _data_array("types", np.full(nc, 5 if d == 2 else 10, dtype=np.uint8)))
+    out.append("</Cells>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n")
+    os.makedirs(os.path.dirname(str(path)) or ".", exist_ok=True)
+    with open(str(path), "w") as fh:
+        fh.write("".join(out))
+
+
 def read_vtu(path: str) -> dict:
     """Minimal reader of the files this module writes (tests, post-processing without VTK):
     {"points", "connectivity", "offsets", "types", "time", "point_data": {name: array}, "cell_data": {name: array}}."""
