@@ -7,7 +7,7 @@
 #include "fe_tables.h"
 #include "fe_tables_h.h"
 #include "fe_tables_h3.h"
-#include "ox_kernels.h"
+#include "ox_element.h"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -26,9 +26,9 @@ struct Elem {
   static_assert(DEG < 3 || RULE == 1, "P3 needs the degree-9 rule");
   static constexpr int NV = GDIM + 1;
   // P3: vertices + 2 per edge + the cell's own dof (triangles) / one per face (tetrahedra)
-  static constexpr int ND = DEG == 1 ? GDIM + 1 : (DEG == 3 ? (GDIM == 2 ? 10 : 20) : (GDIM == 2 ? 6 : 10));
+  static constexpr int ND = ox_nd(GDIM, DEG);
   static constexpr int NQ = RULE == 1 ? (GDIM == 2 ? OX_NQ2H : OX_NQ3H) : (GDIM == 2 ? OX_NQ2 : OX_NQ3);
-  static constexpr int GS = GDIM == 2 ? 6 : 10;
+  static constexpr int GS = ox_gs(GDIM);
   __host__ __device__ static constexpr double w(int q) {
     if constexpr (RULE == 1 && GDIM == 3) return OX_QW3H[q];
     else if constexpr (RULE == 1) return OX_QW2H[q];
@@ -248,21 +248,6 @@ __device__ const QuadW33 QW33 = make_qw33();
 template <int GDIM, int DEG>
 inline constexpr bool OX_CONV_BY_QUADRATURE = (GDIM == 3 && DEG == 3);
 
-template <int GDIM>
-__device__ __forceinline__ void load_geom(const double *__restrict__ g, double (&G)[GDIM + 1][GDIM],
-                                          double &adet) {
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d) G[0][d] = 0.0;
-#pragma unroll
-  for (int a = 1; a <= GDIM; ++a)
-#pragma unroll
-    for (int d = 0; d < GDIM; ++d) {
-      G[a][d] = g[(a - 1) * GDIM + d];
-      G[0][d] -= G[a][d];
-    }
-  adet = g[GDIM * GDIM];
-}
-
 // ---------------------------------------------------------------------------------------
 // Matrix rows.  One wave per slice (64-thread blocks, wave-private LDS accumulator
 // acc[k][lane] for the slice's rows).  KIND = MASS / STIFF write A.vals = acc; KIND = CONV is
@@ -364,9 +349,9 @@ __device__ __forceinline__ void assemble_slice(const ox_cells &cells, const int3
 #ifdef OX_DIAG
       // (OX_AF_DBG bit 2, diagnostic builds only: every pair reads one of 8 cells' geometry -- L1 hits --: what a
       // dictionary of the cell geometry could save at most)
-      load_geom<GDIM>(cells.geom + (size_t)((F.dbg & 32) ? 0 : ((F.dbg & 4) ? (e[u] & 7) : e[u])) * GS, G[u], adet[u]);  // (bit 5: ONE cell: scalar loads)
+      ox_load_geom<GDIM>(cells.geom + (size_t)((F.dbg & 32) ? 0 : ((F.dbg & 4) ? (e[u] & 7) : e[u])) * GS, G[u], adet[u]);  // (bit 5: ONE cell: scalar loads)
 #else
-      load_geom<GDIM>(cells.geom + (size_t)e[u] * GS, G[u], adet[u]);
+      ox_load_geom<GDIM>(cells.geom + (size_t)e[u] * GS, G[u], adet[u]);
 #endif
       if constexpr (KIND == OX_KIND_CONV) {
 #ifdef OX_DIAG
@@ -847,7 +832,7 @@ __global__ __launch_bounds__(256) void k_weights(ox_cells cells, ox_adj adj, int
   const auto &R = rt<GDIM, DEG>();
   double s = 0.0;
   OX_ADJ_WALK_BEGIN
-  s = fma(cells.geom[(size_t)e * E::GS + GDIM * GDIM], R.iphi[i], s);
+  s = fma(ox_geom_adet<GDIM>(cells.geom + (size_t)e * E::GS), R.iphi[i], s);
   OX_ADJ_WALK_END
   if (row < n_rows) w[row] = s;
 }
@@ -927,7 +912,7 @@ __global__ __launch_bounds__(256) void k_dg1_grad_rhs(ox_cells cells, const int3
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= cells.n_cells) return;
   double G[GDIM + 1][GDIM], adet;
-  load_geom<GDIM>(cells.geom + (size_t)e * E::GS, G, adet);
+  ox_load_geom<GDIM>(cells.geom + (size_t)e * E::GS, G, adet);
   double uc[E::ND];
 #pragma unroll
   for (int k = 0; k < E::ND; ++k) uc[k] = u[cell_dofs[(size_t)e * E::ND + k]];
@@ -966,7 +951,7 @@ __global__ __launch_bounds__(256) void k_dg1_mass(ox_cells cells, int ncomp, con
                                                   double *__restrict__ out) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= cells.n_cells) return;
-  constexpr int GS = GDIM == 2 ? 6 : 10, NV = GDIM + 1;
+  constexpr int GS = ox_gs(GDIM), NV = GDIM + 1;
   constexpr double fact = GDIM == 2 ? 2.0 : 6.0;
   const double alpha = cells.geom[(size_t)e * GS + GDIM * GDIM] / fact / (double)((GDIM + 1) * (GDIM + 2));  // |K| / ((d+1)(d+2))
   for (int c = 0; c < ncomp; ++c) {
@@ -1036,7 +1021,7 @@ __global__ __launch_bounds__(256) void k_grad_vector(ox_cells cells, const int32
   for (int d = 0; d < GDIM; ++d) o[d] = 0.0;
   OX_ADJ_WALK_BEGIN
   double G[GDIM + 1][GDIM], adet;
-  load_geom<GDIM>(cells.geom + (size_t)e * ER::GS, G, adet);
+  ox_load_geom<GDIM>(cells.geom + (size_t)e * ER::GS, G, adet);
   const int32_t *__restrict__ pd = cell_pdofs + (size_t)e * EP::ND;
   double pc[EP::ND];
 #pragma unroll
@@ -1137,7 +1122,7 @@ __global__ __launch_bounds__(256) void k_stress_transpose(ox_cells cells, const 
   for (int d = 0; d < GDIM; ++d) o[d] = 0.0;
   OX_ADJ_WALK_BEGIN
   double G[GDIM + 1][GDIM], adet;
-  load_geom<GDIM>(cells.geom + (size_t)e * E::GS, G, adet);
+  ox_load_geom<GDIM>(cells.geom + (size_t)e * E::GS, G, adet);
   const double wn = nut[e] * adet;
   const int32_t *__restrict__ ud = cell_dofs + (size_t)e * E::ND;
   // gu[m][a] = G[a] . u_m
@@ -1214,7 +1199,7 @@ __global__ __launch_bounds__(256) void k_div_vector(ox_cells cells, const int32_
   double o = 0.0;
   OX_ADJ_WALK_BEGIN
   double G[GDIM + 1][GDIM], adet;
-  load_geom<GDIM>(cells.geom + (size_t)e * ER::GS, G, adet);
+  ox_load_geom<GDIM>(cells.geom + (size_t)e * ER::GS, G, adet);
   const int32_t *__restrict__ ud = cell_udofs + (size_t)e * EU::ND;
   // gu[k][b] = G[b] . u_k
   double gu[EU::ND][GDIM + 1];
@@ -1317,7 +1302,7 @@ __global__ __launch_bounds__(256) void k_assemble_rect(ox_cells cells, ox_adj ad
     if (e < 0) continue;
     const int i = adj.adj_loc[pidx];
     double G[GDIM + 1][GDIM], adet;
-    load_geom<GDIM>(cells.geom + (size_t)e * ER::GS, G, adet);
+    ox_load_geom<GDIM>(cells.geom + (size_t)e * ER::GS, G, adet);
     double c[EC::ND][GDIM];
 #pragma unroll
     for (int j = 0; j < EC::ND; ++j)

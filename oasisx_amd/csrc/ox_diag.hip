@@ -23,63 +23,24 @@
 //
 // ox_stats_accumulate: West's (1979) weighted incremental update of mean and upper-triangular covariance sums per dof,
 // one thread per dof (pure streaming, 16-byte accesses where the interleaved layout allows, no atomics).
-#include "fe_tables_c.h"
 #define OX_DIAG_RULE_QUAL __constant__
 #include "fe_tables_d.h"
-#include "ox_kernels.h"
+#include "ox_element.h"
 #include <cmath>
 
 namespace {
 
+// Sizes and tables particular to the diagnostics: the centroid values and the mean mass matrix of the basis
+// (compile-time constants) and the rule of degree 2 (DEG - 1), read at run time from __constant__ memory.
 template <int GDIM, int DEG>
 struct Diag {
-  static_assert(DEG >= 1 && DEG <= 3, "Lagrange degree 1, 2, 3");
-  static constexpr int ND = DEG == 1 ? GDIM + 1 : (DEG == 3 ? (GDIM == 2 ? 10 : 20) : (GDIM == 2 ? 6 : 10));
-  static constexpr int GS = GDIM == 2 ? 6 : 10;
   static constexpr int NF = 4 + (GDIM == 2 ? 1 : 3);
   static constexpr int B0 = DEG == 3 ? 1 : 0;  // (P3: the basis is a polynomial of lambda_1..d, column 0 is zero)
-  static constexpr int NQ = GDIM == 2 ? (DEG == 1 ? OX_NQD2_1 : (DEG == 2 ? OX_NQD2_2 : OX_NQD2_3))
-                                      : (DEG == 1 ? OX_NQD3_1 : (DEG == 2 ? OX_NQD3_2 : OX_NQD3_3));
-  __host__ __device__ static constexpr double dphic(int i, int b) {
-    if constexpr (GDIM == 2 && DEG == 1) return OX_DPHIC2_1[i][b];
-    else if constexpr (GDIM == 2 && DEG == 2) return OX_DPHIC2_2[i][b];
-    else if constexpr (GDIM == 2) return OX_DPHIC2_3[i][b];
-    else if constexpr (DEG == 1) return OX_DPHIC3_1[i][b];
-    else if constexpr (DEG == 2) return OX_DPHIC3_2[i][b];
-    else return OX_DPHIC3_3[i][b];
-  }
-  __host__ __device__ static constexpr double phic(int i) {
-    if constexpr (GDIM == 2 && DEG == 1) return OX_PHIC2_1[i];
-    else if constexpr (GDIM == 2 && DEG == 2) return OX_PHIC2_2[i];
-    else if constexpr (GDIM == 2) return OX_PHIC2_3[i];
-    else if constexpr (DEG == 1) return OX_PHIC3_1[i];
-    else if constexpr (DEG == 2) return OX_PHIC3_2[i];
-    else return OX_PHIC3_3[i];
-  }
-  __host__ __device__ static constexpr double mass(int i, int j) {
-    if constexpr (GDIM == 2 && DEG == 1) return OX_MASSD2_1[i][j];
-    else if constexpr (GDIM == 2 && DEG == 2) return OX_MASSD2_2[i][j];
-    else if constexpr (GDIM == 2) return OX_MASSD2_3[i][j];
-    else if constexpr (DEG == 1) return OX_MASSD3_1[i][j];
-    else if constexpr (DEG == 2) return OX_MASSD3_2[i][j];
-    else return OX_MASSD3_3[i][j];
-  }
-  __device__ static const double *qw() {
-    if constexpr (GDIM == 2 && DEG == 1) return OX_QWD2_1;
-    else if constexpr (GDIM == 2 && DEG == 2) return OX_QWD2_2;
-    else if constexpr (GDIM == 2) return OX_QWD2_3;
-    else if constexpr (DEG == 1) return OX_QWD3_1;
-    else if constexpr (DEG == 2) return OX_QWD3_2;
-    else return OX_QWD3_3;
-  }
-  __device__ static const double *dphiq() {  // [q][i][b], b = 0..GDIM
-    if constexpr (GDIM == 2 && DEG == 1) return &OX_DPHID2_1[0][0][0];
-    else if constexpr (GDIM == 2 && DEG == 2) return &OX_DPHID2_2[0][0][0];
-    else if constexpr (GDIM == 2) return &OX_DPHID2_3[0][0][0];
-    else if constexpr (DEG == 1) return &OX_DPHID3_1[0][0][0];
-    else if constexpr (DEG == 2) return &OX_DPHID3_2[0][0][0];
-    else return &OX_DPHID3_3[0][0][0];
-  }
+  __host__ __device__ static constexpr int nq() { OX_FE_PICK(GDIM, DEG, OX_NQD, ); }
+  __host__ __device__ static constexpr double phic(int i) { OX_FE_PICK(GDIM, DEG, OX_PHIC, [i]); }
+  __host__ __device__ static constexpr double mass(int i, int j) { OX_FE_PICK(GDIM, DEG, OX_MASSD, [i][j]); }
+  __device__ static const double *qw() { OX_FE_PICK(GDIM, DEG, OX_QWD, ); }
+  __device__ static const double *dphiq() { OX_FE_PICK(GDIM, DEG, OX_DPHID, [0][0]); }  // [q][i][b], b = 0..GDIM
 };
 
 // max that keeps a NaN (and, like fmax, prefers neither sign of zero: the operands here are >= 0 or NaN)
@@ -110,34 +71,11 @@ __device__ __forceinline__ void block_reduce8(double (&v)[7], double &m, double 
   }
 }
 
-// g[d][k] = sum_b t[d][b] G[b][k]
-template <int GDIM>
-__device__ __forceinline__ void grad_from_t(const double (&t)[GDIM][GDIM + 1], const double (&G)[GDIM + 1][GDIM],
-                                            double (&g)[GDIM][GDIM], int b0) {
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d)
-#pragma unroll
-    for (int k = 0; k < GDIM; ++k) {
-      double v = 0.0;
-#pragma unroll
-      for (int b = 0; b <= GDIM; ++b)
-        if (b >= b0) v = fma(t[d][b], G[b][k], v);
-      g[d][k] = v;
-    }
-}
-
 // S:S, |omega|^2 (omega: the GDIM == 2 ? 1 : 3 components of curl u) and tr g
 template <int GDIM>
 __device__ __forceinline__ void invariants(const double (&g)[GDIM][GDIM], double &ss, double (&om)[GDIM == 2 ? 1 : 3],
                                            double &om2, double &tr) {
-  ss = 0.0;
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d)
-#pragma unroll
-    for (int k = 0; k < GDIM; ++k) {
-      const double s = 0.5 * (g[d][k] + g[k][d]);
-      ss = fma(s, s, ss);
-    }
+  ss = ox_sym_sq<GDIM>(g);
   if constexpr (GDIM == 2) {
     om[0] = g[1][0] - g[0][1];
     om2 = om[0] * om[0];
@@ -157,7 +95,7 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
                                                     double nu, double *__restrict__ fields, double *__restrict__ cint,
                                                     double *__restrict__ partials) {
   using E = Diag<GDIM, DEG>;
-  constexpr int ND = E::ND, GS = E::GS, NF = E::NF, B0 = E::B0;
+  constexpr int ND = ox_nd(GDIM, DEG), NF = E::NF, B0 = E::B0;
   __shared__ double lds[32];
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   double v[7];
@@ -167,25 +105,11 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
   if (e < cells.n_cells) {
     // round 1: the cell's dofs and geometry (both indexed by e); round 2: the coefficient gathers
     int32_t dd[ND];
-#pragma unroll
-    for (int i = 0; i < ND; ++i) dd[i] = cell_dofs[(size_t)e * ND + i];
-    const double *__restrict__ gp = cells.geom + (size_t)e * GS;
-    double G[GDIM + 1][GDIM];
-#pragma unroll
-    for (int d = 0; d < GDIM; ++d) G[0][d] = 0.0;
-#pragma unroll
-    for (int a = 1; a <= GDIM; ++a)
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d) {
-        G[a][d] = gp[(a - 1) * GDIM + d];
-        G[0][d] -= G[a][d];
-      }
-    const double adet = gp[GDIM * GDIM];
+    ox_load_dofs<ND>(cell_dofs, e, dd);
+    double G[GDIM + 1][GDIM], adet;
+    ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
     double uc[ND][GDIM];
-#pragma unroll
-    for (int i = 0; i < ND; ++i)
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d) uc[i][d] = u[(size_t)dd[i] * GDIM + d];
+    ox_gather<ND, GDIM>(dd, u, uc);
     const double vol = GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0);
 
     // ---- ke = 1/2 |cell| sum_d u_d^T M u_d, M the mean mass matrix
@@ -206,7 +130,7 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
     const double *__restrict__ wq = E::qw();
     const double *__restrict__ dq = E::dphiq();
 #pragma unroll 1
-    for (int q = 0; q < E::NQ; ++q) {
+    for (int q = 0; q < E::nq(); ++q) {
       double t[GDIM][GDIM + 1];
 #pragma unroll
       for (int d = 0; d < GDIM; ++d)
@@ -221,7 +145,7 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
           for (int d = 0; d < GDIM; ++d) t[d][b] = fma(uc[i][d], c, t[d][b]);
         }
       double g[GDIM][GDIM], om[GDIM == 2 ? 1 : 3], ss, om2, tr;
-      grad_from_t<GDIM>(t, G, g, B0);
+      ox_grad_from_t<GDIM>(t, G, g, B0);
       invariants<GDIM>(g, ss, om, om2, tr);
       const double w = wq[q];
       s2 = fma(w, 2.0 * ss, s2);
@@ -241,27 +165,15 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
       for (int i = 0; i < 7; ++i) cint[(size_t)e * 7 + i] = v[i];
     }
 
-    // ---- the centroid: grad u in the contraction order of k_eddy_viscosity, u(x_c) for the CFL number
-    double t[GDIM][GDIM + 1], ucen[GDIM];
+    // ---- the centroid: grad u as k_eddy_viscosity forms it, u(x_c) for the CFL number
+    double t[GDIM][GDIM + 1] = {}, ucen[GDIM] = {};
+    ox_contract<GDIM, ND>(uc, ox_dphic<GDIM, DEG>(), t);
 #pragma unroll
-    for (int d = 0; d < GDIM; ++d) {
-      ucen[d] = 0.0;
-#pragma unroll
-      for (int b = 0; b <= GDIM; ++b) t[d][b] = 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < ND; ++i) {
-#pragma unroll
-      for (int b = 0; b <= GDIM; ++b)
-        if (E::dphic(i, b) != 0.0) {
-#pragma unroll
-          for (int d = 0; d < GDIM; ++d) t[d][b] = fma(uc[i][d], E::dphic(i, b), t[d][b]);
-        }
+    for (int i = 0; i < ND; ++i)
       if (E::phic(i) != 0.0) {
 #pragma unroll
         for (int d = 0; d < GDIM; ++d) ucen[d] = fma(uc[i][d], E::phic(i), ucen[d]);
       }
-    }
     double m = 0.0;
 #pragma unroll
     for (int a = 0; a <= GDIM; ++a) {
@@ -273,7 +185,7 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
     cfl = dt * m;
     if (fields) {
       double g[GDIM][GDIM], om[GDIM == 2 ? 1 : 3], ss, om2, tr;
-      grad_from_t<GDIM>(t, G, g, 0);
+      ox_grad_from_t<GDIM>(t, G, g);
       invariants<GDIM>(g, ss, om, om2, tr);
       double ww = 0.0;  // W:W
 #pragma unroll
@@ -433,10 +345,10 @@ extern "C" int ox_flow_cells(int degree, const ox_cells *cells, const int32_t *c
   if (!(dt > 0.0) || !std::isfinite(dt)) OX_FAIL("ox_flow_cells: dt=%g", dt);
   if (!(nu >= 0.0) || !std::isfinite(nu)) OX_FAIL("ox_flow_cells: nu=%g", nu);
   if (cells->n_cells <= 0) OX_FAIL("ox_flow_cells: %lld cells", (long long)cells->n_cells);
-  if (cells->n_cells > (int64_t)0x7fffffff) OX_FAIL("ox_flow_cells: %lld cells", (long long)cells->n_cells);
+  const int64_t nblk = ox_cell_blocks("ox_flow_cells", cells);
+  if (nblk < 0) return -1;
   hipStream_t st = ox_stream(stream);
   const int g = cells->gdim;
-  const unsigned nblk = (unsigned)((cells->n_cells + 255) / 256);
 #define OX_FLOW_CASE(GD, DG)                                                                                              \
   if (g == GD && degree == DG) {                                                                                          \
     if (ox_prof_on) ox_prof_start(OX_TAG_FLOW_CELLS, st, cells->n_cells);                                                 \
@@ -446,7 +358,7 @@ extern "C" int ox_flow_cells(int degree, const ox_cells *cells, const int32_t *c
     OX_LAUNCH_CHECK();                                                                                                    \
     return 0;                                                                                                             \
   }
-  OX_FLOW_CASE(2, 1) OX_FLOW_CASE(2, 2) OX_FLOW_CASE(2, 3) OX_FLOW_CASE(3, 1) OX_FLOW_CASE(3, 2) OX_FLOW_CASE(3, 3)
+  OX_FOR_GDIM_DEG(OX_FLOW_CASE)
 #undef OX_FLOW_CASE
   OX_FAIL("ox_flow_cells: unsupported gdim=%d degree=%d", g, degree);
 }

@@ -1,0 +1,155 @@
+// The element prologue shared by the per-cell and per-facet kernels: dof and geometry-record
+// sizes, the choice of a generated table by (GDIM, DEG), a cell's dof / geometry / coefficient loads, the gradient
+// contraction and the facet normal.  Every sum has ONE order, written here: the kernels that call these agree bit for bit.
+#pragma once
+#include "fe_tables_c.h"
+#include "fe_tables_f.h"
+#include "fe_tables_o.h"
+#include "ox_kernels.h"
+#include <type_traits>
+
+// dofs of the Lagrange element of degree 1, 2, 3 on a simplex, and doubles of a cell's geometry record
+// (GDIM rows grad lambda_1..GDIM, |det J|, padding)
+__host__ __device__ constexpr int ox_nd(int gdim, int deg) {
+  return deg == 1 ? gdim + 1 : (deg == 3 ? (gdim == 2 ? 10 : 20) : (gdim == 2 ? 6 : 10));
+}
+__host__ __device__ constexpr int ox_gs(int gdim) { return gdim == 2 ? 6 : 10; }
+static_assert(ox_nd(2, 1) == 3 && ox_nd(2, 2) == 6 && ox_nd(2, 3) == 10, "P1, P2, P3 triangles");
+static_assert(ox_nd(3, 1) == 4 && ox_nd(3, 2) == 10 && ox_nd(3, 3) == 20, "P1, P2, P3 tetrahedra");
+
+// The body of a function that returns STEM<GDIM>_<DEG> IDX of the generated tables, e.g.
+// OX_FE_PICK(GDIM, DEG, OX_DPHIC, [i][b]); an empty IDX returns the table itself.
+#define OX_FE_PICK(GDIM, DEG, STEM, IDX)                                                                 \
+  static_assert((GDIM == 2 || GDIM == 3) && DEG >= 1 && DEG <= 3, "simplices, Lagrange degree 1, 2, 3"); \
+  if constexpr (GDIM == 2 && DEG == 1) return STEM##2_1 IDX;                                             \
+  else if constexpr (GDIM == 2 && DEG == 2) return STEM##2_2 IDX;                                        \
+  else if constexpr (GDIM == 2) return STEM##2_3 IDX;                                                    \
+  else if constexpr (DEG == 1) return STEM##3_1 IDX;                                                     \
+  else if constexpr (DEG == 2) return STEM##3_2 IDX;                                                     \
+  else return STEM##3_3 IDX
+
+// dphi_i/dlambda_b at the centroid [i][b] and the facet means of the basis [a][i] (compile-time constants)
+template <int GDIM, int DEG>
+__host__ __device__ constexpr const auto &ox_dphic() {
+  OX_FE_PICK(GDIM, DEG, OX_DPHIC, );
+}
+template <int GDIM, int DEG>
+__host__ __device__ constexpr const auto &ox_phif() {
+  OX_FE_PICK(GDIM, DEG, OX_PHIF, );
+}
+
+template <int ND>
+__device__ __forceinline__ void ox_load_dofs(const int32_t *__restrict__ cell_dofs, int64_t e, int32_t (&dd)[ND]) {
+#pragma unroll
+  for (int i = 0; i < ND; ++i) dd[i] = cell_dofs[(size_t)e * ND + i];
+}
+
+// uc[i][c] = u[dd[i] * NC + c]: NC = GDIM for a velocity, 1 for a pressure
+template <int ND, int NC>
+__device__ __forceinline__ void ox_gather(const int32_t (&dd)[ND], const double *__restrict__ u, double (&uc)[ND][NC]) {
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) uc[i][c] = u[(size_t)dd[i] * NC + c];
+}
+
+// G[b] = grad lambda_b (G[0] = -sum of the others) and |det J| from a cell's geometry record
+template <int GDIM>
+__device__ __forceinline__ double ox_geom_adet(const double *__restrict__ gp) {
+  return gp[GDIM * GDIM];
+}
+template <int GDIM>
+__device__ __forceinline__ void ox_load_geom(const double *__restrict__ gp, double (&G)[GDIM + 1][GDIM], double &adet) {
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) G[0][d] = 0.0;
+#pragma unroll
+  for (int a = 1; a <= GDIM; ++a)
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) {
+      G[a][d] = gp[(a - 1) * GDIM + d];
+      G[0][d] -= G[a][d];
+    }
+  adet = ox_geom_adet<GDIM>(gp);
+}
+
+// t[d][b] += sum_i uc[i][d] tab[i][b] in dof order; tab is a compile-time table, its zero entries cost nothing
+template <int GDIM, int ND>
+__device__ __forceinline__ void ox_contract(const double (&uc)[ND][GDIM], const double (&tab)[ND][GDIM + 1],
+                                            double (&t)[GDIM][GDIM + 1]) {
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+#pragma unroll
+    for (int b = 0; b <= GDIM; ++b)
+      if (tab[i][b] != 0.0) {
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) t[d][b] = fma(uc[i][d], tab[i][b], t[d][b]);
+      }
+}
+
+// g[d][k] = sum_{b >= b0} t[d][b] G[b][k]
+template <int GDIM>
+__device__ __forceinline__ void ox_grad_from_t(const double (&t)[GDIM][GDIM + 1], const double (&G)[GDIM + 1][GDIM],
+                                               double (&g)[GDIM][GDIM], int b0 = 0) {
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+    for (int k = 0; k < GDIM; ++k) {
+      double v = 0.0;
+#pragma unroll
+      for (int b = 0; b <= GDIM; ++b)
+        if (b >= b0) v = fma(t[d][b], G[b][k], v);
+      g[d][k] = v;
+    }
+}
+
+// S:S, S = (g + g^T)/2
+template <int GDIM>
+__device__ __forceinline__ double ox_sym_sq(const double (&g)[GDIM][GDIM]) {
+  double ss = 0.0;
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d)
+#pragma unroll
+    for (int k = 0; k < GDIM; ++k) {
+      const double s = 0.5 * (g[d][k] + g[k][d]);
+      ss = fma(s, s, ss);
+    }
+  return ss;
+}
+
+// The facet opposite local vertex a, Ga = grad lambda_a: outward unit normal n = -Ga / |Ga| and measure
+// |det J| |Ga| / (GDIM - 1)!
+template <int GDIM>
+__device__ __forceinline__ void ox_facet_normal(const double (&Ga)[GDIM], double adet, double (&n)[GDIM], double &area) {
+  double ga2 = 0.0;
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) ga2 = fma(Ga[d], Ga[d], ga2);
+  const double ga = sqrt(ga2);
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) n[d] = -Ga[d] / ga;
+  area = adet * ga * (GDIM == 3 ? 0.5 : 1.0);
+}
+
+// f(std::integral_constant<int, a>) for the run-time local facet 0 <= a <= GDIM: one instantiation of f per facet
+template <int GDIM, class F>
+__device__ __forceinline__ void ox_facet_dispatch(int a, F &&f) {
+  if (a == 0) f(std::integral_constant<int, 0>{});
+  else if (a == 1) f(std::integral_constant<int, 1>{});
+  else if (a == 2) f(std::integral_constant<int, 2>{});
+  else if constexpr (GDIM == 3) f(std::integral_constant<int, 3>{});
+}
+
+// ---- host side: M(gdim, degree, further arguments...) for the six elements
+#define OX_FOR_GDIM_DEG(M, ...)                                         \
+  M(2, 1, ##__VA_ARGS__) M(2, 2, ##__VA_ARGS__) M(2, 3, ##__VA_ARGS__) \
+  M(3, 1, ##__VA_ARGS__) M(3, 2, ##__VA_ARGS__) M(3, 3, ##__VA_ARGS__)
+
+// 256-lane blocks of a launch with one lane per cell: 0 for an empty mesh, -1 with "<who>: <n> cells" as the error
+// beyond INT32_MAX cells
+static inline int64_t ox_cell_blocks(const char *who, const ox_cells *cells) {
+  if (cells->n_cells <= 0) return 0;
+  if (cells->n_cells > (int64_t)0x7fffffff) {
+    snprintf(ox_err_buf, sizeof(ox_err_buf), "%s: %lld cells", who, (long long)cells->n_cells);
+    return -1;
+  }
+  return (cells->n_cells + 255) / 256;
+}

@@ -16,57 +16,24 @@
 // k_outlet_backflow: one lane per touched velocity row; the row's (facet, position of the row among the facet's dofs)
 // pairs in ascending facet id, the slots of A's value array from set-up.  The lane owns its row of A and of b_first: no
 // atomics, a fixed order of sums.
-#include "fe_tables_f.h"
-#include "fe_tables_o.h"
-#include "ox_kernels.h"
+#include "ox_element.h"
 
 namespace {
 
+// The facet rule of the backflow term: its size and tables, indexed at run time (constant memory).  The facet basis at
+// the rule's points is the same on every local facet (facet dofs and points both in ascending local vertex order).
 template <int GDIM, int DU>
 struct Outlet {
-  static_assert(DU >= 1 && DU <= 3, "P1, P2, P3");
-  static constexpr int ND = DU == 1 ? GDIM + 1 : (DU == 3 ? (GDIM == 2 ? 10 : 20) : (GDIM == 2 ? 6 : 10));
-  static constexpr int GS = GDIM == 2 ? 6 : 10;
   static constexpr int NP = DU == 1 ? 2 : (DU == 2 ? 4 : 5);
   static constexpr int NQ = GDIM == 2 ? NP : NP * NP;
   static constexpr int NFD = GDIM == 2 ? DU + 1 : (DU + 1) * (DU + 2) / 2;
-  __host__ __device__ static constexpr double mean(int a, int i) {
-    if constexpr (GDIM == 2 && DU == 1) return OX_PHIF2_1[a][i];
-    else if constexpr (GDIM == 2 && DU == 2) return OX_PHIF2_2[a][i];
-    else if constexpr (GDIM == 2) return OX_PHIF2_3[a][i];
-    else if constexpr (DU == 1) return OX_PHIF3_1[a][i];
-    else if constexpr (DU == 2) return OX_PHIF3_2[a][i];
-    else return OX_PHIF3_3[a][i];
-  }
-  // the facet rule's tables, indexed at run time (constant memory); the facet basis at the rule's points is the same on
-  // every local facet (facet dofs and points both in ascending local vertex order)
-  __device__ static double w(int q) {
-    if constexpr (GDIM == 2 && DU == 1) return OX_OW2_1[q];
-    else if constexpr (GDIM == 2 && DU == 2) return OX_OW2_2[q];
-    else if constexpr (GDIM == 2) return OX_OW2_3[q];
-    else if constexpr (DU == 1) return OX_OW3_1[q];
-    else if constexpr (DU == 2) return OX_OW3_2[q];
-    else return OX_OW3_3[q];
-  }
-  __device__ static double phi(int q, int j) {
-    if constexpr (GDIM == 2 && DU == 1) return OX_OPHI2_1[q][j];
-    else if constexpr (GDIM == 2 && DU == 2) return OX_OPHI2_2[q][j];
-    else if constexpr (GDIM == 2) return OX_OPHI2_3[q][j];
-    else if constexpr (DU == 1) return OX_OPHI3_1[q][j];
-    else if constexpr (DU == 2) return OX_OPHI3_2[q][j];
-    else return OX_OPHI3_3[q][j];
-  }
-  __device__ static int fd(int a, int j) {
-    if constexpr (GDIM == 2 && DU == 1) return OX_OFD2_1[a][j];
-    else if constexpr (GDIM == 2 && DU == 2) return OX_OFD2_2[a][j];
-    else if constexpr (GDIM == 2) return OX_OFD2_3[a][j];
-    else if constexpr (DU == 1) return OX_OFD3_1[a][j];
-    else if constexpr (DU == 2) return OX_OFD3_2[a][j];
-    else return OX_OFD3_3[a][j];
-  }
+  __device__ static double w(int q) { OX_FE_PICK(GDIM, DU, OX_OW, [q]); }
+  __device__ static double phi(int q, int j) { OX_FE_PICK(GDIM, DU, OX_OPHI, [q][j]); }
+  __device__ static int fd(int a, int j) { OX_FE_PICK(GDIM, DU, OX_OFD, [a][j]); }
 };
 
-// outward unit normal and measure of local facet a (0 <= a <= GDIM) from the cell's geometry record
+// outward unit normal and measure of local facet a (0 <= a <= GDIM) from the cell's geometry record: the one row
+// grad lambda_a is selected as the rows are read, no G[GDIM + 1][GDIM] is kept
 template <int GDIM>
 __device__ __forceinline__ void facet_geometry(const double *__restrict__ gp, int a, double (&n)[GDIM], double &area) {
   double Ga[GDIM];
@@ -81,34 +48,14 @@ __device__ __forceinline__ void facet_geometry(const double *__restrict__ gp, in
     }
     Ga[d] = a == 0 ? g0 : ga;
   }
-  double ga2 = 0.0;
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d) ga2 = fma(Ga[d], Ga[d], ga2);
-  const double gn = sqrt(ga2);
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d) n[d] = -Ga[d] / gn;
-  area = gp[GDIM * GDIM] * gn * (GDIM == 3 ? 0.5 : 1.0);
-}
-
-// ub[d] = sum_i u[dof_i][d] mean_f(phi_i) on local facet A, in dof order; dofs with a zero mean are not read
-template <int GDIM, int DU, int A>
-__device__ __forceinline__ void facet_mean_u(const int32_t *__restrict__ dv, const double *__restrict__ u,
-                                             double (&ub)[GDIM]) {
-  using O = Outlet<GDIM, DU>;
-#pragma unroll
-  for (int i = 0; i < O::ND; ++i)
-    if (O::mean(A, i) != 0.0) {
-      const size_t dof = (size_t)dv[i];
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d) ub[d] = fma(u[dof * GDIM + d], O::mean(A, i), ub[d]);
-    }
+  ox_facet_normal<GDIM>(Ga, ox_geom_adet<GDIM>(gp), n, area);
 }
 
 template <int GDIM, int DU>
 __global__ __launch_bounds__(256) void k_outlet_flux(ox_cells cells, const int32_t *__restrict__ vdofs, int64_t n_facets,
                                                      const int2 *__restrict__ rec, const double *__restrict__ u,
                                                      double *__restrict__ flux) {
-  using O = Outlet<GDIM, DU>;
+  constexpr int ND = ox_nd(GDIM, DU);
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= n_facets) return;
   const int2 r = rec[f];
@@ -118,17 +65,20 @@ __global__ __launch_bounds__(256) void k_outlet_flux(ox_cells cells, const int32
     return;
   }
   const int64_t e = r.x;
-  const int32_t *__restrict__ dv = vdofs + (size_t)e * O::ND;
-  double n[GDIM], area, ub[GDIM];
-  facet_geometry<GDIM>(cells.geom + (size_t)e * O::GS, r.y, n, area);
+  const int32_t *__restrict__ dv = vdofs + (size_t)e * ND;
+  double n[GDIM], area, ub[GDIM] = {};
+  facet_geometry<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), r.y, n, area);
+  // ub[d] = sum_i u[dof_i][d] mean_f(phi_i) on the local facet, in dof order; dofs with a zero mean are not read
+  ox_facet_dispatch<GDIM>(r.y, [&](auto facet) {
+    constexpr int A = decltype(facet)::value;
 #pragma unroll
-  for (int d = 0; d < GDIM; ++d) ub[d] = 0.0;
-  if (r.y == 0) facet_mean_u<GDIM, DU, 0>(dv, u, ub);
-  else if (r.y == 1) facet_mean_u<GDIM, DU, 1>(dv, u, ub);
-  else if (r.y == 2) facet_mean_u<GDIM, DU, 2>(dv, u, ub);
-  else {
-    if constexpr (GDIM == 3) facet_mean_u<GDIM, DU, 3>(dv, u, ub);
-  }
+    for (int i = 0; i < ND; ++i)
+      if (ox_phif<GDIM, DU>()[A][i] != 0.0) {
+        const size_t dof = (size_t)dv[i];
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) ub[d] = fma(u[dof * GDIM + d], ox_phif<GDIM, DU>()[A][i], ub[d]);
+      }
+  });
   double q = 0.0;
 #pragma unroll
   for (int d = 0; d < GDIM; ++d) q = fma(n[d], ub[d], q);
@@ -193,7 +143,7 @@ __global__ __launch_bounds__(256) void k_outlet_backflow(ox_cells cells, const i
                                                          double *__restrict__ avals, int64_t a_size,
                                                          double *__restrict__ b_first) {
   using O = Outlet<GDIM, DU>;
-  constexpr int NFD = O::NFD;
+  constexpr int ND = ox_nd(GDIM, DU), NFD = O::NFD;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_rows) return;
   double acc[GDIM];
@@ -208,13 +158,13 @@ __global__ __launch_bounds__(256) void k_outlet_backflow(ox_cells cells, const i
     const int64_t e = r.x;
     const int a = r.y;
     double n[GDIM], area;
-    facet_geometry<GDIM>(cells.geom + (size_t)e * O::GS, a, n, area);
+    facet_geometry<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), a, n, area);
     const double c = 0.5 * beta[fi] * area;
     size_t dvf[NFD];
     double un[NFD], ent[NFD];
 #pragma unroll
     for (int j = 0; j < NFD; ++j) {
-      dvf[j] = (size_t)vdofs[(size_t)e * O::ND + O::fd(a, j)];
+      dvf[j] = (size_t)vdofs[(size_t)e * ND + O::fd(a, j)];
       double s = 0.0;
 #pragma unroll
       for (int d = 0; d < GDIM; ++d) s = fma(uab[dvf[j] * GDIM + d], n[d], s);
@@ -245,8 +195,6 @@ __global__ __launch_bounds__(256) void k_outlet_backflow(ox_cells cells, const i
 
 }  // namespace
 
-#define OX_OUTLET_CASES(M) M(2, 1) M(2, 2) M(2, 3) M(3, 1) M(3, 2) M(3, 3)
-
 extern "C" int ox_outlet_flux(int u_degree, const ox_cells *cells, const int32_t *cell_vdofs, int64_t n_facets,
                               const int32_t *facet_rec, const double *u, double *flux, void *stream) {
   if (!cells || !cells->geom || !cell_vdofs || !facet_rec || !u || !flux) OX_FAIL("ox_outlet_flux: null argument");
@@ -265,7 +213,7 @@ extern "C" int ox_outlet_flux(int u_degree, const ox_cells *cells, const int32_t
     OX_LAUNCH_CHECK();                                                                                             \
     return 0;                                                                                                      \
   }
-  OX_OUTLET_CASES(OX_OUTLET_FLUX_CASE)
+  OX_FOR_GDIM_DEG(OX_OUTLET_FLUX_CASE)
 #undef OX_OUTLET_FLUX_CASE
   OX_FAIL("ox_outlet_flux: unsupported gdim=%d, P%d", g, u_degree);
 }
@@ -314,7 +262,7 @@ extern "C" int ox_outlet_backflow(int u_degree, const ox_cells *cells, const int
     OX_LAUNCH_CHECK();                                                                                                \
     return 0;                                                                                                         \
   }
-  OX_OUTLET_CASES(OX_OUTLET_BACK_CASE)
+  OX_FOR_GDIM_DEG(OX_OUTLET_BACK_CASE)
 #undef OX_OUTLET_BACK_CASE
   OX_FAIL("ox_outlet_backflow: unsupported gdim=%d, P%d", g, u_degree);
 }

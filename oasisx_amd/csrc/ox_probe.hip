@@ -13,7 +13,7 @@
 // spatial order of the mat-vecs: the lanes of a wave open neighbouring rows of the field): gather the cell's dof rows,
 // evaluate the basis in barycentric form (P1, P2, the gll_warped P3 element through its monomial coefficients in
 // __constant__ memory), accumulate in dof order, write out[perm[i]].  No atomics on doubles, no LDS, nothing read back.
-#include "ox_kernels.h"
+#include "ox_element.h"
 
 #define OX_P3_COEF_QUAL __constant__
 #include "fe_tables_eval.h"
@@ -340,13 +340,10 @@ __global__ __launch_bounds__(256) void k_loc_bary(int64_t n, const double *__res
 
 // ---------------------------------------------------------------------------------------------------------------------
 // evaluation
-__host__ __device__ constexpr int probe_nd(int d, int degree) {
-  return degree == 1 ? d + 1 : (degree == 2 ? (d + 1) * (d + 2) / 2 : (d == 2 ? 10 : 20));
-}
 
 // phi of the P1 / P2 element of fem.lagrange_basis at the barycentric point lam
 template <int D, int DEG>
-__device__ __forceinline__ void probe_basis(const double (&lam)[D + 1], double (&phi)[probe_nd(D, DEG)]) {
+__device__ __forceinline__ void probe_basis(const double (&lam)[D + 1], double (&phi)[ox_nd(D, DEG)]) {
   if constexpr (DEG == 1) {
 #pragma unroll
     for (int a = 0; a <= D; ++a) phi[a] = lam[a];
@@ -363,7 +360,7 @@ __device__ __forceinline__ void probe_basis(const double (&lam)[D + 1], double (
 }
 // the monomials of fem._p3_mono at lam: m_c = lambda_1^i lambda_2^j [lambda_3^k], exponents with i slowest
 template <int D>
-__device__ __forceinline__ void probe_mono3(const double (&lam)[D + 1], double (&m)[probe_nd(D, 3)]) {
+__device__ __forceinline__ void probe_mono3(const double (&lam)[D + 1], double (&m)[ox_nd(D, 3)]) {
   double p[D][4];
 #pragma unroll
   for (int v = 0; v < D; ++v) {
@@ -388,8 +385,8 @@ __device__ __forceinline__ void probe_mono3(const double (&lam)[D + 1], double (
 // phi_a of the gll_warped P3 element from the monomials: column a of the coefficient matrix (a uniform over the wave: the
 // coefficients arrive by scalar loads)
 template <int D>
-__device__ __forceinline__ double probe_phi3(const double (&m)[probe_nd(D, 3)], int a) {
-  constexpr int ND = probe_nd(D, 3);
+__device__ __forceinline__ double probe_phi3(const double (&m)[ox_nd(D, 3)], int a) {
+  constexpr int ND = ox_nd(D, 3);
   double s = 0.0;
 #pragma unroll
   for (int q = 0; q < ND; ++q) {
@@ -406,7 +403,7 @@ __global__ __launch_bounds__(256) void k_eval_points(int64_t n, const int32_t *_
                                                      const double *__restrict__ bary, const int64_t *__restrict__ perm,
                                                      const double *__restrict__ field, int nc, int col0, int nv,
                                                      double *__restrict__ out, int64_t ld) {
-  constexpr int ND = probe_nd(D, DEG);
+  constexpr int ND = ox_nd(D, DEG);
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int64_t dst = perm ? perm[i] : i;
@@ -515,7 +512,7 @@ __device__ __forceinline__ bool tracer_locate(const TracerParams &P, const doubl
 template <int D, int DEG>
 __device__ __forceinline__ bool tracer_velocity(const TracerParams &P, int64_t cell, const double (&lam)[D + 1], double theta,
                                                 double (&v)[D]) {
-  constexpr int ND = probe_nd(D, DEG);
+  constexpr int ND = ox_nd(D, DEG);
   const int64_t kp = P.cell_inv[cell];  // (cell is in [0, n_loc) = [0, n_mesh_cells): the caller's check)
   if (kp < 0 || kp >= P.n_cells) return false;
   double ua[D], ub[D];

@@ -16,27 +16,10 @@
 // One lane per cell, in kernel cell order: the cell's dof list (ND x 4 B) and geometry record (GS x 8 B) are streamed,
 // the ND x GDIM coefficients are gathered, 8 B are written.  The centroid derivatives are compile-time constants
 // (fe_tables_c.h): identically-zero entries cost nothing.  No atomics, no LDS; every sum has a fixed order.
-#include "fe_tables_c.h"
-#include "ox_kernels.h"
+#include "ox_element.h"
 #include <cmath>
-#include <type_traits>
 
 namespace {
-
-template <int GDIM, int DEG>
-struct Centroid {
-  static_assert(DEG >= 1 && DEG <= 3, "Lagrange degree 1, 2, 3");
-  static constexpr int ND = DEG == 1 ? GDIM + 1 : (DEG == 3 ? (GDIM == 2 ? 10 : 20) : (GDIM == 2 ? 6 : 10));
-  static constexpr int GS = GDIM == 2 ? 6 : 10;
-  __host__ __device__ static constexpr double dphi(int i, int b) {
-    if constexpr (GDIM == 2 && DEG == 1) return OX_DPHIC2_1[i][b];
-    else if constexpr (GDIM == 2 && DEG == 2) return OX_DPHIC2_2[i][b];
-    else if constexpr (GDIM == 2) return OX_DPHIC2_3[i][b];
-    else if constexpr (DEG == 1) return OX_DPHIC3_1[i][b];
-    else if constexpr (DEG == 2) return OX_DPHIC3_2[i][b];
-    else return OX_DPHIC3_3[i][b];
-  }
-};
 
 #define OX_NUT_SMAGORINSKY 0
 #define OX_NUT_WALE 1
@@ -57,64 +40,20 @@ template <int GDIM, int DEG, int MODEL>
 __global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const int32_t *__restrict__ cell_dofs,
                                                         const double *__restrict__ uab, NutArg<MODEL> coef2,
                                                         double *__restrict__ nut) {
-  using E = Centroid<GDIM, DEG>;
-  constexpr int ND = E::ND, GS = E::GS;
+  constexpr int ND = ox_nd(GDIM, DEG);
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= cells.n_cells) return;
   // round 1: the cell's dofs and geometry (both indexed by e); round 2: the coefficient gathers
   int32_t dd[ND];
-#pragma unroll
-  for (int i = 0; i < ND; ++i) dd[i] = cell_dofs[(size_t)e * ND + i];
-  const double *__restrict__ gp = cells.geom + (size_t)e * GS;
-  double G[GDIM + 1][GDIM];
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d) G[0][d] = 0.0;
-#pragma unroll
-  for (int a = 1; a <= GDIM; ++a)
-#pragma unroll
-    for (int d = 0; d < GDIM; ++d) {
-      G[a][d] = gp[(a - 1) * GDIM + d];
-      G[0][d] -= G[a][d];
-    }
-  const double adet = gp[GDIM * GDIM];
+  ox_load_dofs<ND>(cell_dofs, e, dd);
+  double G[GDIM + 1][GDIM], adet;
+  ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
   double uc[ND][GDIM];
-#pragma unroll
-  for (int i = 0; i < ND; ++i)
-#pragma unroll
-    for (int d = 0; d < GDIM; ++d) uc[i][d] = uab[(size_t)dd[i] * GDIM + d];
-  // t[d][b] = sum_i u_i[d] dphi_i/dlambda_b, in dof order
-  double t[GDIM][GDIM + 1];
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d)
-#pragma unroll
-    for (int b = 0; b <= GDIM; ++b) t[d][b] = 0.0;
-#pragma unroll
-  for (int i = 0; i < ND; ++i)
-#pragma unroll
-    for (int b = 0; b <= GDIM; ++b)
-      if (E::dphi(i, b) != 0.0) {
-#pragma unroll
-        for (int d = 0; d < GDIM; ++d) t[d][b] = fma(uc[i][d], E::dphi(i, b), t[d][b]);
-      }
-  // g[d][k] = sum_b t[d][b] G[b][k]
-  double g[GDIM][GDIM];
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d)
-#pragma unroll
-    for (int k = 0; k < GDIM; ++k) {
-      double v = 0.0;
-#pragma unroll
-      for (int b = 0; b <= GDIM; ++b) v = fma(t[d][b], G[b][k], v);
-      g[d][k] = v;
-    }
-  double ss = 0.0;  // S:S
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d)
-#pragma unroll
-    for (int k = 0; k < GDIM; ++k) {
-      const double s = 0.5 * (g[d][k] + g[k][d]);
-      ss = fma(s, s, ss);
-    }
+  ox_gather<ND, GDIM>(dd, uab, uc);
+  double t[GDIM][GDIM + 1] = {}, g[GDIM][GDIM];
+  ox_contract<GDIM, ND>(uc, ox_dphic<GDIM, DEG>(), t);
+  ox_grad_from_t<GDIM>(t, G, g);
+  const double ss = ox_sym_sq<GDIM>(g);
   // Delta^2 = |cell|^(2/gdim)
   double delta2;
   if constexpr (GDIM == 2) delta2 = 0.5 * adet;
@@ -174,11 +113,10 @@ extern "C" int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, c
                                  double coefficient, double *nut, void *stream) {
   if (!cells || !cell_dofs || !uab || !nut || !cells->geom) OX_FAIL("ox_eddy_viscosity: null argument");
   if (!(coefficient >= 0.0)) OX_FAIL("ox_eddy_viscosity: coefficient=%g", coefficient);
-  if (cells->n_cells <= 0) return 0;
-  if (cells->n_cells > (int64_t)0x7fffffff) OX_FAIL("ox_eddy_viscosity: %lld cells", (long long)cells->n_cells);
+  const int64_t nblk = ox_cell_blocks("ox_eddy_viscosity", cells);
+  if (nblk <= 0) return (int)nblk;
   hipStream_t st = ox_stream(stream);
   const int g = cells->gdim;
-  const unsigned nblk = (unsigned)((cells->n_cells + 255) / 256);
   const double c2 = coefficient * coefficient;
   if (model == OX_NUT_WALE && g != 3) OX_FAIL("ox_eddy_viscosity: WALE is built for gdim = 3 (got %d)", g);
   if (model != OX_NUT_SMAGORINSKY && model != OX_NUT_WALE) OX_FAIL("ox_eddy_viscosity: model=%d", model);
@@ -190,9 +128,8 @@ extern "C" int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, c
     OX_LAUNCH_CHECK();                                                                                                 \
     return 0;                                                                                                          \
   }
-  OX_NUT_CASE(2, 1, 0) OX_NUT_CASE(2, 2, 0) OX_NUT_CASE(2, 3, 0)
-  OX_NUT_CASE(3, 1, 0) OX_NUT_CASE(3, 2, 0) OX_NUT_CASE(3, 3, 0)
-  OX_NUT_CASE(3, 1, 1) OX_NUT_CASE(3, 2, 1) OX_NUT_CASE(3, 3, 1)
+  OX_FOR_GDIM_DEG(OX_NUT_CASE, OX_NUT_SMAGORINSKY)
+  OX_NUT_CASE(3, 1, OX_NUT_WALE) OX_NUT_CASE(3, 2, OX_NUT_WALE) OX_NUT_CASE(3, 3, OX_NUT_WALE)
 #undef OX_NUT_CASE
   OX_FAIL("ox_eddy_viscosity: unsupported gdim=%d degree=%d", g, degree);
 }
@@ -226,11 +163,10 @@ extern "C" int ox_viscosity_law(int law, int degree, const ox_cells *cells, cons
       P.c3 = e;
     }
   }
-  if (cells->n_cells <= 0) return 0;
-  if (cells->n_cells > (int64_t)0x7fffffff) OX_FAIL("ox_viscosity_law: %lld cells", (long long)cells->n_cells);
+  const int64_t nblk = ox_cell_blocks("ox_viscosity_law", cells);
+  if (nblk <= 0) return (int)nblk;
   hipStream_t st = ox_stream(stream);
   const int g = cells->gdim;
-  const unsigned nblk = (unsigned)((cells->n_cells + 255) / 256);
 #define OX_LAW_CASE(GD, DG, MD)                                                                                       \
   if (g == GD && degree == DG && law == MD) {                                                                         \
     if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                         \
@@ -239,10 +175,9 @@ extern "C" int ox_viscosity_law(int law, int degree, const ox_cells *cells, cons
     OX_LAUNCH_CHECK();                                                                                                \
     return 0;                                                                                                         \
   }
-#define OX_LAW_ALL(MD) \
-  OX_LAW_CASE(2, 1, MD) OX_LAW_CASE(2, 2, MD) OX_LAW_CASE(2, 3, MD) OX_LAW_CASE(3, 1, MD) OX_LAW_CASE(3, 2, MD) OX_LAW_CASE(3, 3, MD)
-  OX_LAW_ALL(2) OX_LAW_ALL(3) OX_LAW_ALL(4)
-#undef OX_LAW_ALL
+  OX_FOR_GDIM_DEG(OX_LAW_CASE, OX_NUT_CARREAU_YASUDA)
+  OX_FOR_GDIM_DEG(OX_LAW_CASE, OX_NUT_CROSS)
+  OX_FOR_GDIM_DEG(OX_LAW_CASE, OX_NUT_POWER_LAW)
 #undef OX_LAW_CASE
   OX_FAIL("ox_viscosity_law: unsupported gdim=%d degree=%d", g, degree);
 }

@@ -16,50 +16,14 @@
 // local facet selects one of GDIM + 1 instantiations of the contraction.  No atomics; every sum has a fixed order.
 // k_wall_forces: one block per tag sums its contiguous segment of |f| t (lane-strided partial sums in ascending facet
 // order, then the fixed tree of ox_block_sum_256) and writes -rho sum into slot k of a ring (capacity, n_tags, gdim).
-#include "fe_tables_f.h"
-#include "ox_kernels.h"
+#include "ox_element.h"
 
 namespace {
 
-template <int GDIM, int DU, int DP>
-struct Wall {
-  static_assert(DU >= 1 && DU <= 3 && DP >= 1 && DP <= 2, "P1-P1, P2-P1, P3-P2");
-  static constexpr int nd_of(int deg) { return deg == 1 ? GDIM + 1 : (deg == 3 ? (GDIM == 2 ? 10 : 20) : (GDIM == 2 ? 6 : 10)); }
-  static constexpr int ND = nd_of(DU), NDQ = nd_of(DP);
-  static constexpr int GS = GDIM == 2 ? 6 : 10;
-  __host__ __device__ static constexpr double dphi(int a, int i, int b) {
-    if constexpr (GDIM == 2 && DU == 1) return OX_DPHIF2_1[a][i][b];
-    else if constexpr (GDIM == 2 && DU == 2) return OX_DPHIF2_2[a][i][b];
-    else if constexpr (GDIM == 2) return OX_DPHIF2_3[a][i][b];
-    else if constexpr (DU == 1) return OX_DPHIF3_1[a][i][b];
-    else if constexpr (DU == 2) return OX_DPHIF3_2[a][i][b];
-    else return OX_DPHIF3_3[a][i][b];
-  }
-  __host__ __device__ static constexpr double psi(int a, int j) {
-    if constexpr (GDIM == 2 && DP == 1) return OX_PHIF2_1[a][j];
-    else if constexpr (GDIM == 2) return OX_PHIF2_2[a][j];
-    else if constexpr (DP == 1) return OX_PHIF3_1[a][j];
-    else return OX_PHIF3_2[a][j];
-  }
-};
-
-// tb[d][b] = sum_i u_i[d] mean_f(dphi_i/dlambda_b) and pbar = sum_j p_j mean_f(psi_j) on local facet A, in dof order
-template <int GDIM, int DU, int DP, int A>
-__device__ __forceinline__ void facet_means(const double (&uc)[Wall<GDIM, DU, DP>::ND][GDIM],
-                                            const double (&pc)[Wall<GDIM, DU, DP>::NDQ], double (&tb)[GDIM][GDIM + 1],
-                                            double &pbar) {
-  using W = Wall<GDIM, DU, DP>;
-#pragma unroll
-  for (int i = 0; i < W::ND; ++i)
-#pragma unroll
-    for (int b = 0; b <= GDIM; ++b)
-      if (W::dphi(A, i, b) != 0.0) {
-#pragma unroll
-        for (int d = 0; d < GDIM; ++d) tb[d][b] = fma(uc[i][d], W::dphi(A, i, b), tb[d][b]);
-      }
-#pragma unroll
-  for (int j = 0; j < W::NDQ; ++j)
-    if (W::psi(A, j) != 0.0) pbar = fma(pc[j], W::psi(A, j), pbar);
+// facet means of dphi_i/dlambda_b, [a][i][b]
+template <int GDIM, int DEG>
+__host__ __device__ constexpr const auto &dphif() {
+  OX_FE_PICK(GDIM, DEG, OX_DPHIF, );
 }
 
 #define OX_WALL_NS 5  // rows staged per block: t, wss, |f| t, weight wss, weight t
@@ -73,8 +37,7 @@ __global__ __launch_bounds__(256) void k_wall_stress(ox_cells cells, const int32
                                                      double *__restrict__ out_wss, double *__restrict__ out_ft,
                                                      double *__restrict__ acc_vec, double *__restrict__ acc_mag,
                                                      double *__restrict__ acc_t) {
-  using W = Wall<GDIM, DU, DP>;
-  constexpr int ND = W::ND, NDQ = W::NDQ, GS = W::GS;
+  constexpr int ND = ox_nd(GDIM, DU), NDQ = ox_nd(GDIM, DP);
   __shared__ double lds[OX_WALL_NS][256 * GDIM];
   const int64_t f0 = (int64_t)blockIdx.x * 256;
   const int64_t f = f0 + threadIdx.x;
@@ -93,76 +56,29 @@ __global__ __launch_bounds__(256) void k_wall_stress(ox_cells cells, const int32
       const int64_t e = r.x;
       const int a = r.y;
       int32_t dv[ND], dq[NDQ];
-#pragma unroll
-      for (int i = 0; i < ND; ++i) dv[i] = vdofs[(size_t)e * ND + i];
-#pragma unroll
-      for (int j = 0; j < NDQ; ++j) dq[j] = qdofs[(size_t)e * NDQ + j];
-      const double *__restrict__ gp = cells.geom + (size_t)e * GS;
-      double G[GDIM + 1][GDIM];
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d) G[0][d] = 0.0;
-#pragma unroll
-      for (int b = 1; b <= GDIM; ++b)
-#pragma unroll
-        for (int d = 0; d < GDIM; ++d) {
-          G[b][d] = gp[(b - 1) * GDIM + d];
-          G[0][d] -= G[b][d];
-        }
-      const double adet = gp[GDIM * GDIM];
+      ox_load_dofs<ND>(vdofs, e, dv);
+      ox_load_dofs<NDQ>(qdofs, e, dq);
+      double G[GDIM + 1][GDIM], adet;
+      ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
       const double nu_eff = nut ? nu + nut[e] : nu;
-      double uc[ND][GDIM], pc[NDQ];
+      double uc[ND][GDIM], pc[NDQ][1];
+      ox_gather<ND, GDIM>(dv, u, uc);
+      ox_gather<NDQ, 1>(dq, p, pc);
+      // tb[d][b] = sum_i u_i[d] mean_f(dphi_i/dlambda_b) and pbar = sum_j p_j mean_f(psi_j) on the local facet, in dof
+      // order; Ga = grad lambda_a
+      double tb[GDIM][GDIM + 1] = {}, pbar = 0.0, Ga[GDIM] = {};
+      ox_facet_dispatch<GDIM>(a, [&](auto facet) {
+        constexpr int A = decltype(facet)::value;
+        ox_contract<GDIM, ND>(uc, dphif<GDIM, DU>()[A], tb);
 #pragma unroll
-      for (int i = 0; i < ND; ++i)
+        for (int j = 0; j < NDQ; ++j)
+          if (ox_phif<GDIM, DP>()[A][j] != 0.0) pbar = fma(pc[j][0], ox_phif<GDIM, DP>()[A][j], pbar);
 #pragma unroll
-        for (int d = 0; d < GDIM; ++d) uc[i][d] = u[(size_t)dv[i] * GDIM + d];
-#pragma unroll
-      for (int j = 0; j < NDQ; ++j) pc[j] = p[dq[j]];
-      double tb[GDIM][GDIM + 1], pbar = 0.0;
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d)
-#pragma unroll
-        for (int b = 0; b <= GDIM; ++b) tb[d][b] = 0.0;
-      double Ga[GDIM];
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d) Ga[d] = 0.0;
-      if (a == 0) {
-        facet_means<GDIM, DU, DP, 0>(uc, pc, tb, pbar);
-#pragma unroll
-        for (int d = 0; d < GDIM; ++d) Ga[d] = G[0][d];
-      } else if (a == 1) {
-        facet_means<GDIM, DU, DP, 1>(uc, pc, tb, pbar);
-#pragma unroll
-        for (int d = 0; d < GDIM; ++d) Ga[d] = G[1][d];
-      } else if (a == 2) {
-        facet_means<GDIM, DU, DP, 2>(uc, pc, tb, pbar);
-#pragma unroll
-        for (int d = 0; d < GDIM; ++d) Ga[d] = G[2][d];
-      } else {
-        if constexpr (GDIM == 3) {
-          facet_means<GDIM, DU, DP, 3>(uc, pc, tb, pbar);
-#pragma unroll
-          for (int d = 0; d < GDIM; ++d) Ga[d] = G[3][d];
-        }
-      }
-      // gbar[d][k] = sum_b tb[d][b] G[b][k]
-      double g[GDIM][GDIM];
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d)
-#pragma unroll
-        for (int k = 0; k < GDIM; ++k) {
-          double v = 0.0;
-#pragma unroll
-          for (int b = 0; b <= GDIM; ++b) v = fma(tb[d][b], G[b][k], v);
-          g[d][k] = v;
-        }
-      double ga2 = 0.0;
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d) ga2 = fma(Ga[d], Ga[d], ga2);
-      const double ga = sqrt(ga2);
-      double n[GDIM];
-#pragma unroll
-      for (int d = 0; d < GDIM; ++d) n[d] = -Ga[d] / ga;
-      const double area = adet * ga * (GDIM == 3 ? 0.5 : 1.0);
+        for (int d = 0; d < GDIM; ++d) Ga[d] = G[A][d];
+      });
+      double g[GDIM][GDIM], n[GDIM], area;
+      ox_grad_from_t<GDIM>(tb, G, g);
+      ox_facet_normal<GDIM>(Ga, adet, n, area);
       double tn = 0.0;
 #pragma unroll
       for (int d = 0; d < GDIM; ++d) {
@@ -251,18 +167,18 @@ extern "C" int ox_wall_stress(int u_degree, int p_degree, const ox_cells *cells,
   hipStream_t st = ox_stream(stream);
   const int g = cells->gdim;
   const unsigned nblk = (unsigned)((n_facets + 255) / 256);
-#define OX_WALL_CASE(GD, DU, DP)                                                                                        \
-  if (g == GD && u_degree == DU && p_degree == DP) {                                                                    \
+  // P1-P1, P2-P1, P3-P2: the pressure degree follows from the velocity's
+#define OX_WALL_CASE(GD, DU)                                                                                            \
+  if (g == GD && u_degree == DU && p_degree == (DU == 3 ? 2 : 1)) {                                                     \
     if (ox_prof_on) ox_prof_start(OX_TAG_WALL_STRESS, st, n_facets);                                                    \
-    hipLaunchKernelGGL((k_wall_stress<GD, DU, DP>), dim3(nblk), dim3(256), 0, st, *cells, cell_vdofs, cell_qdofs,       \
-                       n_facets, reinterpret_cast<const int2 *>(facet_rec), u, p, nut, nu, weight, t, wss, ft, acc_vec, \
-                       acc_mag, acc_t);                                                                                 \
+    hipLaunchKernelGGL((k_wall_stress<GD, DU, (DU == 3 ? 2 : 1)>), dim3(nblk), dim3(256), 0, st, *cells, cell_vdofs,    \
+                       cell_qdofs, n_facets, reinterpret_cast<const int2 *>(facet_rec), u, p, nut, nu, weight, t, wss,  \
+                       ft, acc_vec, acc_mag, acc_t);                                                                    \
     if (ox_prof_on) ox_prof_stop(st);                                                                                   \
     OX_LAUNCH_CHECK();                                                                                                  \
     return 0;                                                                                                           \
   }
-  OX_WALL_CASE(2, 1, 1) OX_WALL_CASE(2, 2, 1) OX_WALL_CASE(2, 3, 2)
-  OX_WALL_CASE(3, 1, 1) OX_WALL_CASE(3, 2, 1) OX_WALL_CASE(3, 3, 2)
+  OX_FOR_GDIM_DEG(OX_WALL_CASE)
 #undef OX_WALL_CASE
   OX_FAIL("ox_wall_stress: unsupported gdim=%d, P%d-P%d", g, u_degree, p_degree);
 }
