@@ -765,6 +765,33 @@ int ox_tracer_advance(const ox_tracer_args *args, void *stream);
 int ox_scalar_rows(const ox_sell *A, const ox_sell *M, const ox_sell *K, const ox_sell *Ac, double s, double dt, int ncomp,
                    const double *c1, const double *b0, double *b, double *a_c1, void *stream);
 
+/* ---- Scalars that drive the flow, scalar fluxes through walls (ox_scalar.hip) ------------------
+ * Boussinesq force of 1..OX_MAXC coupled scalars onto the interleaved (n, gdim) block b (b_first of the velocity step), in
+ * ONE pass over the mass matrix M.  Term t reads column col of the interleaved (n, nc) blocks c1, c2 (terms may come from
+ * different groups: nc and col are per term; c2 == NULL: no second level):
+ *   d_t[j] = (c1[j nc + col] + 0.5 (c1[j nc + col] - c2[j nc + col])) - ref          (c2 == NULL: c1[j nc + col] - ref)
+ *   y_t[r] = sum_e M[r,e] d_t[col_e]     stored entry order, from 0, one fused multiply-add per entry (ox_spmv's operations)
+ *   b[r gdim + i] += sum_t coef[t][i] y_t[r], terms ascending, rows < n_rows.
+ * A component i whose coefficients are all zero is neither read nor written.  M is read through its 1-byte value codes
+ * where it carries a dictionary, as f64 otherwise.  `terms` is a HOST array (copied into the kernel arguments).  No
+ * atomics, a fixed order: two runs give the same bits. */
+typedef struct {
+  const double *c1, *c2;
+  int32_t nc, col;
+  double ref;
+  double coef[3];
+} ox_buoy_term;
+int ox_buoyancy_rows(const ox_sell *M, int gdim, int n_terms, const ox_buoy_term *terms, double *b, void *stream);
+/* Diffusive flux of column col of the interleaved (n, nc) block c through exterior facets; facets and records as for
+ * ox_wall_stress (sorted by tag; a record outside the tables leaves NaN).  With the outward unit normal n, the measure
+ * |f| and the exact facet means gbar of grad c and cbar of c (compile-time facet means of the P1 / P2 / P3 basis):
+ *   q[i] = -kappa n . gbar   (a positive q leaves the domain),   fq[i] = |f| q[i],   cbar[i];   device [n_facets] each.
+ * weight > 0: acc_q += weight q in the same launch.  cell_dofs: the table of c's space in kernel cell order.  One lane per
+ * facet, no atomics.  The per-tag sums of fq: ox_outlet_update(..., params = NULL). */
+int ox_scalar_flux(int degree, const ox_cells *cells, const int32_t *cell_dofs, int64_t n_facets, const int32_t *facet_rec,
+                   const double *c, int nc, int col, double kappa, double weight, double *q, double *fq, double *cbar,
+                   double *acc_q, void *stream);
+
 /* ---- Wall shear stress, traction and boundary forces on exterior facets (ox_wall.hip) ----------
  * Facet i -- the caller passes the facets SORTED by tag -- belongs to the cell at kernel position facet_rec[2 i] and lies
  * opposite that cell's local vertex facet_rec[2 i + 1] (a record outside the tables reads nothing and leaves NaN).  With

@@ -13,7 +13,7 @@ from .function import Projector
 from .geometry import Probes  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
-from .scalar import ScalarTransport
+from .scalar import ScalarFlux, ScalarTransport
 from .tracers import Tracers
 from .viscosity import CarreauYasuda, CellViscosity, Cross, PowerLaw, Smagorinsky, Wale
 from .wall import WallStress
@@ -29,6 +29,7 @@ __all__ = [
     "LocatorMethod",
     "PressureBC",
     "ScalarTransport",
+    "ScalarFlux",
     "Smagorinsky",
     "Wale",
     "CellViscosity",

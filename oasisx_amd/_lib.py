@@ -246,6 +246,19 @@ class ox_tracer_args(C.Structure):
     ]
 
 
+class ox_buoy_term(C.Structure):
+    _fields_ = [
+        ("c1", C.c_void_p),
+        ("c2", C.c_void_p),
+        ("nc", C.c_int32),
+        ("col", C.c_int32),
+        ("ref", C.c_double),
+        ("coef", C.c_double * 3),
+    ]
+
+
+PROF_TAG_BUOYANCY_ROWS = 190  # OX_TAG_BUOYANCY_ROWS of csrc/ox_kernels.h (ox_profile_get: key = 2 x terms + dictionary)
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -347,6 +360,8 @@ SIGNATURES = {
     "ox_tracer_advance": (_I, [C.POINTER(ox_tracer_args), _P]),
     "ox_scalar_rows": (_I, [C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _D, _D, _I,
                             _P, _P, _P, _P, _P]),
+    "ox_buoyancy_rows": (_I, [C.POINTER(ox_sell), _I, _I, C.POINTER(ox_buoy_term), _P, _P]),
+    "ox_scalar_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
     "ox_wall_stress": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _L, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
     "ox_wall_forces": (_I, [_I, _I, _P, _P, _D, _P, _L, _L, _P]),
     "ox_outlet_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P]),

@@ -28,10 +28,15 @@ static_assert(ox_nd(3, 1) == 4 && ox_nd(3, 2) == 10 && ox_nd(3, 3) == 20, "P1, P
   else if constexpr (DEG == 2) return STEM##3_2 IDX;                                                     \
   else return STEM##3_3 IDX
 
-// dphi_i/dlambda_b at the centroid [i][b] and the facet means of the basis [a][i] (compile-time constants)
+// dphi_i/dlambda_b at the centroid [i][b], its facet means [a][i][b] and the facet means of the basis [a][i]
+// (compile-time constants)
 template <int GDIM, int DEG>
 __host__ __device__ constexpr const auto &ox_dphic() {
   OX_FE_PICK(GDIM, DEG, OX_DPHIC, );
+}
+template <int GDIM, int DEG>
+__host__ __device__ constexpr const auto &ox_dphif() {
+  OX_FE_PICK(GDIM, DEG, OX_DPHIF, );
 }
 template <int GDIM, int DEG>
 __host__ __device__ constexpr const auto &ox_phif() {

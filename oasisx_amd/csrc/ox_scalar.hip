@@ -12,7 +12,12 @@
 // summed in the stored entry order with one fused multiply-add per entry, from 0 -- the operations of k_spmv -- so the
 // optional a_c1 = A_c c_1 equals ox_spmv(A_c, c_1) bit for bit and may be handed to the solver as its first mat-vec.
 // No atomics, fixed order: two runs give the same bits.  Padding slots hold 0 in A and K and stay 0.
-#include "ox_common.h"
+//
+// Scalars that drive the flow and the flux through walls:
+//   k_buoyancy_rows   b_first[r][i] += sum_t coef_t[i] (M d_t)[r],  d_t = (c1 + 0.5 (c1 - c2)) - ref of up to OX_MAXC
+//                     coupled scalars, in one pass over M in the launch shape of k_scalar_rows
+//   k_scalar_flux     q = -kappa n . gbar(c) on tagged exterior facets, one lane per facet as k_wall_stress
+#include "ox_element.h"
 
 namespace {
 
@@ -122,6 +127,173 @@ int launch(const ox_sell *A, const ox_sell *M, const ox_sell *K, double *acv, do
   return 0;
 }
 
+// ---- Boussinesq force ---------------------------------------------------------------------------------------------------
+// The terms of one launch, by value in the kernel arguments: after unrolling every index into the table is a
+// compile-time constant, so it stays in scalar registers (no scratch).
+template <int NT>
+struct BuoyTerms {
+  ox_buoy_term t[NT];
+};
+
+// d_t[j]: the midpoint value c1 + 0.5 (c1 - c2) (c1 itself without a second level) minus the reference.  c1 == c2 gives
+// c1 exactly, c == ref gives 0 exactly.
+__device__ __forceinline__ double buoy_d(const ox_buoy_term &t, int j) {
+  const size_t k = (size_t)j * t.nc + t.col;
+  const double a = t.c1[k];
+  const double e = t.c2 ? a + 0.5 * (a - t.c2[k]) : a;
+  return e - t.ref;
+}
+
+// Launch shape of k_scalar_rows: one wave per slice (lane = row), 4 slices per block, the blocks of an XCD on contiguous
+// slices.  Streamed per entry pair: 2 B of value codes (16 B of f64 values without a dictionary) and 8 B of columns;
+// gathered: c1 and c2 of every term at the entry's column -- the terms of one scalar group read one (nc x 8 B) row of the
+// group's blocks.  y_t = (M d_t)[row] is summed in the stored entry order with one fused multiply-add per entry, from 0:
+// the operations of k_spmv on the vector d_t.  live: bit i set where component i has a nonzero coefficient; the others
+// are neither read nor written.
+template <int NT, bool DICT>
+__global__ __launch_bounds__(256) void k_buoyancy_rows(ox_sell M, BuoyTerms<NT> T, int gdim, int live,
+                                                       double *__restrict__ b) {
+  __shared__ double dM[DICT ? 256 : 1];
+  if constexpr (DICT) {
+    if ((int)threadIdx.x < M.n_dict) dM[threadIdx.x] = M.vdict[threadIdx.x];
+    __syncthreads();
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int li = ox_xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
+  if (li >= M.n_slices) return;
+  const int slice = __builtin_amdgcn_readfirstlane(li);
+  const int64_t row = (int64_t)slice * 64 + lane;
+  const int64_t base = M.slice_ptr[slice];
+  const int npair = (int)((M.slice_ptr[slice + 1] - base) >> 7);
+  const v2d *__restrict__ mv = reinterpret_cast<const v2d *>(M.vals + base) + lane;
+  const v2i *__restrict__ cp = reinterpret_cast<const v2i *>(M.cols + base) + lane;
+  const unsigned short *__restrict__ mc = DICT ? reinterpret_cast<const unsigned short *>(M.vcode + base) + lane : nullptr;
+  double y[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) y[t] = 0.0;
+  constexpr int EU = 4;  // entry pairs per turn: streams -> gathers -> arithmetic in the stored order, as k_scalar_rows
+  for (int k0 = 0; k0 < npair; k0 += EU) {
+    v2d m[EU];
+    v2i col[EU];
+#pragma unroll
+    for (int q = 0; q < EU; ++q) {
+      const int k = min(k0 + q, npair - 1);  // unconditional loads inside the slice; the surplus is not used
+      if constexpr (DICT) {
+        const unsigned cm = __builtin_nontemporal_load(mc + (size_t)k * 64);
+        m[q].x = dM[cm & 0xff], m[q].y = dM[cm >> 8];
+      } else {
+        m[q] = __builtin_nontemporal_load(mv + (size_t)k * 64);
+      }
+      col[q] = __builtin_nontemporal_load(cp + (size_t)k * 64);
+    }
+    double d0[EU][NT], d1[EU][NT];
+#pragma unroll
+    for (int q = 0; q < EU; ++q)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        d0[q][t] = buoy_d(T.t[t], col[q].x);
+        d1[q][t] = buoy_d(T.t[t], col[q].y);
+      }
+#pragma unroll
+    for (int q = 0; q < EU; ++q)
+      if (k0 + q < npair) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) y[t] = fma(m[q].y, d1[q][t], fma(m[q].x, d0[q][t], y[t]));
+      }
+  }
+  if (row < M.n_rows) {
+#pragma unroll
+    for (int i = 0; i < OX_MAXC; ++i)
+      if (i < gdim && ((live >> i) & 1)) {
+        double s = T.t[0].coef[i] * y[0];
+#pragma unroll
+        for (int t = 1; t < NT; ++t) s = fma(T.t[t].coef[i], y[t], s);  // terms ascending
+        b[row * gdim + i] += s;
+      }
+  }
+}
+
+template <int NT>
+int launch_buoyancy(const ox_sell *M, int gdim, const ox_buoy_term *terms, double *b, hipStream_t st) {
+  BuoyTerms<NT> T;
+  int live = 0;
+  for (int t = 0; t < NT; ++t) {
+    T.t[t] = terms[t];
+    for (int i = 0; i < gdim; ++i)
+      if (terms[t].coef[i] != 0.0) live |= 1 << i;
+  }
+  if (!live) return 0;  // nothing to add to any component
+  const bool dict = M->vcode && M->vdict && M->n_dict > 0 && M->n_dict <= 256;
+  const unsigned nblk = (unsigned)((M->n_slices + 3) / 4);
+  if (ox_prof_on) ox_prof_start(OX_TAG_BUOYANCY_ROWS, st, 2 * NT + (dict ? 1 : 0));
+  if (dict) hipLaunchKernelGGL((k_buoyancy_rows<NT, true>), dim3(nblk), dim3(256), 0, st, *M, T, gdim, live, b);
+  else hipLaunchKernelGGL((k_buoyancy_rows<NT, false>), dim3(nblk), dim3(256), 0, st, *M, T, gdim, live, b);
+  if (ox_prof_on) ox_prof_stop(st);
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- diffusive flux through exterior facets -----------------------------------------------------------------------------
+// One lane per facet, records as for k_wall_stress.  Streamed: the record (8 B) and the three results (and, with
+// weight > 0, the read-modify-write of the accumulator); gathered: the cell's dof list, geometry record and ND values of
+// column col of c.  The facet means of the basis and of its gradient are compile-time constants: identically-zero
+// entries cost nothing; the local facet selects one of GDIM + 1 instantiations of the contraction.
+template <int GDIM, int DEG>
+__global__ __launch_bounds__(256) void k_scalar_flux(ox_cells cells, const int32_t *__restrict__ dofs, int64_t n_facets,
+                                                     const int2 *__restrict__ rec, const double *__restrict__ c, int nc,
+                                                     int col, double kappa, double weight, double *__restrict__ q,
+                                                     double *__restrict__ fq, double *__restrict__ cbar,
+                                                     double *__restrict__ acc_q) {
+  constexpr int ND = ox_nd(GDIM, DEG);
+  const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (f >= n_facets) return;
+  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+  double qv = qnan, fv = qnan, cb = qnan;
+  const int2 r = rec[f];
+  // a record outside the tables reads nothing and leaves NaN
+  if (r.x >= 0 && (int64_t)r.x < cells.n_cells && r.y >= 0 && r.y <= GDIM) {
+    const int64_t e = r.x;
+    int32_t dd[ND];
+    ox_load_dofs<ND>(dofs, e, dd);
+    double G[GDIM + 1][GDIM], adet;
+    ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
+    double cc[ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) cc[i] = c[(size_t)dd[i] * nc + col];
+    // tb[b] = sum_i c_i mean_f(dphi_i/dlambda_b) and the mean of c on the local facet, in dof order; Ga = grad lambda_a
+    double tb[GDIM + 1] = {}, mean = 0.0, Ga[GDIM] = {};
+    ox_facet_dispatch<GDIM>(r.y, [&](auto facet) {
+      constexpr int A = decltype(facet)::value;
+#pragma unroll
+      for (int i = 0; i < ND; ++i) {
+#pragma unroll
+        for (int bb = 0; bb <= GDIM; ++bb)
+          if (ox_dphif<GDIM, DEG>()[A][i][bb] != 0.0) tb[bb] = fma(cc[i], ox_dphif<GDIM, DEG>()[A][i][bb], tb[bb]);
+        if (ox_phif<GDIM, DEG>()[A][i] != 0.0) mean = fma(cc[i], ox_phif<GDIM, DEG>()[A][i], mean);
+      }
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d) Ga[d] = G[A][d];
+    });
+    double n[GDIM], area;
+    ox_facet_normal<GDIM>(Ga, adet, n, area);
+    double gn = 0.0;  // n . gbar, gbar[k] = sum_b tb[b] G[b][k]
+#pragma unroll
+    for (int k = 0; k < GDIM; ++k) {
+      double g = 0.0;
+#pragma unroll
+      for (int bb = 0; bb <= GDIM; ++bb) g = fma(tb[bb], G[bb][k], g);
+      gn = fma(n[k], g, gn);
+    }
+    qv = -kappa * gn;
+    fv = area * qv;
+    cb = mean;
+  }
+  q[f] = qv;
+  fq[f] = fv;
+  cbar[f] = cb;
+  if (weight > 0.0) acc_q[f] = __dadd_rn(acc_q[f], __dmul_rn(weight, qv));
+}
+
 }  // namespace
 
 extern "C" int ox_scalar_rows(const ox_sell *A, const ox_sell *M, const ox_sell *K, const ox_sell *Ac, double s, double dt,
@@ -141,4 +313,50 @@ extern "C" int ox_scalar_rows(const ox_sell *A, const ox_sell *M, const ox_sell 
     case 2: return launch<2>(A, M, K, Ac->vals, s, dt, c1, b0, b, a_c1, st);
     default: return launch<3>(A, M, K, Ac->vals, s, dt, c1, b0, b, a_c1, st);
   }
+}
+
+extern "C" int ox_buoyancy_rows(const ox_sell *M, int gdim, int n_terms, const ox_buoy_term *terms, double *b,
+                                void *stream) {
+  if (!M || !M->vals || !M->cols || !M->slice_ptr || !terms || !b) OX_FAIL("ox_buoyancy_rows: null argument");
+  if (gdim != 2 && gdim != 3) OX_FAIL("ox_buoyancy_rows: gdim=%d", gdim);
+  if (n_terms < 1 || n_terms > OX_MAXC) OX_FAIL("ox_buoyancy_rows: n_terms=%d", n_terms);
+  for (int t = 0; t < n_terms; ++t) {
+    if (!terms[t].c1) OX_FAIL("ox_buoyancy_rows: term %d has no c1", t);
+    if (terms[t].nc < 1 || terms[t].col < 0 || terms[t].col >= terms[t].nc)
+      OX_FAIL("ox_buoyancy_rows: term %d: column %d of %d", t, (int)terms[t].col, (int)terms[t].nc);
+  }
+  if (M->n_slices <= 0) return 0;
+  hipStream_t st = ox_stream(stream);
+  switch (n_terms) {
+    case 1: return launch_buoyancy<1>(M, gdim, terms, b, st);
+    case 2: return launch_buoyancy<2>(M, gdim, terms, b, st);
+    default: return launch_buoyancy<3>(M, gdim, terms, b, st);
+  }
+}
+
+extern "C" int ox_scalar_flux(int degree, const ox_cells *cells, const int32_t *cell_dofs, int64_t n_facets,
+                              const int32_t *facet_rec, const double *c, int nc, int col, double kappa, double weight,
+                              double *q, double *fq, double *cbar, double *acc_q, void *stream) {
+  if (!cells || !cells->geom || !cell_dofs || !facet_rec || !c || !q || !fq || !cbar) OX_FAIL("ox_scalar_flux: null argument");
+  if (nc < 1 || col < 0 || col >= nc) OX_FAIL("ox_scalar_flux: column %d of %d", col, nc);
+  if (weight > 0.0 && !acc_q) OX_FAIL("ox_scalar_flux: weight > 0 without an accumulator");
+  if (!(weight >= 0.0)) OX_FAIL("ox_scalar_flux: weight=%g", weight);
+  if (n_facets <= 0) return 0;
+  if (n_facets > (int64_t)0x7fffffff || cells->n_cells > (int64_t)0x7fffffff)
+    OX_FAIL("ox_scalar_flux: %lld facets, %lld cells", (long long)n_facets, (long long)cells->n_cells);
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const unsigned nblk = (unsigned)((n_facets + 255) / 256);
+#define OX_SCALAR_FLUX_CASE(GD, DG)                                                                                   \
+  if (g == GD && degree == DG) {                                                                                      \
+    if (ox_prof_on) ox_prof_start(OX_TAG_SCALAR_FLUX, st, n_facets);                                                  \
+    hipLaunchKernelGGL((k_scalar_flux<GD, DG>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, n_facets,            \
+                       reinterpret_cast<const int2 *>(facet_rec), c, nc, col, kappa, weight, q, fq, cbar, acc_q);     \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                 \
+    OX_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                         \
+  }
+  OX_FOR_GDIM_DEG(OX_SCALAR_FLUX_CASE)
+#undef OX_SCALAR_FLUX_CASE
+  OX_FAIL("ox_scalar_flux: unsupported gdim=%d, P%d", g, degree);
 }

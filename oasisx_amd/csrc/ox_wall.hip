@@ -20,12 +20,6 @@
 
 namespace {
 
-// facet means of dphi_i/dlambda_b, [a][i][b]
-template <int GDIM, int DEG>
-__host__ __device__ constexpr const auto &dphif() {
-  OX_FE_PICK(GDIM, DEG, OX_DPHIF, );
-}
-
 #define OX_WALL_NS 5  // rows staged per block: t, wss, |f| t, weight wss, weight t
 
 template <int GDIM, int DU, int DP>
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(256) void k_wall_stress(ox_cells cells, const int32
       double tb[GDIM][GDIM + 1] = {}, pbar = 0.0, Ga[GDIM] = {};
       ox_facet_dispatch<GDIM>(a, [&](auto facet) {
         constexpr int A = decltype(facet)::value;
-        ox_contract<GDIM, ND>(uc, dphif<GDIM, DU>()[A], tb);
+        ox_contract<GDIM, ND>(uc, ox_dphif<GDIM, DU>()[A], tb);
 #pragma unroll
         for (int j = 0; j < NDQ; ++j)
           if (ox_phif<GDIM, DP>()[A][j] != 0.0) pbar = fma(pc[j][0], ox_phif<GDIM, DP>()[A][j], pbar);

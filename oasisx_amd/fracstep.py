@@ -101,9 +101,13 @@ class FractionalStep_AB_CN:
         options: ``"low_memory_version"`` accepted (see module docstring)
         body_force: per direction a constant, a callable ``f(x)``, a Function of the component space or a
             :class:`oasisx_amd.function.Expression` of fields (assembled once, as in the reference)
-        scalars: list of :class:`oasisx_amd.ScalarTransport`: passive scalars on the velocity component space, advected by
+        scalars: list of :class:`oasisx_amd.ScalarTransport`: scalars on the velocity component space, advected by
             the extrapolated velocity and solved once per step after the velocity update (:mod:`oasisx_amd.scalar`);
-            ``None`` / ``[]``: no scalar phase runs.  One GPU only
+            ``None`` / ``[]``: no scalar phase runs.  A scalar is passive unless it is given ``buoyancy=b``: then
+            component ``i`` of the momentum equation gains the Boussinesq force ``b_i (c* - reference)``, with ``c*`` the
+            scalar extrapolated to the step's midpoint, added to ``b_first`` inside ``assemble_first`` in one pass over the
+            mass matrix (``buoyancy_assemble``); the coupling is explicit in ``c`` and conditionally stable.
+            :class:`oasisx_amd.ScalarFlux` reads the Nusselt / Sherwood number through tagged walls.  One GPU only
         viscosity_model: :class:`oasisx_amd.Smagorinsky`, :class:`oasisx_amd.Wale` or :class:`oasisx_amd.CellViscosity`:
             an additional viscosity per cell, ``div(nut grad u)``, evaluated per step from the extrapolated velocity and
             added by the fused assembly kernel (:mod:`oasisx_amd.viscosity`); ``None``: the constant-viscosity step,
@@ -290,7 +294,9 @@ class FractionalStep_AB_CN:
         self._solver_u.setOptions(self._A)
         # ---- passive scalars (scalar.py): groups of scalars that share one operator ----------------
         self._scalar_groups, self._scalar_index = [], {}
+        self._buoyancy = []
         self._A_pre_bc = False
+        self._b_first_open = False  # inside assemble_first, between the fused kernel and the boundary terms of b_first
         if scalars:
             from . import scalar as _sc
 
@@ -300,6 +306,8 @@ class FractionalStep_AB_CN:
                 _sc.set_initial(self, g)
                 for j, m in enumerate(g.members):
                     self._scalar_index[m.name] = (g, j)
+            # scalars that drive the flow: the kernel's term records, per launch (empty: every scalar is passive)
+            self._buoyancy = _sc.buoyancy_terms(self._scalar_groups)
         self.timings = {}
 
     # ------------------------------------------------------------------------------------
@@ -446,6 +454,12 @@ class FractionalStep_AB_CN:
                 self.scalar_assemble(dt, nu)
             finally:
                 self._A_pre_bc = False
+        if self._buoyancy:  # b_first += b M (c* - reference) of the coupled scalars; A (and its A u1) is not touched
+            self._b_first_open = True
+            try:
+                self.buoyancy_assemble()
+            finally:
+                self._b_first_open = False
         if self._outlet_models is not None:  # Q of u1, the models' Pc and h: once per assemble_first
             self.outlet_assemble(dt)
         # outlet terms int h n_i dv/dx_i ds (:445-446, :461-465)
@@ -665,6 +679,19 @@ class FractionalStep_AB_CN:
             _sc.assemble(self, g, dt, nu)
 
     @_phase
+    def buoyancy_assemble(self):
+        """The Boussinesq forces of the coupled scalars: ``b_first_i += b_i M (c* - reference)``, ``c* = c_1 + 0.5 (c_1 -
+        c_2)`` (``c_1`` without extrapolation), summed over the scalars with ``buoyancy=`` in one pass over the mass matrix
+        per three of them (``ox_buoyancy_rows``).  Runs INSIDE ``assemble_first``, after the fused row kernel has written
+        ``b_first`` and before its outlet terms and the identity rows; a solver without a coupled scalar never calls it."""
+        if not self._b_first_open:
+            raise RuntimeError("buoyancy_assemble runs inside assemble_first (which calls it): it adds to the b_first that "
+                               "the fused kernel has just written, once per step")
+        from . import scalar as _sc
+
+        _sc.add_buoyancy(self, self._buoyancy)
+
+    @_phase
     def scalar_solve(self) -> dict:
         """Solve every scalar group (columns in lock-step), then c_1 <- c.  Returns {name: converged reason}."""
         from . import scalar as _sc
@@ -678,12 +705,19 @@ class FractionalStep_AB_CN:
 
     def scalar(self, name: str, level: int = 0) -> Function:
         """The scalar ``name``: the current level ``c`` (``level=0``) or the previous one ``c_1`` (``level=1``), from which
-        the next step starts -- write initial data there."""
+        the next step starts -- write initial data there -- or ``c_2`` (``level=2``), which only a group with a coupled
+        scalar that extrapolates its force keeps (the first step's force is taken from ``c_1`` and ``c_2``: initial data
+        written to ``c_1`` after construction belongs there too)."""
         if name not in self._scalar_index:
             raise KeyError(f"no scalar named {name!r} (have: {sorted(self._scalar_index)})")
-        if level not in (0, 1):
-            raise ValueError("scalar: level is 0 (c) or 1 (c_1)")
+        if level not in (0, 1, 2):
+            raise ValueError("scalar: level is 0 (c), 1 (c_1) or 2 (c_2)")
         g, j = self._scalar_index[name]
+        if level == 2:
+            if g.c2 is None:
+                raise ValueError(f"scalar {name!r} keeps no second time level: only the group of a scalar with buoyancy= "
+                                 "and extrapolate=True does")
+            return g.c2[j]
         return (g.c if level == 0 else g.c1)[j]
 
     def solve(self, dt: float, nu: float, max_error: float = 1e-12, max_iter: int = 10):

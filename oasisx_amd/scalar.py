@@ -7,15 +7,26 @@ pressure iteration and is solved once)::
     b_c = (M/dt - C/2 - kappa K/2) c_1 + b0_c  =  (2/dt) M c_1 - A_c c_1 + b0_c
     the scalar's own Dirichlet rows -> identity in A_c, boundary value in b_c;  solve A_c c = b_c;  c_1 <- c
 
-Plain Galerkin, no coupling back into the momentum equation.  ``C(u_ab)`` is what the velocity step assembles anyway:
+Plain Galerkin.  ``C(u_ab)`` is what the velocity step assembles anyway:
 ``A_c = A + (kappa - nu)/2 K`` with the velocity matrix ``A`` before its boundary rows, one streaming pass over the
 values of the shared SELL-64 pattern (``ox_scalar_rows``, csrc/ox_scalar.hip) instead of a second element loop.
 
 Scalars with the same diffusivity specification and the same set of Dirichlet rows form a GROUP: one matrix, solved in
 lock-step as the columns of one block solve (at most 3 columns; more open further groups).  One group costs one f64
 value array of the velocity pattern in device memory.
+
+A scalar with ``buoyancy=b`` drives the flow (Boussinesq): component ``i`` of the momentum equation
+gains ``b_i (c* - reference)`` with ``c* = c_1 + 0.5 (c_1 - c_2)``, the scalar at the step's midpoint (``c* = c_1`` with
+``extrapolate=False``)::
+
+    b_first_i += b_i M (c* - reference)          summed over the coupled scalars, inside assemble_first
+
+in one pass over ``M`` (``ox_buoyancy_rows``); ``A`` is not touched.  The coupling is explicit in ``c``.
+:class:`ScalarFlux` evaluates the diffusive flux ``-kappa n . grad c`` through tagged exterior facets on the device.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 import torch
@@ -25,7 +36,7 @@ from .fem import FieldStorage, Function, Vector
 from .ksp import KSPSolver
 from .la import SellMatrix
 
-__all__ = ["ScalarTransport"]
+__all__ = ["ScalarTransport", "ScalarFlux"]
 
 MAX_COLUMNS = 3  # OX_MAXC: the columns ox_ksp_solve / ox_spmv take in lock-step
 
@@ -41,9 +52,19 @@ class ScalarTransport:
         source: a float, a callable ``f(x)``, a ``Function`` of the component space or a
             :class:`oasisx_amd.function.Expression` -- the four kinds of ``body_force``; assembled once
         initial: c(t0): a float, a callable ``f(x)`` or a ``Function`` of the component space (default 0)
+        buoyancy: ``None`` (default): the scalar is passive.  A sequence of ``gdim`` finite floats ``b``: the momentum
+            equation of component ``i`` gains the force ``b_i (c - reference)`` -- ``b = -beta g`` for a thermal expansion
+            coefficient ``beta``, or ``(0, Ra Pr)`` in diffusion units.  The coupling is EXPLICIT in ``c`` and therefore
+            conditionally stable: ``dt`` is bounded by the buoyancy (Brunt-Vaisala) time scale ``1 / sqrt(|b . grad c|)``
+            beside the step's convective limit
+        reference: the value of ``c`` at which the force vanishes
+        extrapolate: ``True`` (default): the force is taken at the step's midpoint, ``c* = c_1 + 0.5 (c_1 - c_2)`` (second
+            order; the group keeps a second time level ``c_2``, ``solver.scalar(name, level=2)``); ``False``: ``c* = c_1``,
+            first order
     """
 
-    def __init__(self, name, diffusivity=None, schmidt=None, bcs=(), source=0.0, initial=None):
+    def __init__(self, name, diffusivity=None, schmidt=None, bcs=(), source=0.0, initial=None, buoyancy=None,
+                 reference=0.0, extrapolate=True):
         if not isinstance(name, str) or not name:
             raise ValueError("ScalarTransport: name must be a non-empty string")
         if (diffusivity is None) == (schmidt is None):
@@ -68,6 +89,15 @@ class ScalarTransport:
         if initial is not None and not (callable(initial) or isinstance(initial, Function)):
             initial = float(initial)
         self.initial = initial
+        if buoyancy is not None:
+            buoyancy = tuple(float(b) for b in buoyancy)
+            if not all(np.isfinite(b) for b in buoyancy):
+                raise ValueError(f"ScalarTransport {name!r}: buoyancy = {buoyancy}: finite numbers are expected")
+        self.buoyancy = buoyancy
+        self.reference = float(reference)
+        if not np.isfinite(self.reference):
+            raise ValueError(f"ScalarTransport {name!r}: reference = {self.reference}: a finite number is expected")
+        self.extrapolate = bool(extrapolate)
 
     def kappa(self, nu: float) -> float:
         return self.diffusivity if self.schmidt is None else float(nu) / self.schmidt
@@ -89,6 +119,11 @@ class ScalarGroup:
         self.C, self.C1, self.B0, self.B, self.AC1 = (FieldStorage(n, nc, dev) for _ in range(5))
         self.c = [Function(Vi, m.name, self.C, j) for j, m in enumerate(members)]
         self.c1 = [Function(Vi, m.name + "_1", self.C1, j) for j, m in enumerate(members)]
+        # a second time level, only where a coupled member extrapolates its force to the step's midpoint
+        self.C2, self.c2 = None, None
+        if any(m.buoyancy is not None and m.extrapolate for m in members):
+            self.C2 = FieldStorage(n, nc, dev)
+            self.c2 = [Function(Vi, m.name + "_2", self.C2, j) for j, m in enumerate(members)]
         self.rows_dev = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32)).to(dev)
         self.Ac = SellMatrix(Vi.pattern, symmetric=False, name="A_" + "+".join(m.name for m in members))
         self.ksp = KSPSolver(solver._mesh.comm, options, prefix="scalar_transport")
@@ -115,6 +150,11 @@ def build_groups(solver, scalars, options):
     dup = sorted({n for n in names if names.count(n) > 1})
     if dup:
         raise ValueError(f"scalars: duplicate names {dup}")
+    gdim = solver._gdim
+    for s in scalars:
+        if s.buoyancy is not None and len(s.buoyancy) != gdim:
+            raise ValueError(f"ScalarTransport {s.name!r}: buoyancy has {len(s.buoyancy)} entries, the mesh has {gdim} "
+                             "directions")
     for s in scalars:
         for what, f in (("source", s.source), ("initial", s.initial)):
             if isinstance(f, Function) and getattr(f.function_space, "scalar", f.function_space) is not Vi:
@@ -138,7 +178,7 @@ def build_groups(solver, scalars, options):
 
 
 def set_initial(solver, group: ScalarGroup):
-    """c(t0) into both time levels, b0_c = int source v dx (once)."""
+    """c(t0) into every time level, b0_c = int source v dx (once)."""
     Vi = solver._Vi[0][0]
     for j, s in enumerate(group.members):
         f = s.initial
@@ -150,6 +190,42 @@ def set_initial(solver, group: ScalarGroup):
             group.C1.dev()[: Vi.n_local, j] = float(f)
         group.B0.dev()[: Vi.n_owned, j] = solver._source_vector(s.source, f"ScalarTransport {s.name!r}: source")
     group.C.dev().copy_(group.C1.rdev())
+    if group.C2 is not None:
+        group.C2.dev().copy_(group.C1.rdev())
+
+
+def buoyancy_terms(groups):
+    """The ``ox_buoy_term`` records of the coupled scalars of a solver, in the order of the groups and their columns, in
+    launches of at most ``MAX_COLUMNS`` terms: a list of ctypes arrays (the blocks never move: built once)."""
+    terms = []
+    for g in groups:
+        for j, m in enumerate(g.members):
+            if m.buoyancy is None:
+                continue
+            t = _lib.ox_buoy_term()
+            t.c1 = g.C1.rdev().data_ptr()
+            t.c2 = g.C2.rdev().data_ptr() if m.extrapolate else None
+            t.nc, t.col, t.ref = g.nc, j, m.reference
+            for i in range(3):
+                t.coef[i] = m.buoyancy[i] if i < len(m.buoyancy) else 0.0
+            terms.append((g, t))
+    out = []
+    for i in range(0, len(terms), MAX_COLUMNS):
+        chunk = terms[i:i + MAX_COLUMNS]
+        out.append(((_lib.ox_buoy_term * len(chunk))(*[t for _, t in chunk]), [g for g, _ in chunk]))
+    return out
+
+
+def add_buoyancy(solver, launches):
+    """``b_first_i += sum_t b_t,i M (c*_t - reference_t)``: one pass over ``M`` per launch (``ox_buoyancy_rows``)."""
+    st = _lib.current_stream()
+    for arr, groups in launches:
+        for g in groups:  # blocks checked out to the host go back to the device first; read-only from here
+            g.C1.rptr()
+            if g.C2 is not None:
+                g.C2.rptr()
+        _lib.check(solver._lib.ox_buoyancy_rows(solver._M.ref(), solver._gdim, len(arr), arr, solver._BFIRST.ptr(), st),
+                   "ox_buoyancy_rows")
 
 
 def assemble(solver, group: ScalarGroup, dt: float, nu: float):
@@ -180,5 +256,140 @@ def solve(solver, group: ScalarGroup):
             ax0 = group.AC1
     group.ax0_valid = False
     group.reasons = np.asarray(group.ksp.solve_block(group.B, group.C, ax0=ax0), dtype=np.int32)
+    if group.C2 is not None:  # c_2 <- c_1
+        _lib.check(lib.ox_axpby(n, 1.0, group.C1.rptr(), 0.0, None, group.C2.ptr(), st), "ox_axpby")
     _lib.check(lib.ox_axpby(n, 1.0, group.C.rptr(), 0.0, None, group.C1.ptr(), st), "ox_axpby")  # c_1 <- c
     return group.reasons
+
+
+class ScalarFlux:
+    """Diffusive flux ``q_f = -kappa n . mean_f(grad c)`` of one scalar of a ``FractionalStep_AB_CN`` solver through
+    exterior facets, evaluated on the device beside the time step: the Nusselt / Sherwood number of a wall is
+    ``totals()`` over the wall's area and the reference flux.  ``n`` points outward: a positive flux leaves the domain.
+
+    The facet is affine, so the facet mean of the gradient is exact (compile-time facet means of the basis,
+    ``csrc/fe_tables_f.h``); for P1 it is the cell's constant gradient, first order in ``h``.  Limits: one GPU; exterior
+    facets; the DIFFUSIVE flux only -- on an open boundary the advective part ``c u . n`` is not included.
+
+    Args:
+        solver: the solver (one GPU: ``comm.size > 1`` raises ``NotImplementedError``)
+        scalar: the name of one of the solver's scalars
+        facets: ``None``: all exterior facets, one tag 0; ``(meshtags, id)`` / ``(meshtags, (id, ...))``: the facets of
+            those values, one tag per id; an array of facet ids: those facets, one tag 0.  Interior facets raise
+            ``ValueError``
+        capacity: initial length of the ring of totals (it doubles when full)
+
+    The object's facet order is by tag, then by facet id (``.facets``, ``.facet_tags``).  ``.tags``: the tag values;
+    ``.normals`` (outward), ``.areas``, ``.midpoints``: host arrays in that order.
+    """
+
+    def __init__(self, solver, scalar: str, facets=None, capacity: int = 64):
+        from .wall import FacetSet, select_facets
+
+        mesh = solver._mesh
+        comm = getattr(mesh, "comm", None)
+        if comm is not None and getattr(comm, "size", 1) > 1:
+            raise NotImplementedError("ScalarFlux on a mesh partition (comm.size > 1): the facet evaluation and the sums "
+                                      "are built for one GPU")
+        if scalar not in solver._scalar_index:
+            raise KeyError(f"ScalarFlux: no scalar named {scalar!r} (have: {sorted(solver._scalar_index)})")
+        if int(capacity) < 1:
+            raise ValueError(f"ScalarFlux: capacity = {capacity}")
+        ids, tag_of, tags = select_facets(mesh, facets, "ScalarFlux")
+        fs = FacetSet(solver, ids, tag_of, tags.shape[0], "ScalarFlux", "scalar fluxes")
+        self._solver, self.scalar = solver, scalar
+        self._group, self._col = solver._scalar_index[scalar]
+        self.facets, self.tags = ids, tags
+        self.facet_tags = tags[tag_of] if ids.size else tag_of
+        self.cells, self.local_facets = fs.cells, fs.local_facets
+        self.n_facets, self.n_tags = fs.n_facets, fs.n_tags
+        self.normals, self.areas, self.midpoints = fs.normals, fs.areas, fs.midpoints
+        self._rec, self._tag_ptr = fs.rec, fs.tag_ptr
+        dev = mesh.device
+        n = max(self.n_facets, 1)  # (the sums are handed a valid pointer also without facets)
+        self._q, self._fq, self._cbar, self._acc = (torch.zeros(n, dtype=torch.float64, device=dev) for _ in range(4))
+        self._T = 0.0
+        self.capacity = int(capacity)
+        self._ring = torch.zeros((self.capacity, self.n_tags), dtype=torch.float64, device=dev)
+        self._times = []
+
+    @property
+    def n_samples(self) -> int:
+        return len(self._times)
+
+    @property
+    def times(self) -> np.ndarray:
+        return np.asarray(self._times, dtype=np.float64)
+
+    @property
+    def total_weight(self) -> float:
+        return self._T
+
+    def sample(self, t: float, nu: float, dt: float = 0.0) -> None:
+        """Evaluate the flux of the scalar's current ``c`` (``kappa`` from ``nu`` for a Schmidt number) on the current
+        stream: two launches (``ox_scalar_flux``, then the per-tag sums of ``|f| q`` by ``ox_outlet_update``), no host
+        synchronisation; ``c`` is read through ``rptr()``.  ``dt > 0`` adds the sample to the time average with weight
+        ``dt``."""
+        dt = float(dt)
+        if not dt >= 0.0:
+            raise ValueError(f"ScalarFlux.sample: dt = {dt}")
+        k = len(self._times)
+        if k == self.capacity:  # the ring doubles (a device copy on the current stream)
+            ring = torch.zeros((2 * self.capacity, self.n_tags), dtype=torch.float64, device=self._ring.device)
+            ring[: self.capacity] = self._ring
+            self._ring, self.capacity = ring, 2 * self.capacity
+        S, g = self._solver, self._group
+        Vi = S._Vi[0][0]
+        lib, st = _lib.load(), _lib.current_stream()
+        kappa = g.members[self._col].kappa(nu)
+        if self.n_facets:
+            _lib.check(lib.ox_scalar_flux(Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), self.n_facets,
+                                          _lib.ptr(self._rec), g.C.rptr(), g.nc, self._col, float(kappa), dt, _lib.ptr(self._q),
+                                          _lib.ptr(self._fq), _lib.ptr(self._cbar), _lib.ptr(self._acc), st), "ox_scalar_flux")
+        _lib.check(lib.ox_outlet_update(self.n_tags, _lib.ptr(self._tag_ptr), _lib.ptr(self._fq), _lib.ptr(self._ring),
+                                        self.capacity, k, None, 0.0, None, None, None, None, None, 0, st), "ox_outlet_update")
+        self._T += dt
+        self._times.append(float(t))
+
+    def flux(self) -> torch.Tensor:
+        """``q_f`` of the latest sample, (n_facets,) on the device."""
+        return self._q[: self.n_facets]
+
+    def facet_mean(self) -> torch.Tensor:
+        """The facet means of ``c`` of the latest sample, (n_facets,) on the device."""
+        return self._cbar[: self.n_facets]
+
+    def history(self) -> np.ndarray:
+        """(n_samples, n_tags) on the host: ``sum_{f in tag} |f| q_f`` of every sample (one synchronisation)."""
+        return self._ring[: len(self._times)].cpu().numpy()
+
+    def totals(self) -> np.ndarray:
+        """(n_tags,) on the host: ``sum_{f in tag} |f| q_f`` of the latest sample."""
+        if not self._times:
+            raise RuntimeError("ScalarFlux: no sample has been taken")
+        return self._ring[len(self._times) - 1].cpu().numpy()
+
+    def mean_flux(self) -> torch.Tensor:
+        """The time average ``(1/T) sum dt q_f`` over the samples taken with ``dt > 0``."""
+        if not self._T > 0.0:
+            raise RuntimeError("ScalarFlux: no sample with dt > 0 has been taken since the statistics were reset")
+        return self._acc[: self.n_facets] / self._T
+
+    def reset_statistics(self) -> None:
+        self._acc.zero_()
+        self._T = 0.0
+
+    def save(self, path, vtu=None, time: float = 0.0) -> None:
+        """History and per-facet fields as ``.npz``; ``vtu``: a path for the facets' surface with ``flux`` and
+        ``facet_mean`` (and ``mean_flux``) as cell data (:func:`oasisx_amd.io.write_facet_vtu`)."""
+        out = dict(history=self.history(), times=self.times, facets=self.facets, facet_tags=self.facet_tags, tags=self.tags,
+                   normals=self.normals, areas=self.areas, midpoints=self.midpoints, flux=self.flux().cpu().numpy(),
+                   facet_mean=self.facet_mean().cpu().numpy(), total_weight=self._T)
+        if self._T > 0.0:
+            out.update(mean_flux=self.mean_flux().cpu().numpy())
+        np.savez(path, **out)
+        if vtu is not None:
+            from .io import write_facet_vtu
+
+            data = {k: out[k] for k in ("flux", "facet_mean", "mean_flux") if k in out}
+            write_facet_vtu(vtu, self._solver._mesh, self.facets, data, time=time)
