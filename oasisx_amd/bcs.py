@@ -322,7 +322,8 @@ class PressureBC:
         """The assembled term of component i as a full vector (tests; reference test_bcs.py:166-217)."""
         from .fem import FieldStorage
 
-        B = FieldStorage(self._V.n_local, len(self._S) or 1, self._V.mesh.device)
+        # (a rank of a partition that holds no facet of the boundary has no operators: its term is zero in every component)
+        B = FieldStorage(self._V.n_local, self._V.mesh.gdim, self._V.mesh.device)
         self.add_surface_terms(B)
         return B.host()[:, i].copy()
 
