@@ -288,8 +288,11 @@ class RankIPCS:
 
     def _solve(self, kind, A, dinv, b, x, ncomp, plan, name):
         res = self.L.ox_ksp_result()
-        self.L.check(self.lib.ox_ksp_solve(kind, C.byref(A), dinv, b, x, ncomp, self.rtol, 1e-30, 10000, 0, 4, 0, self.work,
-                                           self.work_bytes, C.byref(res), plan.handle, None), "ox_ksp_solve")
+        opt = self.L.ox_ksp_options()
+        self.L.check(self.lib.ox_ksp_options_default(C.byref(opt)), "ox_ksp_options_default")  # zero guess, no restarts
+        opt.rtol, opt.atol, opt.max_it, opt.check_every = self.rtol, 1e-30, 10000, 4
+        self.L.check(self.lib.ox_ksp_solve(kind, C.byref(A), dinv, b, x, ncomp, C.byref(opt), self.work, self.work_bytes,
+                                           C.byref(res), plan.handle, None), "ox_ksp_solve")
         self.L.check(self.lib.ox_halo_forward(plan.handle, x, ncomp, None), "x.scatter_forward")  # reference ksp.py:77
         reasons = [int(res.reason[c]) for c in range(ncomp)]
         assert all(r > 0 for r in reasons), (name, reasons)

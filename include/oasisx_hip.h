@@ -84,6 +84,9 @@ extern "C" {
                              for the next point (the carried r.z is replaced every iteration: no drift; the convergence test
                              sees the true |D^-1 r|, one point later: one surplus mat-vec per solve).  Same Krylov space;
                              iteration counts equal to OX_KSP_CG's up to rounding.  With ncomp > 1 the call runs OX_KSP_CG */
+#define OX_KSP_CG_MG 6 /* "cg" preconditioned by the V-cycle of an ox_mg hierarchy (ox_ksp_options.mg) instead of the Jacobi
+                          diagonal: PETSc's KSPCG + PCGAMG; on a mesh-partitioned operator pc_type bjacobi + sub_pc_type gamg.
+                          One right-hand side */
 
 /* SELL-64 matrix: pattern + one value array (PETSc Mat on this path). */
 typedef struct {
@@ -182,6 +185,8 @@ typedef struct {
 
 /* Halo plan + communicator for mesh-partitioned runs (NULL = single GPU). */
 typedef struct ox_dist ox_dist;
+/* Smoothed-aggregation AMG hierarchy (ox_mg_create, below) */
+typedef struct ox_mg ox_mg;
 
 typedef struct {
   int32_t reason[4];         /* per component, KSPConvergedReason                        */
@@ -522,60 +527,61 @@ int ox_assemble_div_vector(int row_degree, int u_degree, const ox_cells *cells,
 int ox_jacobi_setup(const ox_sell *A, double *dinv, void *stream);
 
 /* ---- K1/K2/K3: KSP.solve (reference ksp.py:71-78; fracstep.py:521,578,634) ---------- */
-/* Left-Jacobi-preconditioned CG or BiCGStab on `ncomp` right-hand sides that share A
- * (the velocity components share one matrix, fracstep.py:274,521), run in lockstep with
- * per-component scalars; PETSc conventions: zero initial guess unless nonzero_guess,
- * convergence on ||D^-1 r|| <= max(rtol*||D^-1 b||, atol).  Scalars stay on the device;
- * the host reads the state back every `check_every` iterations. */
-size_t ox_ksp_work_bytes(int64_t n_rows, int64_t n_cols, int ncomp, int ksp_type);
-int ox_ksp_solve(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x,
-                 int ncomp, double rtol, double atol, int max_it, int nonzero_guess,
-                 int check_every, int max_restarts, void *work, size_t work_bytes,
-                 ox_ksp_result *result, const ox_dist *dist, void *stream);
-/* The same with A x0 supplied by the caller (nonzero_guess only; NULL = computed here): the velocity
- * update has M u* at hand from its right-hand side (fracstep.py:615,634), so the solver's first
- * mat-vec is skipped.  ax0: device [n_rows][ncomp], the product with the x passed in. */
-int ox_ksp_solve_ax0(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x,
-                     int ncomp, double rtol, double atol, int max_it, int nonzero_guess,
-                     int check_every, int max_restarts, void *work, size_t work_bytes,
-                     ox_ksp_result *result, const ox_dist *dist, void *stream, const double *ax0);
-/* The same with a value dictionary of dinv (dinv_code: device [n_rows] bytes, dinv[i] == dinv_dict[dinv_code[i]] bit
- * for bit; ox_value_dictionary builds it where dinv takes <= 256 distinct values, as the diagonals of M and Ap do on
- * meshes of congruent cells): the CG update kernels then read one byte per row instead of eight.  Same iterates. */
-int ox_ksp_solve_dc(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x,
-                    int ncomp, double rtol, double atol, int max_it, int nonzero_guess,
-                    int check_every, int max_restarts, void *work, size_t work_bytes,
-                    ox_ksp_result *result, const ox_dist *dist, void *stream, const double *ax0,
-                    const uint8_t *dinv_code, const double *dinv_dict, int n_dinv_dict);
-/* The same with every option of the solve in one block -- PETSc's KSP options (reference ksp.py:38-53 forwards any key to
- * KSPSetFromOptions) and this library's schedule knobs, per call instead of per process:
- *   divtol       -ksp_divtol: |D^-1 r| >= divtol |D^-1 b| ends the column with OX_DIVERGED_DTOL (KSPConvergedDefault;
- *                PETSc's default 1e4 -- "divergence=10000." in -ksp_view); the older entry points run with that default
+/* ONE call solves A x = b with the Krylov method `ksp_type` (OX_KSP_*) on `ncomp` (1..3) right-hand sides that share A
+ * (the velocity components share one matrix, fracstep.py:274,521), run in lockstep with per-component scalars; b and x
+ * are interleaved [n][ncomp].  Left preconditioning by the Jacobi diagonal `dinv` (ox_jacobi_setup), or, with
+ * OX_KSP_CG_MG, by one V-cycle z = B r of the hierarchy `opt->mg` (one right-hand side; dinv may be NULL and
+ * opt->dinv_code is ignored; A is the operator of the hierarchy's level 0).  PETSc conventions: zero initial guess unless
+ * opt->nonzero_guess, convergence on the preconditioned norm |B r| <= max(rtol |B b|, atol).  Scalars stay on the device;
+ * the host reads the state every `check_every` iterations, and once all columns but one have finished the rest of the
+ * solve runs on one-column vectors.  Every argument is checked before the first device call.
+ *   work         ox_ksp_work_bytes_for(A, ncomp, ksp_type) bytes of device memory
+ *   dist         NULL on one GPU.  Otherwise A (n_owned x n_local) is the partitioned operator: every mat-vec refreshes
+ *                the ghosts of its operand (one halo exchange), dot products run over the owned rows and every
+ *                synchronisation point all-reduces.  x's ghosts are NOT refreshed at the end (ox_halo_forward).  A
+ *                timed-out peer fails the solve (ox_dist_status).
+ * The options, in one block -- PETSc's KSP options (reference ksp.py:38-53 forwards any key to KSPSetFromOptions) and
+ * this library's schedule knobs, per call instead of per process:
+ *   divtol       -ksp_divtol: |B r| >= divtol |B b| ends the column with OX_DIVERGED_DTOL (KSPConvergedDefault; PETSc's
+ *                default 1e4 -- "divergence=10000." in -ksp_view)
+ *   max_restarts BiCGStab only.  0 = PETSc's KSPBCGS: a rho = rhat.r = 0 (or omega = 0) breakdown ends the solve with
+ *                OX_DIVERGED_BREAKDOWN.  > 0: re-seed the shadow residual (rhat <- r) and continue, at most that many
+ *                times per component (used when a direct solver was asked for)
  *   fold_blocks  one-column CG on one GPU: blocks of the folded update kernels; 0 = separate synchronisation points
  *                (five kernels per iteration), -1 = ox_ksp_default_fold_blocks()
  *   run_ahead    one-column solves queue one batch ahead of the state the host reads: 1 / 0, -1 = default (1)
- * ox_ksp_options_default fills in PETSc's defaults (rtol 1e-5, atol 1e-50, divtol 1e4, max_it 10000, zero guess). */
+ *   ax0          A x0 supplied by the caller (nonzero_guess only; NULL = computed here), device [n_rows][ncomp], the
+ *                product with the x passed in: the velocity update has M u* at hand from its right-hand side
+ *                (fracstep.py:615,634), so the solver's first mat-vec is skipped.  Same iterates
+ *   dinv_code    a value dictionary of dinv (device [n_rows] bytes, dinv[i] == dinv_dict[dinv_code[i]] bit for bit,
+ *                1 <= n_dinv_dict <= 256; ox_value_dictionary builds it where dinv takes <= 256 distinct values, as the
+ *                diagonals of M and Ap do on meshes of congruent cells): the CG update kernels then read one byte per row
+ *                instead of eight.  Same iterates
+ *   mg           OX_KSP_CG_MG: the hierarchy; with dist != NULL that of the rank's owned-by-owned block (n_owned rows,
+ *                ghost columns dropped), applied without communication, and NULL on a rank that owns no rows (it still
+ *                takes part in every exchange and all-reduce)
+ * ox_ksp_options_default fills in PETSc's defaults (rtol 1e-5, atol 1e-50, divtol 1e4, max_it 10000, zero guess) and
+ * leaves ax0, dinv_code and mg NULL. */
 typedef struct {
   double rtol, atol, divtol;
   int32_t max_it, nonzero_guess, check_every, max_restarts;
   int32_t fold_blocks, run_ahead;
-  const double *ax0;         /* see ox_ksp_solve_ax0                                      */
-  const uint8_t *dinv_code;  /* see ox_ksp_solve_dc                                       */
+  const double *ax0;
+  const uint8_t *dinv_code;
   const double *dinv_dict;
   int32_t n_dinv_dict;
   int32_t reserved;
+  const ox_mg *mg;
 } ox_ksp_options;
 int ox_ksp_options_default(ox_ksp_options *opt);
-int ox_ksp_solve_opt(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x, int ncomp,
-                     const ox_ksp_options *opt, void *work, size_t work_bytes, ox_ksp_result *result,
-                     const ox_dist *dist, void *stream);
+int ox_ksp_solve(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x, int ncomp,
+                 const ox_ksp_options *opt, void *work, size_t work_bytes, ox_ksp_result *result,
+                 const ox_dist *dist, void *stream);
+size_t ox_ksp_work_bytes(int64_t n_rows, int64_t n_cols, int ncomp, int ksp_type);
 /* Workspace of a solve on THIS operator: ox_ksp_work_bytes sizes the partial-sum arrays for the lane = row grid; an
  * operator that carries an LDS-window stream may launch more blocks than that (one per window block).  Callers with the
  * ox_sell at hand use this one; ox_ksp_solve checks against it. */
 size_t ox_ksp_work_bytes_for(const ox_sell *A, int ncomp, int ksp_type);
-/* max_restarts: BiCGStab only.  0 = PETSc's KSPBCGS: a rho = rhat.r = 0 (or omega = 0) breakdown
- * ends the solve with OX_DIVERGED_BREAKDOWN.  > 0: re-seed the shadow residual (rhat <- r) and
- * continue, at most that many times per component (used when a direct solver was asked for). */
 
 /* ---- Projector into a discontinuous P1 space (reference function.py:13-143 with the "DG" 1 target of its
  *      test_projector.py:26-35).  Dof (cell e, vertex a, component c) at (e * (gdim+1) + a) * ncomp + c, cells in
@@ -602,7 +608,8 @@ int ox_remove_mean(int64_t n, int64_t n_apply, double *x, const double *w, doubl
  * for it: one block per compute unit.  Partitioned operators never fold (their points carry an all-reduce). */
 int ox_ksp_default_fold_blocks(void);
 /* Kernels one iteration of the given method launches on this operator with these options (reporting: bench.py);
- * partitioned != 0: the operator has a halo plan. */
+ * partitioned != 0: the operator has a halo plan.  OX_KSP_CG_MG: -1 (the count is ox_mg_kernels_per_cycle(mg) + 6: the
+ * mat-vec, two synchronisation points, three vector kernels). */
 int ox_ksp_kernels_per_iteration(int ksp_type, const ox_sell *A, int ncomp, int check_every, int fold_blocks,
                                  int partitioned);
 int ox_profile_begin(int max_records, int sample_every); /* time every sample_every-th launch per tag */
@@ -617,7 +624,7 @@ int ox_profile_get(int tag, long long key, long long *count, double *total_ms); 
 int ox_range_push(const char *name);
 int ox_range_pop(void);
 
-/* ---- Smoothed-aggregation AMG (PETSc's pc_type gamg) for one-column CG on one GPU (ox_amg.hip) ----------------------
+/* ---- Smoothed-aggregation AMG (PETSc's pc_type gamg) for one-column CG, OX_KSP_CG_MG (ox_amg.hip) --------------------
  * The hierarchy is built on the host (oasisx_amd/amg.py); the library keeps copies of the level descriptions below and
  * its own level vectors.  Level 0 is the caller's operator with all its storage levels; levels 1.. are plain-f64 SELL-64.
  * Level l < n_levels - 1 is smoothed by `degree` Chebyshev-Jacobi steps,  r = D^-1 (b - A x);  d = c_d d + c_r r;
@@ -626,7 +633,6 @@ int ox_range_pop(void);
  * unused) is solved with the dense row-major inverse `coarse_inv` (device [n_c * n_c]): a symmetric V-cycle. */
 #define OX_MG_MAX_DEGREE 8
 #define OX_MG_MAX_LEVELS 16
-#define OX_KSP_CG_MG 6 /* the preconditioned CG of ox_ksp_solve_mg: workspace sizing (ox_ksp_work_bytes_for) only */
 typedef struct {
   ox_sell A;             /* level operator                                   */
   ox_sell P;             /* prolongation to this level from the next coarser */
@@ -637,7 +643,6 @@ typedef struct {
   int32_t reserved;
   double cheb[2 * OX_MG_MAX_DEGREE];
 } ox_mg_level;
-typedef struct ox_mg ox_mg;
 /* tail_rows: the levels of at most this many rows (and the coarse solve) run in ONE single-workgroup launch; <= 0: the
  * library's default */
 int ox_mg_create(int n_levels, const ox_mg_level *levels, const double *coarse_inv, int tail_rows, ox_mg **out);
@@ -646,19 +651,6 @@ int ox_mg_destroy(ox_mg *mg);
 int ox_mg_apply(const ox_mg *mg, const double *r, double *z, void *stream);
 /* kernel launches of one V-cycle (reporting) */
 int ox_mg_kernels_per_cycle(const ox_mg *mg);
-/* CG preconditioned by the V-cycle (PETSc's KSPCG + PCGAMG), one right-hand side, one GPU: same options, same state
- * machinery and the same convergence test on the preconditioned norm |B r| <= max(rtol |B b|, atol) as ox_ksp_solve_opt;
- * z = B r is stored.  A: the operator of the hierarchy's level 0; work: ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG) bytes;
- * opt->dinv_code is ignored. */
-int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt, void *work,
-                    size_t work_bytes, ox_ksp_result *result, void *stream);
-/* The same CG on a mesh-partitioned operator (PETSc's pc_type bjacobi + sub_pc_type gamg, one block per rank): `mg` is the
- * hierarchy of the rank's owned-by-owned block (n_owned rows, ghost columns dropped; nullptr on a rank that owns no rows),
- * applied without communication; A (n_owned x n_local) is the partitioned operator.  Per iteration one halo exchange (the
- * mat-vec refreshes the ghosts of p) and two all-reduces; dot products over the owned rows.  x's ghosts are NOT refreshed
- * at the end (ox_halo_forward).  A timed-out peer fails the solve (ox_dist_status). */
-int ox_ksp_solve_mg_dist(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
-                         void *work, size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, void *stream);
 
 /* ---- Projected initial guesses (PETSc's -ksp_guess_type fischer) for repeated CG solves on one operator (ox_guess.hip)
  * Per column of an interleaved (n_rows x ncomp) block the object keeps k <= size A-orthonormal directions x~_j (model 1

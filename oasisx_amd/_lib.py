@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OX_LIB_PATH") or os.path.join(_HERE, "liboasisx_hip.so")  # override: tuning builds
 
 KSP_CG, KSP_BCGS, KSP_CG_SINGLE, KSP_BCGS_MERGED, KSP_CG_MERGED = 1, 2, 3, 4, 5
-KSP_CG_MG = 6  # OX_KSP_CG_MG: workspace sizing of ox_ksp_solve_mg
+KSP_CG_MG = 6  # OX_KSP_CG_MG: CG preconditioned by the V-cycle of ox_ksp_options.mg
 MG_MAX_DEGREE = 8  # OX_MG_MAX_DEGREE
 ROW_BLOCK_WAVES, ROW_BLOCK_LDS = 8, 134 * 1024  # OX_ROW_BLOCK_WAVES / OX_ROW_BLOCK_LDS of include/oasisx_hip.h
 CONVERGED_RTOL, CONVERGED_ATOL, CONVERGED_ITS = 2, 3, 4
@@ -210,6 +210,7 @@ class ox_ksp_options(C.Structure):
         ("dinv_dict", C.c_void_p),
         ("n_dinv_dict", C.c_int32),
         ("reserved", C.c_int32),
+        ("mg", C.c_void_p),
     ]
 
 
@@ -321,28 +322,18 @@ SIGNATURES = {
     "ox_dg1_mass": (_I, [_I, C.POINTER(ox_cells), _I, _P, _P, _P]),
     "ox_jacobi_setup": (_I, [C.POINTER(ox_sell), _P, _P]),
     "ox_ksp_work_bytes": (C.c_size_t, [_L, _L, _I, _I]),
-    "ox_ksp_solve": (_I, [_I, C.POINTER(ox_sell), _P, _P, _P, _I, _D, _D, _I, _I, _I, _I, _P,
-                          C.c_size_t, C.POINTER(ox_ksp_result), _P, _P]),
-    "ox_ksp_solve_ax0": (_I, [_I, C.POINTER(ox_sell), _P, _P, _P, _I, _D, _D, _I, _I, _I, _I, _P,
-                              C.c_size_t, C.POINTER(ox_ksp_result), _P, _P, _P]),
-    "ox_ksp_solve_dc": (_I, [_I, C.POINTER(ox_sell), _P, _P, _P, _I, _D, _D, _I, _I, _I, _I, _P,
-                             C.c_size_t, C.POINTER(ox_ksp_result), _P, _P, _P, _P, _P, _I]),
     "ox_remove_mean": (_I, [_L, _L, _P, _P, _D, _P, _P]),
     "ox_window_retile": (_I, [C.POINTER(ox_sell), _P, _P, _I, _P, _P]),
     "ox_ksp_default_fold_blocks": (_I, []),
     "ox_ksp_kernels_per_iteration": (_I, [_I, C.POINTER(ox_sell), _I, _I, _I, _I]),
     "ox_ksp_options_default": (_I, [C.POINTER(ox_ksp_options)]),
-    "ox_ksp_solve_opt": (_I, [_I, C.POINTER(ox_sell), _P, _P, _P, _I, C.POINTER(ox_ksp_options), _P, C.c_size_t,
-                              C.POINTER(ox_ksp_result), _P, _P]),
+    "ox_ksp_solve": (_I, [_I, C.POINTER(ox_sell), _P, _P, _P, _I, C.POINTER(ox_ksp_options), _P, C.c_size_t,
+                          C.POINTER(ox_ksp_result), _P, _P]),
     "ox_ksp_work_bytes_for": (C.c_size_t, [C.POINTER(ox_sell), _I, _I]),
     "ox_mg_create": (_I, [_I, C.POINTER(ox_mg_level), _P, _I, C.POINTER(_P)]),
     "ox_mg_destroy": (_I, [_P]),
     "ox_mg_apply": (_I, [_P, _P, _P, _P]),
     "ox_mg_kernels_per_cycle": (_I, [_P]),
-    "ox_ksp_solve_mg": (_I, [_P, C.POINTER(ox_sell), _P, _P, C.POINTER(ox_ksp_options), _P, C.c_size_t,
-                             C.POINTER(ox_ksp_result), _P]),
-    "ox_ksp_solve_mg_dist": (_I, [_P, C.POINTER(ox_sell), _P, _P, C.POINTER(ox_ksp_options), _P, C.c_size_t,
-                                  C.POINTER(ox_ksp_result), _P, _P]),
     "ox_guess_create": (_I, [_L, _L, _I, _I, _I, C.POINTER(_P)]),
     "ox_guess_destroy": (_I, [_P]),
     "ox_guess_reset": (_I, [_P]),

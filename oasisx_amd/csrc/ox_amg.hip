@@ -385,7 +385,7 @@ extern "C" int ox_mg_destroy(ox_mg *mg) {
 extern "C" int ox_mg_kernels_per_cycle(const ox_mg *mg) { return mg ? mg->kernels : -1; }
 int64_t ox_mg_fine_rows(const ox_mg *mg) { return mg ? mg->lv[0].n_rows : -1; }
 
-// z = B r on `st`; every kernel is a no-op once *done (nullptr: always runs).  (Used by ox_ksp_solve_mg.)
+// z = B r on `st`; every kernel is a no-op once *done (nullptr: always runs).  (Used by OX_KSP_CG_MG: ox_ksp.hip.)
 int ox_mg_vcycle(const ox_mg *mg, const double *r, double *z, const int *done, hipStream_t st) {
   const ox_sell *A0 = &mg->lv[0].A;
   for (const MgOp &o : mg->ops) {

@@ -1037,17 +1037,31 @@ extern "C" size_t ox_ksp_work_bytes_for(const ox_sell *A, int ncomp, int ksp_typ
   return ksp_layout(A->n_rows, A->n_cols, ncomp, ksp_type, ksp_grid_max(A)).total;
 }
 
-// (per host thread: several ranks of a job may be driven from threads of ONE process, each inside its own solve --
-// tests/test_gpu_threads_rehearsal.py; a thread's 1.2 KB of pinned memory and two events live as long as the process)
-static thread_local KspState *g_state_host = nullptr;
-// Where the last synchronisation point of the batch being queued writes the host's copy of the state (pinned, host
-// mapped: g_state_host[1 + slot]); nullptr outside ksp_run_ahead.  An in-stream copy of these 400 bytes is a blit
+// The host's side of a solve, per host thread: several ranks of a job may be driven from threads of ONE process, each
+// inside its own solve (tests/test_gpu_threads_rehearsal.py).  state: 3 pinned, host-mapped blocks -- [0] the state the
+// host acts on, [1], [2] the two batches in flight of ksp_iterate's run-ahead form --; ev: the events behind those two.
+// Created on first use and never released: a thread_local destructor would free pinned memory and events after the HIP
+// runtime's own teardown on the main thread, so a thread's 1.2 KB and two events live as long as the process (the
+// per-thread leak is the open item of ADVICE.md).
+struct KspHost {
+  KspState *state;
+  hipEvent_t ev[2];
+};
+static int ksp_host(KspHost **out) {
+  static thread_local KspHost H{nullptr, {nullptr, nullptr}};
+  if (!H.state) OX_HIP(hipHostMalloc(&H.state, 3 * sizeof(KspState)));
+  for (int i = 0; i < 2; ++i)
+    if (!H.ev[i]) OX_HIP(hipEventCreateWithFlags(&H.ev[i], hipEventDisableTiming));
+  *out = &H;
+  return 0;
+}
+// `mirror`: where the last synchronisation point of the batch being queued writes the host's copy of the state
+// (KspHost::state[1 + slot]; nullptr: the host copies the state itself).  An in-stream copy of these 400 bytes is a blit
 // kernel of ~18 us plus ~6 us of stream bubble (rocprofv3, r03: 0.7 ms of a 16-ms pressure solve at 8 iterations a
 // batch); the kernel's own posted stores cost it ~1 us.
-static thread_local KspState *g_batch_mirror = nullptr;
-static inline KspParams ksp_last_point(const KspParams &P, int k, int count) {
+static inline KspParams ksp_last_point(const KspParams &P, int k, int count, KspState *mirror) {
   KspParams Q = P;
-  Q.mirror = (k + 1 == count) ? g_batch_mirror : nullptr;
+  Q.mirror = (k + 1 == count) ? mirror : nullptr;
   return Q;
 }
 
@@ -1127,6 +1141,10 @@ struct KspCtx {
   hipStream_t st;
   int nb, nbs;
   int fold;  // blocks of the folded one-column CG update kernels (0: separate synchronisation points)
+  int type;  // the OX_KSP_* method (merged CG on several columns already demoted to plain CG)
+  double *vec[6];     // the method's vectors, ncomp columns wide
+  double *narrow[8];  // ncomp > 1: compact one-column vectors of the narrowed continuation
+  const ox_mg *mg;  // OX_KSP_CG_MG: the hierarchy behind z = B r (nullptr: a rank that owns no rows)
 };
 
 #define KSP_SYNC(PH, partial, nparts, nv)                                                       \
@@ -1137,34 +1155,59 @@ struct KspCtx {
 // blocks of the folded CG update kernels: the library's default (a per-solve value comes in through ox_ksp_options;
 // the environment is read by the host layer, not here)
 static int ksp_fold_blocks_default() {
-  static int dflt = -1;
-  if (dflt < 0) {
-    // ONE block per compute unit: a CU that receives a second 1024-thread block takes twice as long as the others
-    // (128^3 pressure: 256 blocks 59.1 us per iteration, 262 blocks 66.0, 512 blocks 65.8, 128 blocks 62.5)
+  // ONE block per compute unit: a CU that receives a second 1024-thread block takes twice as long as the others
+  // (128^3 pressure: 256 blocks 59.1 us per iteration, 262 blocks 66.0, 512 blocks 65.8, 128 blocks 62.5)
+  static const int dflt = [] {
     hipDeviceProp_t prop;
     int dev = 0;
     int ncu = 256;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
       ncu = prop.multiProcessorCount;
-    dflt = ncu > OX_FOLD_T ? OX_FOLD_T : ncu;  // (the second point reads one partial row per thread)
-  }
+    return ncu > OX_FOLD_T ? OX_FOLD_T : ncu;  // (the second point reads one partial row per thread)
+  }();
   return dflt;
 }
 static inline int ksp_fold_blocks_of(int v) { return v < 0 ? ksp_fold_blocks_default() : (v > OX_FOLD_T ? OX_FOLD_T : v); }
+// Iterations queued in one go by the run-ahead form of ksp_iterate: small batches (the tail of no-ops after convergence
+// is about one batch), large enough for the host to stay ahead: 8 pressure-CG iterations are 40 launches for 600 us of
+// GPU time
+static inline int ksp_batch(int check_every) { return check_every > 8 ? 8 : (check_every < 1 ? 1 : check_every); }
+
+// The form the iterations of a batch of `count` take on this operator.  Decided HERE alone: cg_iterations and
+// cgm_iterations launch what it says, ox_ksp_kernels_per_iteration reports it.  One column on one GPU folds the
+// synchronisation points into the update kernels (`fold` blocks of them, ksp_fold_grid); the merged form alternates its
+// state block per iteration, so only even batches fold, and its threads request at most 10 partial rows each.
+enum KspForm { KSP_UNFOLDED, KSP_CG_FOLDED, KSP_CG_FOLDED_PRERED, KSP_CGM_FOLDED };
+static KspForm ksp_form(int ksp_type, const ox_sell *A, int ncomp, bool partitioned, int fold, int count) {
+  if (ncomp != 1 || partitioned || A->n_rows < 2 || fold <= 0) return KSP_UNFOLDED;
+  const int nbs1 = ox_spmv_dist_nparts(A, nullptr, 1);  // (block sums of the ONE-column mat-vec)
+  if (ksp_type == OX_KSP_CG) {
+    const int npin = nbs1;  // rows the first folded point reads: pre-reduced when there are many
+    if (npin >= OX_PRERED_MIN) return KSP_CG_FOLDED_PRERED;  // (a 17 M-row mass matrix: 66 K block sums)
+    return KSP_CG_FOLDED;
+  }
+  if (ksp_type == OX_KSP_CG_MERGED && (count & 1) == 0 && nbs1 <= 10 * OX_FOLD_T) return KSP_CGM_FOLDED;
+  return KSP_UNFOLDED;
+}
+static inline int ksp_fold_grid(int64_t n, int fold) {
+  int64_t want = ((n >> 1) + OX_FOLD_T - 1) / OX_FOLD_T;
+  if (want < 1) want = 1;
+  return (int)(want < fold ? want : fold);
+}
+
 template <int NC>
-static int cg_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count) {
+static int cg_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, KspState *mirror) {
   const int64_t n = C.A->n_rows;
   const int *done = &C.S->done;
-  if (NC == 1 && !C.dist && n >= 2 && C.fold > 0) {  // one column, one GPU: both points folded into the update kernels
-    int64_t want = ((n >> 1) + OX_FOLD_T - 1) / OX_FOLD_T;
-    if (want < 1) want = 1;
-    const int nbf = (int)(want < C.fold ? want : C.fold);
-    const int nbs1 = ox_spmv_dist_nparts(C.A, nullptr, 1);  // (block sums of the ONE-column mat-vec)
+  const KspForm form = ksp_form(OX_KSP_CG, C.A, NC, C.dist != nullptr, C.fold, count);
+  if (form != KSP_UNFOLDED) {  // one column, one GPU: both points folded into the update kernels
+    const int nbf = ksp_fold_grid(n, C.fold);
+    const int nbs1 = ox_spmv_dist_nparts(C.A, nullptr, 1);
     for (int k = 0; k < count; ++k) {
       if (ox_spmv_dist(C.A, V.p, V.q, 1, OX_EPI_DOT, nullptr, nullptr, C.partial, done, nullptr, C.st)) return -1;
       const double *pin = C.partial;
       int npin = nbs1;
-      if (npin >= OX_PRERED_MIN) {  // (a 17 M-row mass matrix: 66 K block sums)
+      if (form == KSP_CG_FOLDED_PRERED) {
         double *scr = C.sums + OX_PRERED_OFFSET;
         const int g = ksp_prered_rows(npin);
         hipLaunchKernelGGL(k_prereduce, dim3(g), dim3(256), 0, C.st, pin, npin, 1, scr);
@@ -1175,12 +1218,12 @@ static int cg_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, 
         hipLaunchKernelGGL(k_cg_update1f<true>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, C.S, C.S2, pin, npin, P, V.r, V.q,
                            C.D, C.partial2);
         hipLaunchKernelGGL(k_cg_update2f<true>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, C.S2, C.S, C.partial2, nbf,
-                           ksp_last_point(P, k, count), V.x, V.r, C.D, V.p);
+                           ksp_last_point(P, k, count, mirror), V.x, V.r, C.D, V.p);
       } else {
         hipLaunchKernelGGL(k_cg_update1f<false>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, C.S, C.S2, pin, npin, P, V.r, V.q,
                            C.D, C.partial2);
         hipLaunchKernelGGL(k_cg_update2f<false>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, C.S2, C.S, C.partial2, nbf,
-                           ksp_last_point(P, k, count), V.x, V.r, C.D, V.p);
+                           ksp_last_point(P, k, count, mirror), V.x, V.r, C.D, V.p);
       }
       OX_LAUNCH_CHECK();
     }
@@ -1191,7 +1234,7 @@ static int cg_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, 
     KSP_SYNC(PH_CG_A, C.partial, C.nbs, NC);
     hipLaunchKernelGGL((k_cg_update1<NC>), dim3(C.nb), dim3(256), 0, C.st, n, C.S, P.c0, V.r, V.q, C.D, C.partial);
     OX_LAUNCH_CHECK();
-    if (ksp_sync_point<PH_CG_B>(C.S, C.partial, C.nb, 2 * NC, C.sums, ksp_last_point(P, k, count), C.dist, C.st)) return -1;
+    if (ksp_sync_point<PH_CG_B>(C.S, C.partial, C.nb, 2 * NC, C.sums, ksp_last_point(P, k, count, mirror), C.dist, C.st)) return -1;
     hipLaunchKernelGGL((k_cg_update2<NC>), dim3(C.nb), dim3(256), 0, C.st, n, C.S, P.c0, V.x, V.r, C.D, V.p, 0);
     OX_LAUNCH_CHECK();
   }
@@ -1365,44 +1408,41 @@ __global__ __launch_bounds__(OX_FOLD_T) void k_cgm_updatef(int64_t n, const KspS
 }
 
 template <int NC>
-static int cgm_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, bool first) {
+static int cgm_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, bool first, KspState *mirror) {
   const int64_t n = C.A->n_rows;
   const int *done = &C.S->done;
-  if (NC == 1 && !C.dist && n >= 2 && C.fold > 0 && (count & 1) == 0) {
+  if (ksp_form(OX_KSP_CG_MERGED, C.A, NC, C.dist != nullptr, C.fold, count) == KSP_CGM_FOLDED) {
     // folded: the state alternates S / S2 per iteration (an even batch leaves it in S, where the host and the next
-    // batch look for it), the update's partial sums between two arrays
+    // batch look for it), the update's partial sums between two arrays; every thread's <= 10 partial rows of the
+    // mat-vec are requested in one round
     const int nbs1 = ox_spmv_dist_nparts(C.A, nullptr, 1);
-    if (nbs1 <= 10 * OX_FOLD_T) {  // (every thread's <= 10 partial rows of the mat-vec are requested in one round)
-      int64_t want = ((n >> 1) + OX_FOLD_T - 1) / OX_FOLD_T;
-      if (want < 1) want = 1;
-      const int nbf = (int)(want < C.fold ? want : C.fold);
-      double *pu[2] = {C.partial2, C.partial2 + 3 * OX_FOLD_T};
-      for (int k = 0; k < count; ++k) {
-        KspState *Sin = (k & 1) ? C.S2 : C.S, *Sout = (k & 1) ? C.S : C.S2;
-        ox_spmv_set_epilogue_dinv(C.D.code, C.D.dict);
-        const int rc = ox_spmv_dist(C.A, V.p, V.q, 1, OX_EPI_CG_M2, C.dinv, nullptr, C.partial, &Sin->done, nullptr, C.st);
-        ox_spmv_set_epilogue_dinv(nullptr, nullptr);
-        if (rc) return -1;
-        KspParams Q = ksp_last_point(P, k, count);
-        Q.first = (first && k == 0) ? 1 : 0;
-        const int npb = Q.first ? 0 : nbf;
-        if (C.D.code)
-          hipLaunchKernelGGL(k_cgm_updatef<true>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, Sin, Sout, C.partial, nbs1,
-                             pu[(k + 1) & 1], npb, Q, V.x, V.r, V.q, C.D, V.p, pu[k & 1]);
-        else
-          hipLaunchKernelGGL(k_cgm_updatef<false>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, Sin, Sout, C.partial, nbs1,
-                             pu[(k + 1) & 1], npb, Q, V.x, V.r, V.q, C.D, V.p, pu[k & 1]);
-        OX_LAUNCH_CHECK();
-      }
-      return 0;
+    const int nbf = ksp_fold_grid(n, C.fold);
+    double *pu[2] = {C.partial2, C.partial2 + 3 * OX_FOLD_T};
+    for (int k = 0; k < count; ++k) {
+      KspState *Sin = (k & 1) ? C.S2 : C.S, *Sout = (k & 1) ? C.S : C.S2;
+      ox_spmv_set_epilogue_dinv(C.D.code, C.D.dict);
+      const int rc = ox_spmv_dist(C.A, V.p, V.q, 1, OX_EPI_CG_M2, C.dinv, nullptr, C.partial, &Sin->done, nullptr, C.st);
+      ox_spmv_set_epilogue_dinv(nullptr, nullptr);
+      if (rc) return -1;
+      KspParams Q = ksp_last_point(P, k, count, mirror);
+      Q.first = (first && k == 0) ? 1 : 0;
+      const int npb = Q.first ? 0 : nbf;
+      if (C.D.code)
+        hipLaunchKernelGGL(k_cgm_updatef<true>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, Sin, Sout, C.partial, nbs1,
+                           pu[(k + 1) & 1], npb, Q, V.x, V.r, V.q, C.D, V.p, pu[k & 1]);
+      else
+        hipLaunchKernelGGL(k_cgm_updatef<false>, dim3(nbf), dim3(OX_FOLD_T), 0, C.st, n, Sin, Sout, C.partial, nbs1,
+                           pu[(k + 1) & 1], npb, Q, V.x, V.r, V.q, C.D, V.p, pu[k & 1]);
+      OX_LAUNCH_CHECK();
     }
+    return 0;
   }
   for (int k = 0; k < count; ++k) {
     ox_spmv_set_epilogue_dinv(C.D.code, C.D.dict);
     const int rc = ox_spmv_dist(C.A, V.p, V.q, NC, OX_EPI_CG_M2, C.dinv, nullptr, C.partial, done, C.dist, C.st);
     ox_spmv_set_epilogue_dinv(nullptr, nullptr);
     if (rc) return -1;
-    KspParams Q = ksp_last_point(P, k, count);
+    KspParams Q = ksp_last_point(P, k, count, mirror);
     Q.first = (first && k == 0) ? 1 : 0;
     if (ksp_sync_point<PH_CGM_IT>(C.S, C.partial, C.nbs, 2 * NC, C.sums, Q, C.dist, C.st,
                                   Q.first ? KspPart2{nullptr, 0, 0} : KspPart2{C.partial2, C.nb, 3 * NC}))
@@ -1416,7 +1456,7 @@ static int cgm_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P,
 // Single-reduction CG: update kernel, SpMV with the w.u epilogue, ONE synchronisation point (one
 // all-reduce of {r.u, u.u, w.u} in a partitioned run) -- 3 kernels per iteration instead of 5.
 template <int NC>
-static int cgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count) {
+static int cgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, KspState *mirror) {
   const int64_t n = C.A->n_rows;
   const int *done = &C.S->done;
   for (int k = 0; k < count; ++k) {
@@ -1424,7 +1464,7 @@ static int cgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P,
                        C.dinv, C.partial);
     OX_LAUNCH_CHECK();
     if (ox_spmv_dist(C.A, V.u, V.w, NC, OX_EPI_DOT, nullptr, nullptr, C.partial2, done, C.dist, C.st)) return -1;
-    if (ksp_sync_point<PH_CGS_IT>(C.S, C.partial, C.nb, 2 * NC, C.sums, ksp_last_point(P, k, count), C.dist, C.st,
+    if (ksp_sync_point<PH_CGS_IT>(C.S, C.partial, C.nb, 2 * NC, C.sums, ksp_last_point(P, k, count, mirror), C.dist, C.st,
                                   KspPart2{C.partial2, C.nbs, NC}))
       return -1;
   }
@@ -1432,7 +1472,7 @@ static int cgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P,
 }
 
 template <int NC>
-static int bcgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, bool first) {
+static int bcgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, bool first, KspState *mirror) {
   const int64_t n = C.A->n_rows;
   const int *done = &C.S->done;
   for (int k = 0; k < count; ++k) {
@@ -1449,7 +1489,7 @@ static int bcgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P
     hipLaunchKernelGGL((k_bcgs_x<NC>), dim3(C.nb), dim3(256), 0, C.st, n, C.S, P.c0, V.x, V.r, V.rhat, V.p, V.s,
                        V.t, C.partial, 0);
     OX_LAUNCH_CHECK();
-    if (ksp_sync_point<PH_BCGS_3>(C.S, C.partial, C.nb, 2 * NC, C.sums, ksp_last_point(P, k, count), C.dist, C.st)) return -1;
+    if (ksp_sync_point<PH_BCGS_3>(C.S, C.partial, C.nb, 2 * NC, C.sums, ksp_last_point(P, k, count, mirror), C.dist, C.st)) return -1;
   }
   return 0;
 }
@@ -1460,17 +1500,17 @@ static int bcgs_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P
 // The x / r update runs after the second point with that iteration's alpha and omega, fused with the next p
 // update (k_bcgs_xp); the update the `done` flag skips at the end of the solve is applied by bcgsm_finish.
 template <int NC>
-static int bcgsm_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, bool first) {
+static int bcgsm_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, KspState *mirror) {
   const int64_t n = C.A->n_rows;
   const int *done = &C.S->done;
-  (void)first;  // the first iteration's p = r was written by k_bcgs_init; every later p comes out of k_bcgs_xp
+  // (the first iteration's p = r was written by k_bcgs_init; every later p comes out of k_bcgs_xp)
   for (int k = 0; k < count; ++k) {
     if (ox_spmv_dist(C.A, V.p, V.v, NC, OX_EPI_BCGS_V, C.dinv, V.rhat, C.partial, done, C.dist, C.st)) return -1;
     if (ksp_sync_point<PH_BCGS_1>(C.S, C.partial, C.nbs, NC, C.sums, P, C.dist, C.st)) return -1;
     hipLaunchKernelGGL((k_bcgs_s<NC>), dim3(C.nb), dim3(256), 0, C.st, n, C.S, P.c0, V.r, V.v, V.s);
     OX_LAUNCH_CHECK();
     if (ox_spmv_dist(C.A, V.s, V.t, NC, OX_EPI_BCGS_T5, C.dinv, V.rhat, C.partial, done, C.dist, C.st)) return -1;
-    if (ksp_sync_point<PH_BCGSM_B>(C.S, C.partial, C.nbs, 5 * NC, C.sums, ksp_last_point(P, k, count), C.dist, C.st)) return -1;
+    if (ksp_sync_point<PH_BCGSM_B>(C.S, C.partial, C.nbs, 5 * NC, C.sums, ksp_last_point(P, k, count, mirror), C.dist, C.st)) return -1;
     hipLaunchKernelGGL((k_bcgs_xp<NC>), dim3(C.nb), dim3(256), 0, C.st, n, C.S, P.c0, V.x, V.r, V.rhat, V.p, V.s, V.t, V.v, 0);
     OX_LAUNCH_CHECK();
   }
@@ -1484,259 +1524,12 @@ static int bcgsm_finish(const KspCtx &C, const KspVecs &V, const KspParams &P) {
   return 0;
 }
 
-static int ksp_read_state(const KspCtx &C) {
-  OX_HIP(hipMemcpyAsync(g_state_host, C.S, sizeof(KspState), hipMemcpyDeviceToHost, C.st));
-  OX_HIP(hipStreamSynchronize(C.st));
-  return C.dist ? ox_dist_status(C.dist) : 0;  // a timed-out peer wait fails the solve
-}
-
-// One-column solves (the pressure CG, the narrowed tail of the velocity solves) run ONE BATCH AHEAD of
-// the state the host looks at: batch k+1 is queued before the copy of the state after batch k is waited
-// for, so the GPU never idles for the ~30 us of a read-back (the "host reads" of SURVEY section 7).  The
-// price is one batch of no-op kernels after convergence, hence small batches.  g_state_host[1], [2] are
-// the two copies in flight; the final state ends up in g_state_host[0].
-static thread_local hipEvent_t g_state_ev[2] = {nullptr, nullptr};
-template <class Iterate>
-static int ksp_run_ahead(const KspCtx &C, Iterate &&iterate, int batch, int &it, int max_it) {
-  for (int i = 0; i < 2; ++i)
-    if (!g_state_ev[i]) OX_HIP(hipEventCreateWithFlags(&g_state_ev[i], hipEventDisableTiming));
-  // batch -> state in g_state_host[1 + slot]: written by the batch's last synchronisation point itself (g_batch_mirror)
-  auto queue = [&](int slot) -> int {
-    g_state_host[1 + slot].done = 0;
-    g_batch_mirror = g_state_host + 1 + slot;
-    const int rc = iterate(batch);
-    g_batch_mirror = nullptr;
-    if (rc) return -1;
-    OX_HIP(hipEventRecord(g_state_ev[slot], C.st));
-    return 0;
-  };
-  if (queue(0)) return -1;
-  it += batch;
-  int cur = 0;
-  for (;;) {
-    const bool more = it <= max_it;  // (the kernels stop by themselves at max_it: reason DIVERGED_ITS)
-    if (more) {
-      if (queue(1 - cur)) return -1;
-      it += batch;
-    }
-    OX_HIP(hipEventSynchronize(g_state_ev[cur]));
-    if (C.dist && ox_dist_status(C.dist)) return -1;
-    if (g_state_host[1 + cur].done || !more) {
-      OX_HIP(hipStreamSynchronize(C.st));  // the batch queued ahead (no-ops after `done`) and its copy
-      if (!more && !g_state_host[1 + cur].done) {  // ran out of batches: take the newest state
-        OX_HIP(hipMemcpyAsync(g_state_host, C.S, sizeof(KspState), hipMemcpyDeviceToHost, C.st));
-        OX_HIP(hipStreamSynchronize(C.st));
-        return 0;
-      }
-      g_state_host[0] = g_state_host[1 + cur];
-      return 0;
-    }
-    cur = 1 - cur;
-  }
-}
-
-template <int NC>
-static int ksp_run(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x,
-                   const KspParams &P, int guess, int check_every, char *work,
-                   ox_ksp_result *result, const ox_dist *dist, hipStream_t st, const double *ax0, const KspDinv &Dc,
-                   int fold_blocks, int run_ahead) {
-  const int64_t n = A->n_rows;
-  const KspLayout L = ksp_layout(A->n_rows, A->n_cols, NC, ksp_type, ksp_grid_max(A));
-  KspCtx C;
-  C.A = A;
-  C.dinv = dinv;
-  C.D = Dc;
-  C.S = reinterpret_cast<KspState *>(work + L.state);
-  C.S2 = reinterpret_cast<KspState *>(work + L.state2);
-  C.sums = reinterpret_cast<double *>(work + L.sums);
-  C.partial = reinterpret_cast<double *>(work + L.partial);
-  C.partial2 = reinterpret_cast<double *>(work + L.partial2);
-  C.dist = dist;
-  C.st = st;
-  C.nb = ox_vec_blocks(2 * (n > 0 ? n : 1));  // one row per thread
-  C.nbs = ox_spmv_dist_nparts(A, dist, NC);
-  C.fold = fold_blocks;
-  double *vec[6];
-  for (int i = 0; i < L.nvec; ++i) vec[i] = reinterpret_cast<double *>(work + L.vec0 + L.vec_stride * i);
-  if (!g_state_host) OX_HIP(hipHostMalloc(&g_state_host, 3 * sizeof(KspState)));
-  const bool cg = ksp_type == OX_KSP_CG, cgs = ksp_type == OX_KSP_CG_SINGLE, bm = ksp_type == OX_KSP_BCGS_MERGED;
-  const bool cgm = ksp_type == OX_KSP_CG_MERGED;  // (one right-hand side only: ox_ksp_solve_dc)
-  KspVecs V{};
-  V.x = x;
-  if (cgs) {
-    V.r = vec[0], V.u = vec[1], V.p = vec[2], V.s = vec[3], V.w = vec[4];
-    if (guess && !ax0) {
-      if (ox_spmv_dist(A, x, V.w, NC, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
-    }
-    hipLaunchKernelGGL((k_cgs_init<NC>), dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && ax0) ? ax0 : V.w, dinv, V.r, V.u,
-                       V.p, V.s, guess, C.partial);
-    OX_LAUNCH_CHECK();
-    if (ox_spmv_dist(A, V.u, V.w, NC, OX_EPI_DOT, nullptr, nullptr, C.partial2, nullptr, dist, st)) return -1;
-    if (ksp_sync_point<PH_CGS_INIT>(C.S, C.partial, C.nb, 3 * NC, C.sums, P, dist, st, KspPart2{C.partial2, C.nbs, NC}))
-      return -1;
-  } else if (cg || cgm) {
-    V.r = vec[0], V.p = vec[1], V.q = vec[2];
-    if (guess && !ax0) {
-      if (ox_spmv_dist(A, x, V.q, NC, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
-    }
-    hipLaunchKernelGGL((k_cg_init<NC>), dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && ax0) ? ax0 : V.q, dinv, V.r,
-                       V.p, guess, C.partial);
-    OX_LAUNCH_CHECK();
-    KSP_SYNC(PH_CG_INIT, C.partial, C.nb, 3 * NC);
-  } else {
-    V.r = vec[0], V.rhat = vec[1], V.p = vec[2], V.v = vec[3], V.s = vec[4], V.t = vec[5];
-    if (guess && !ax0) {
-      if (ox_spmv_dist(A, x, V.t, NC, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
-    }
-    hipLaunchKernelGGL((k_bcgs_init<NC>), dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && ax0) ? ax0 : V.t, dinv, V.r,
-                       V.rhat, V.p, V.v, guess, C.partial);
-    OX_LAUNCH_CHECK();
-    KSP_SYNC(PH_BCGS_INIT, C.partial, C.nb, 2 * NC);
-  }
-  bool bm_first = true;  // BiCGStab: the first iteration of the solve finds p = r in place (k_bcgs_init)
-  auto iterate = [&](auto nc_tag, const KspVecs &W, const KspParams &Q) -> int {
-    constexpr int N_ = decltype(nc_tag)::value;
-    const bool first = bm_first;
-    bm_first = false;
-    return cgs ? cgs_iterations<N_>(C, W, Q, check_every)
-           : cgm ? cgm_iterations<N_>(C, W, Q, check_every, first)
-               : (cg ? cg_iterations<N_>(C, W, Q, check_every)
-                     : (bm ? bcgsm_iterations<N_>(C, W, Q, check_every, first) : bcgs_iterations<N_>(C, W, Q, check_every, first)));
-  };
-  // small batches (the tail of no-ops after convergence is about one batch), large enough for the host
-  // to stay ahead: 8 pressure-CG iterations are 40 launches for 600 us of GPU time
-  auto batch_of = [&](int every) { return every > 8 ? 8 : every; };
-  int it = 0;  // iterations queued so far (the kernels stop by themselves at max_it)
-  bool tail_done = false;  // the narrowed continuation applied the deferred updates of its column itself
-  // The merged-reduction BiCGStab re-enters this loop when the STORED residual of a column fails the test its
-  // recurrence norm passed (PH_BCGSM_FIN); every other method leaves it after one pass.
-  for (;;) {
-    tail_done = false;
-    if (NC == 1 && run_ahead) {
-      const int bsz = batch_of(check_every);
-      auto it1 = [&](int count) -> int {
-        const bool first = bm_first;
-        bm_first = false;
-        return cgs ? cgs_iterations<1>(C, V, P, count)
-               : cgm ? cgm_iterations<1>(C, V, P, count, first)
-                   : (cg ? cg_iterations<1>(C, V, P, count)
-                         : (bm ? bcgsm_iterations<1>(C, V, P, count, first) : bcgs_iterations<1>(C, V, P, count, first)));
-      };
-      if (ksp_run_ahead(C, it1, bsz, it, P.max_it)) return -1;
-    }
-    for (; !(NC == 1 && run_ahead) && it <= P.max_it; it += check_every) {
-      if (iterate(std::integral_constant<int, NC>{}, V, P)) return -1;
-      if (ksp_read_state(C)) return -1;
-      if (g_state_host->done) break;
-      if (NC > 1) {
-        // Narrowing: the columns run in lockstep, so once all but one have converged the rest of
-        // the solve would drag NC-wide vectors along for nothing.  Extract the live column into
-        // compact vectors and continue with the 1-column kernels (same recurrences, same scalars:
-        // the state block is addressed through P.c0); insert x back at the end.
-        int live = -1, nlive = 0;
-        for (int c = 0; c < NC; ++c)
-          if (g_state_host->active[c]) live = c, ++nlive;
-        if (nlive == 1) {
-          double *cv[8];
-          for (int i = 0; i < 8; ++i) cv[i] = reinterpret_cast<double *>(work + L.narrow0 + L.narrow_stride * i);
-          KspVecs W{};
-          double *src[8] = {V.x, V.r, V.z, V.p, V.q, V.rhat, V.v, nullptr};
-          double **dst[8] = {&W.x, &W.r, &W.z, &W.p, &W.q, &W.rhat, &W.v, nullptr};
-          if (cg) src[2] = nullptr;  // no z vector: the second update kernel forms D^-1 r itself
-          if (cgs) {  // x, r, u, p, s (a recurrence: carried over), w
-            src[2] = V.u, dst[2] = &W.u;
-            src[4] = V.s, dst[4] = &W.s;
-            src[5] = V.w, dst[5] = &W.w;
-            src[6] = nullptr;
-          }
-          for (int i = 0; i < 7; ++i) {
-            *dst[i] = cv[i];
-            if (!src[i]) continue;
-            hipLaunchKernelGGL(k_extract_col, dim3(C.nb), dim3(256), 0, st, n, src[i], NC, live, cv[i]);
-            OX_LAUNCH_CHECK();
-          }
-          if (!cgs) {
-            W.s = cv[2];  // BiCGStab temporaries share the slots CG uses for z and q
-            W.t = cv[4];
-          }
-          KspParams P1 = P;
-          P1.nc = 1;
-          P1.c0 = live;
-          if (run_ahead) {
-            const int bsz = batch_of(check_every);
-            auto it1 = [&](int count) -> int {
-              return cgs ? cgs_iterations<1>(C, W, P1, count)
-                         : (cg ? cg_iterations<1>(C, W, P1, count)
-                               : (bm ? bcgsm_iterations<1>(C, W, P1, count, false) : bcgs_iterations<1>(C, W, P1, count, false)));
-            };
-            it += check_every;
-            if (ksp_run_ahead(C, it1, bsz, it, P.max_it)) return -1;
-          } else {
-            for (it += check_every; it <= P.max_it; it += check_every) {
-              if (iterate(std::integral_constant<int, 1>{}, W, P1)) return -1;
-              if (ksp_read_state(C)) return -1;
-              if (g_state_host->done) break;
-            }
-          }
-          if (cg) {  // the last x += alpha p (see k_cg_update2)
-            hipLaunchKernelGGL((k_cg_update2<1>), dim3(C.nb), dim3(256), 0, st, n, C.S, P1.c0, W.x, W.r, C.D, W.p, 1);
-            OX_LAUNCH_CHECK();
-          }
-          if (bm && g_state_host->its[live] > 0) {
-            if (bcgsm_finish<1>(C, W, P1)) return -1;
-            // (the re-test below reads the stored residuals of all columns from the NC-wide block)
-            hipLaunchKernelGGL(k_insert_col, dim3(C.nb), dim3(256), 0, st, n, W.r, NC, live, V.r);
-            OX_LAUNCH_CHECK();
-          }
-          tail_done = true;
-          hipLaunchKernelGGL(k_insert_col, dim3(C.nb), dim3(256), 0, st, n, W.x, NC, live, x);
-          OX_LAUNCH_CHECK();
-          break;
-        }
-      }
-    }
-    if (!g_state_host->done) OX_FAIL("ox_ksp_solve: device state never reported completion");
-    if (!bm) break;
-    bool any = false;
-    for (int c = 0; c < NC; ++c) any = any || g_state_host->its[c] > 0;
-    if (!any) break;  // every column converged on the initial (stored) residual: nothing ran, nothing to re-test
-    // the x / r update of the last iteration (skipped by `done`)
-    if (!tail_done && bcgsm_finish<NC>(C, V, P)) return -1;
-    bool retest = false;
-    for (int c = 0; c < NC; ++c)
-      retest = retest || g_state_host->reason[c] == OX_CONVERGED_RTOL || g_state_host->reason[c] == OX_CONVERGED_ATOL;
-    if (!retest) break;
-    hipLaunchKernelGGL((k_rr<NC>), dim3(C.nb), dim3(256), 0, st, n, V.r, C.partial);
-    OX_LAUNCH_CHECK();
-    KSP_SYNC(PH_BCGSM_FIN, C.partial, C.nb, NC);
-    if (ksp_read_state(C)) return -1;
-    if (g_state_host->done) break;  // every stored residual passes (or a column ran out of iterations)
-    // resume: rhat <- r, p <- r in the re-opened columns (k_bcgs_p reads the restart flags); p = r in the others
-    hipLaunchKernelGGL((k_bcgs_p<NC>), dim3(C.nb), dim3(256), 0, st, n, C.S, P.c0, V.r, V.p, V.v, V.rhat);
-    OX_LAUNCH_CHECK();
-    it = 0;
-    for (int c = 0; c < NC; ++c) it = g_state_host->its[c] > it ? g_state_host->its[c] : it;
-  }
-  if (cg && !tail_done) {  // the last x += alpha p (see k_cg_update2)
-    hipLaunchKernelGGL((k_cg_update2<NC>), dim3(C.nb), dim3(256), 0, st, n, C.S, P.c0, V.x, V.r, C.D, V.p, 1);
-    OX_LAUNCH_CHECK();
-  }
-  for (int c = 0; c < NC; ++c) {
-    result->reason[c] = g_state_host->reason[c];
-    result->its[c] = g_state_host->its[c];
-    result->rnorm[c] = g_state_host->rn[c];
-    result->bnorm[c] = g_state_host->bn[c];
-    result->resumed[c] = bm ? g_state_host->nresume[c] : 0;
-  }
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------
 // CG preconditioned by an AMG V-cycle (PETSc's KSPCG + PCGAMG; ox_amg.hip), one column.  z = B r is stored (the
 // preconditioner is not a diagonal the update kernels could apply on the fly); the synchronisation points, the state and
 // the run-ahead batches are those of the Jacobi CG (PH_CG_INIT, PH_CG_A, PH_CG_B): the convergence test sees |z| = |B r|.
 // Per iteration:  q = A p (+ p.q);  point A;  x += alpha p, r -= alpha q;  z = B r;  {r.z, z.z};  point B;  p = z + beta p.
-// On a mesh-partitioned operator (ox_ksp_solve_mg_dist: PETSc's pc_type bjacobi + sub_pc_type gamg) B is the V-cycle of
+// On a mesh-partitioned operator (dist != NULL: PETSc's pc_type bjacobi + sub_pc_type gamg) B is the V-cycle of
 // the rank's owned-by-owned block -- no communication inside it --, the mat-vec refreshes the ghosts of p (one halo
 // exchange), the dot products run over the owned rows and both points all-reduce.
 // ---------------------------------------------------------------------------------------
@@ -1792,7 +1585,7 @@ __global__ __launch_bounds__(256) void k_mgcg_update2(int64_t n, const KspState 
   OX_ROW_LOOP { p[row] = fma(be, p[row], z[row]); }
 }
 
-static int mgcg_iterations(const ox_mg *mg, const KspCtx &C, const KspVecs &V, const KspParams &P, int count) {
+static int mgcg_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, KspState *mirror) {
   const int64_t n = C.A->n_rows;
   const int *done = &C.S->done;
   for (int k = 0; k < count; ++k) {
@@ -1800,99 +1593,306 @@ static int mgcg_iterations(const ox_mg *mg, const KspCtx &C, const KspVecs &V, c
     KSP_SYNC(PH_CG_A, C.partial, C.nbs, 1);
     hipLaunchKernelGGL(k_mgcg_update1, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.x, V.r, V.p, V.q);
     OX_LAUNCH_CHECK();
-    if (mg && ox_mg_vcycle(mg, V.r, V.z, done, C.st)) return -1;  // (no hierarchy: a rank that owns no rows)
+    if (C.mg && ox_mg_vcycle(C.mg, V.r, V.z, done, C.st)) return -1;  // (no hierarchy: a rank that owns no rows)
     hipLaunchKernelGGL(k_mgcg_dots<false>, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.r, V.z, nullptr, nullptr, C.partial);
     OX_LAUNCH_CHECK();
-    if (ksp_sync_point<PH_CG_B>(C.S, C.partial, C.nb, 2, C.sums, ksp_last_point(P, k, count), C.dist, C.st)) return -1;
+    if (ksp_sync_point<PH_CG_B>(C.S, C.partial, C.nb, 2, C.sums, ksp_last_point(P, k, count, mirror), C.dist, C.st)) return -1;
     hipLaunchKernelGGL(k_mgcg_update2, dim3(C.nb), dim3(256), 0, C.st, n, C.S, V.z, V.p);
     OX_LAUNCH_CHECK();
   }
   return 0;
 }
 
-// dist: nullptr on one GPU (ox_ksp_solve_mg); mg: nullptr only on a rank that owns no rows (it still takes part in
-// every exchange and all-reduce)
-static int mgcg_solve(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt, void *work,
-                      size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, hipStream_t st) {
-  if (work_bytes < ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG))
-    OX_FAIL("ox_ksp_solve_mg: workspace too small (%zu < %zu)", work_bytes, ox_ksp_work_bytes_for(A, 1, OX_KSP_CG_MG));
-  if (!(opt->divtol > 0.0)) OX_FAIL("ox_ksp_solve_mg: divtol=%g (must be positive; PETSc's default is 1e4)", opt->divtol);
-  if (mg && ox_mg_fine_rows(mg) != A->n_rows)  // (the cycle's fine-level vectors have the hierarchy's rows)
-    OX_FAIL("ox_ksp_solve_mg: hierarchy of %lld fine rows for an operator of %lld rows", (long long)ox_mg_fine_rows(mg),
+// ------------------------------- one solve: dispatch, host loop, set-up --------------------------------
+// `count` iterations of the context's method on N columns.  `first`: the first iteration of the solve is among them
+// (BiCGStab finds p = r in place, written by k_bcgs_init; merged CG has no update kernel behind its first point).
+template <int N>
+static int ksp_iterations(const KspCtx &C, const KspVecs &V, const KspParams &P, int count, bool first, KspState *mirror) {
+  switch (C.type) {
+    case OX_KSP_CG: return cg_iterations<N>(C, V, P, count, mirror);
+    case OX_KSP_CG_MERGED: return cgm_iterations<N>(C, V, P, count, first, mirror);  // (one column: ksp_check_args)
+    case OX_KSP_CG_SINGLE: return cgs_iterations<N>(C, V, P, count, mirror);
+    case OX_KSP_BCGS: return bcgs_iterations<N>(C, V, P, count, first, mirror);
+    case OX_KSP_BCGS_MERGED: return bcgsm_iterations<N>(C, V, P, count, mirror);
+    default: return mgcg_iterations(C, V, P, count, mirror);  // OX_KSP_CG_MG (one column: ksp_check_args)
+  }
+}
+
+static int ksp_read_state(const KspCtx &C, KspHost *H) {
+  OX_HIP(hipMemcpyAsync(H->state, C.S, sizeof(KspState), hipMemcpyDeviceToHost, C.st));
+  OX_HIP(hipStreamSynchronize(C.st));
+  return C.dist ? ox_dist_status(C.dist) : 0;  // a timed-out peer wait fails the solve
+}
+
+// the one column of an nc-column solve that is still active (-1: none, or several)
+static int ksp_last_live(const KspState *s, int nc) {
+  int live = -1, nlive = 0;
+  for (int c = 0; c < nc; ++c)
+    if (s->active[c]) live = c, ++nlive;
+  return nlive == 1 ? live : -1;
+}
+
+// The host loop of every method and width: queue iterations (`it` counts them; the kernels stop by themselves at
+// max_it: reason DIVERGED_ITS) until the state in H->state[0] says `done` -- or, with N > 1 columns, until all but one
+// of them have finished (the caller narrows).
+//   lock-step: `check_every` iterations, then a copy of the state the host waits for (~30 us of idle GPU).
+//   ahead (one-column solves: the pressure CG, the narrowed tail of the velocity solves): ONE BATCH AHEAD of the state
+//   the host looks at -- batch k+1 is queued before the state after batch k is waited for, so the GPU never idles for
+//   a read-back (the "host reads" of SURVEY section 7).  The price is one batch of no-op kernels after convergence,
+//   hence ksp_batch.  The last point of a batch writes the state into H->state[1 + slot] itself (ksp_last_point).
+template <int N>
+static int ksp_iterate(const KspCtx &C, const KspVecs &V, const KspParams &P, int check_every, bool ahead, int &it, bool &first,
+                       KspHost *H) {
+  auto queue = [&](int count, KspState *mirror) -> int {
+    const bool f = first;
+    first = false;
+    return ksp_iterations<N>(C, V, P, count, f, mirror);
+  };
+  if (!ahead) {
+    for (; it <= P.max_it; it += check_every) {
+      if (queue(check_every, nullptr)) return -1;
+      if (ksp_read_state(C, H)) return -1;
+      if (H->state->done || (N > 1 && ksp_last_live(H->state, N) >= 0)) break;
+    }
+    return 0;
+  }
+  const int batch = ksp_batch(check_every);
+  KspState *hs = H->state;
+  auto queue_ahead = [&](int slot) -> int {
+    hs[1 + slot].done = 0;
+    if (queue(batch, hs + 1 + slot)) return -1;
+    OX_HIP(hipEventRecord(H->ev[slot], C.st));
+    it += batch;
+    return 0;
+  };
+  if (queue_ahead(0)) return -1;
+  for (int cur = 0;; cur = 1 - cur) {
+    const bool more = it <= P.max_it;
+    if (more && queue_ahead(1 - cur)) return -1;
+    OX_HIP(hipEventSynchronize(H->ev[cur]));
+    if (C.dist && ox_dist_status(C.dist)) return -1;
+    if (hs[1 + cur].done || !more) {
+      OX_HIP(hipStreamSynchronize(C.st));  // the batch queued ahead (no-ops after `done`)
+      if (!hs[1 + cur].done) {             // ran out of batches: take the newest state
+        OX_HIP(hipMemcpyAsync(hs, C.S, sizeof(KspState), hipMemcpyDeviceToHost, C.st));
+        OX_HIP(hipStreamSynchronize(C.st));
+      } else {
+        hs[0] = hs[1 + cur];
+      }
+      return 0;
+    }
+  }
+}
+
+// The ONE argument check of a solve and its KspParams from the options; every refusal happens here, before the first
+// HIP call.  Merged CG is the one-column solver: with more columns it is demoted to plain CG, here and nowhere else.
+static int ksp_check_args(int &ksp_type, const ox_sell *A, const double *dinv, const double *b, const double *x, int ncomp,
+                          const ox_ksp_options *opt, const void *work, size_t work_bytes, const ox_ksp_result *result,
+                          const ox_dist *dist, KspParams &P) {
+  const bool mg = ksp_type == OX_KSP_CG_MG;
+  if (!A || !b || !x || !work || !result || !opt || (!dinv && !mg)) OX_FAIL("ox_ksp_solve: null argument");
+  if (ksp_type != OX_KSP_CG && ksp_type != OX_KSP_BCGS && ksp_type != OX_KSP_CG_SINGLE && ksp_type != OX_KSP_BCGS_MERGED &&
+      ksp_type != OX_KSP_CG_MERGED && !mg)
+    OX_FAIL("ox_ksp_solve: ksp_type=%d", ksp_type);
+  if (ksp_type == OX_KSP_CG_MERGED && ncomp > 1) ksp_type = OX_KSP_CG;
+  if (ncomp < 1 || ncomp > OX_MAXC) OX_FAIL("ox_ksp_solve: ncomp=%d out of range", ncomp);
+  if (mg && ncomp != 1) OX_FAIL("ox_ksp_solve: ncomp=%d with OX_KSP_CG_MG (one column)", ncomp);
+  if (mg && !opt->mg && (!dist || A->n_rows > 0))  // (no hierarchy: only a rank that owns no rows)
+    OX_FAIL("ox_ksp_solve: no hierarchy for %lld owned rows", (long long)A->n_rows);
+  if (work_bytes < ox_ksp_work_bytes_for(A, ncomp, ksp_type))
+    OX_FAIL("ox_ksp_solve: workspace too small (%zu < %zu)", work_bytes, ox_ksp_work_bytes_for(A, ncomp, ksp_type));
+  if (!mg && opt->dinv_code && (!opt->dinv_dict || opt->n_dinv_dict < 1 || opt->n_dinv_dict > 256))
+    OX_FAIL("ox_ksp_solve: dinv dictionary of %d entries", opt->n_dinv_dict);
+  if (!(opt->divtol > 0.0)) OX_FAIL("ox_ksp_solve: divtol=%g (must be positive; PETSc's default is 1e4)", opt->divtol);
+  if (mg && opt->mg && ox_mg_fine_rows(opt->mg) != A->n_rows)  // (the cycle's fine-level vectors have the hierarchy's rows)
+    OX_FAIL("ox_ksp_solve: hierarchy of %lld fine rows for an operator of %lld rows", (long long)ox_mg_fine_rows(opt->mg),
             (long long)A->n_rows);
-  memset(result, 0, sizeof(*result));
-  KspParams P{};
+  P = KspParams{};
   P.rtol = opt->rtol;
   P.atol = opt->atol;
   P.dtol = opt->divtol;
   P.max_it = opt->max_it < 1 ? 1 : opt->max_it;
-  P.nc = 1;
+  P.nc = ncomp;
   P.c0 = 0;
-  P.nc_total = 1;
-  const int check_every = opt->check_every < 1 ? 1 : opt->check_every;
-  const int guess = opt->nonzero_guess;
-  const bool ahead = opt->run_ahead != 0;
-  const int64_t n = A->n_rows;
-  char *work_c = static_cast<char *>(work);
-  const KspLayout L = ksp_layout(A->n_rows, A->n_cols, 1, OX_KSP_CG_MG, ksp_grid_max(A));
-  KspCtx C{};
-  C.A = A;
-  C.S = reinterpret_cast<KspState *>(work_c + L.state);
-  C.S2 = reinterpret_cast<KspState *>(work_c + L.state2);
-  C.sums = reinterpret_cast<double *>(work_c + L.sums);
-  C.partial = reinterpret_cast<double *>(work_c + L.partial);
-  C.partial2 = reinterpret_cast<double *>(work_c + L.partial2);
-  C.dist = dist;
-  C.st = st;
-  C.nb = ox_vec_blocks(2 * (n > 0 ? n : 1));
-  C.nbs = ox_spmv_dist_nparts(A, dist, 1);
-  double *vec[6];
-  for (int i = 0; i < 6; ++i) vec[i] = reinterpret_cast<double *>(work_c + L.vec0 + L.vec_stride * i);
-  if (!g_state_host) OX_HIP(hipHostMalloc(&g_state_host, 3 * sizeof(KspState)));
-  KspVecs V{};
-  V.x = x, V.r = vec[0], V.z = vec[1], V.p = vec[2], V.q = vec[3];
-  double *zb = vec[4];  // B b (nonzero initial guess: the norm the relative test uses)
-  if (guess && !opt->ax0) {
-    if (ox_spmv_dist(A, x, V.q, 1, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
-  }
-  hipLaunchKernelGGL(k_mgcg_init, dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && opt->ax0) ? opt->ax0 : V.q, V.r, guess);
-  OX_LAUNCH_CHECK();
-  if (mg && guess && ox_mg_vcycle(mg, b, zb, nullptr, st)) return -1;
-  if (mg && ox_mg_vcycle(mg, V.r, V.z, nullptr, st)) return -1;
-  hipLaunchKernelGGL(k_mgcg_dots<true>, dim3(C.nb), dim3(256), 0, st, n, C.S, V.r, V.z, guess ? zb : V.z, V.p, C.partial);
-  OX_LAUNCH_CHECK();
-  KSP_SYNC(PH_CG_INIT, C.partial, C.nb, 3);
-  int it = 0;
-  auto it1 = [&](int count) -> int { return mgcg_iterations(mg, C, V, P, count); };
-  if (ahead) {
-    if (ksp_run_ahead(C, it1, check_every > 8 ? 8 : check_every, it, P.max_it)) return -1;
-  } else {
-    for (; it <= P.max_it; it += check_every) {
-      if (it1(check_every)) return -1;
-      if (ksp_read_state(C)) return -1;
-      if (g_state_host->done) break;
-    }
-  }
-  if (!g_state_host->done) OX_FAIL("ox_ksp_solve_mg: device state never reported completion");
-  result->reason[0] = g_state_host->reason[0];
-  result->its[0] = g_state_host->its[0];
-  result->rnorm[0] = g_state_host->rn[0];
-  result->bnorm[0] = g_state_host->bn[0];
+  P.nc_total = ncomp;
+  P.max_restarts = opt->max_restarts < 0 ? 0 : opt->max_restarts;
   return 0;
 }
 
-extern "C" int ox_ksp_solve_mg(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
-                               void *work, size_t work_bytes, ox_ksp_result *result, void *stream) {
-  if (!mg || !A || !b || !x || !work || !result || !opt) OX_FAIL("ox_ksp_solve_mg: null argument");
-  return mgcg_solve(mg, A, b, x, opt, work, work_bytes, result, nullptr, ox_stream(stream));
+// The ONE carve-up of `work` (ksp_layout) and the launch sizes of the vector kernels and the mat-vec's block sums
+static void ksp_ctx_init(KspCtx &C, int ksp_type, const ox_sell *A, const double *dinv, int ncomp, const ox_ksp_options *opt,
+                         char *work, const ox_dist *dist, hipStream_t st) {
+  const bool mg = ksp_type == OX_KSP_CG_MG;
+  const KspLayout L = ksp_layout(A->n_rows, A->n_cols, ncomp, ksp_type, ksp_grid_max(A));
+  C = KspCtx{};
+  C.type = ksp_type;
+  C.A = A;
+  C.dinv = dinv;
+  if (!mg) C.D = KspDinv{dinv, opt->dinv_code, opt->dinv_dict, opt->dinv_code ? opt->n_dinv_dict : 0};
+  C.mg = mg ? opt->mg : nullptr;
+  C.S = reinterpret_cast<KspState *>(work + L.state);
+  C.S2 = reinterpret_cast<KspState *>(work + L.state2);
+  C.sums = reinterpret_cast<double *>(work + L.sums);
+  C.partial = reinterpret_cast<double *>(work + L.partial);
+  C.partial2 = reinterpret_cast<double *>(work + L.partial2);
+  C.dist = dist;
+  C.st = st;
+  C.nb = ox_vec_blocks(2 * (A->n_rows > 0 ? A->n_rows : 1));  // one row per thread
+  C.nbs = ox_spmv_dist_nparts(A, dist, ncomp);
+  C.fold = mg ? 0 : ksp_fold_blocks_of(opt->fold_blocks);
+  for (int i = 0; i < L.nvec; ++i) C.vec[i] = reinterpret_cast<double *>(work + L.vec0 + L.vec_stride * i);
+  for (int i = 0; ncomp > 1 && i < 8; ++i) C.narrow[i] = reinterpret_cast<double *>(work + L.narrow0 + L.narrow_stride * i);
 }
 
-extern "C" int ox_ksp_solve_mg_dist(const ox_mg *mg, const ox_sell *A, const double *b, double *x, const ox_ksp_options *opt,
-                                    void *work, size_t work_bytes, ox_ksp_result *result, const ox_dist *dist,
-                                    void *stream) {
-  if (!A || !b || !x || !work || !result || !opt || !dist) OX_FAIL("ox_ksp_solve_mg_dist: null argument");
-  if (!mg && A->n_rows > 0) OX_FAIL("ox_ksp_solve_mg_dist: no hierarchy for %lld owned rows", (long long)A->n_rows);
-  return mgcg_solve(mg, A, b, x, opt, work, work_bytes, result, dist, ox_stream(stream));
+template <int NC>
+static int ksp_run(const KspCtx &C, const double *b, double *x, const KspParams &P, int guess, const double *ax0,
+                   int check_every, bool ahead, ox_ksp_result *result) {
+  const ox_sell *A = C.A;
+  const ox_dist *dist = C.dist;
+  hipStream_t st = C.st;
+  const int64_t n = A->n_rows;
+  double *const *vec = C.vec;
+  KspHost *H;
+  if (ksp_host(&H)) return -1;
+  const KspState *hs = H->state;  // [0]: the state ksp_iterate leaves for the host
+  const bool cg = C.type == OX_KSP_CG, cgs = C.type == OX_KSP_CG_SINGLE, bm = C.type == OX_KSP_BCGS_MERGED;
+  const bool cgm = C.type == OX_KSP_CG_MERGED;
+  KspVecs V{};
+  V.x = x;
+  if (C.type == OX_KSP_CG_MG) {
+    V.r = vec[0], V.z = vec[1], V.p = vec[2], V.q = vec[3];
+    double *zb = vec[4];  // B b (nonzero initial guess: the norm the relative test uses)
+    if (guess && !ax0) {
+      if (ox_spmv_dist(A, x, V.q, 1, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
+    }
+    hipLaunchKernelGGL(k_mgcg_init, dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && ax0) ? ax0 : V.q, V.r, guess);
+    OX_LAUNCH_CHECK();
+    if (C.mg && guess && ox_mg_vcycle(C.mg, b, zb, nullptr, st)) return -1;
+    if (C.mg && ox_mg_vcycle(C.mg, V.r, V.z, nullptr, st)) return -1;
+    hipLaunchKernelGGL(k_mgcg_dots<true>, dim3(C.nb), dim3(256), 0, st, n, C.S, V.r, V.z, guess ? zb : V.z, V.p, C.partial);
+    OX_LAUNCH_CHECK();
+    KSP_SYNC(PH_CG_INIT, C.partial, C.nb, 3);
+  } else if (cgs) {
+    V.r = vec[0], V.u = vec[1], V.p = vec[2], V.s = vec[3], V.w = vec[4];
+    if (guess && !ax0) {
+      if (ox_spmv_dist(A, x, V.w, NC, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
+    }
+    hipLaunchKernelGGL((k_cgs_init<NC>), dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && ax0) ? ax0 : V.w, C.dinv, V.r, V.u,
+                       V.p, V.s, guess, C.partial);
+    OX_LAUNCH_CHECK();
+    if (ox_spmv_dist(A, V.u, V.w, NC, OX_EPI_DOT, nullptr, nullptr, C.partial2, nullptr, dist, st)) return -1;
+    if (ksp_sync_point<PH_CGS_INIT>(C.S, C.partial, C.nb, 3 * NC, C.sums, P, dist, st, KspPart2{C.partial2, C.nbs, NC}))
+      return -1;
+  } else if (cg || cgm) {
+    V.r = vec[0], V.p = vec[1], V.q = vec[2];
+    if (guess && !ax0) {
+      if (ox_spmv_dist(A, x, V.q, NC, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
+    }
+    hipLaunchKernelGGL((k_cg_init<NC>), dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && ax0) ? ax0 : V.q, C.dinv, V.r,
+                       V.p, guess, C.partial);
+    OX_LAUNCH_CHECK();
+    KSP_SYNC(PH_CG_INIT, C.partial, C.nb, 3 * NC);
+  } else {
+    V.r = vec[0], V.rhat = vec[1], V.p = vec[2], V.v = vec[3], V.s = vec[4], V.t = vec[5];
+    if (guess && !ax0) {
+      if (ox_spmv_dist(A, x, V.t, NC, OX_EPI_NONE, nullptr, nullptr, nullptr, nullptr, dist, st)) return -1;
+    }
+    hipLaunchKernelGGL((k_bcgs_init<NC>), dim3(C.nb), dim3(256), 0, st, n, b, x, (guess && ax0) ? ax0 : V.t, C.dinv, V.r,
+                       V.rhat, V.p, V.v, guess, C.partial);
+    OX_LAUNCH_CHECK();
+    KSP_SYNC(PH_BCGS_INIT, C.partial, C.nb, 2 * NC);
+  }
+  bool first = true;  // the next iteration queued is the first of the solve (see ksp_iterations)
+  int it = 0;         // iterations queued so far
+  bool tail_done = false;  // the narrowed continuation applied the deferred updates of its column itself
+  // The merged-reduction BiCGStab re-enters this loop when the STORED residual of a column fails the test its
+  // recurrence norm passed (PH_BCGSM_FIN); every other method leaves it after one pass.
+  for (;;) {
+    tail_done = false;
+    // (several columns stay in lock-step with the host, so that the solve narrows at the iteration the check
+    // interval names)
+    if (ksp_iterate<NC>(C, V, P, check_every, ahead && NC == 1, it, first, H)) return -1;
+    int live = -1;
+    if (NC > 1 && !hs->done) live = ksp_last_live(hs, NC);
+    if (live >= 0) {
+      // Narrowing: the columns run in lockstep, so once all but one have converged the rest of
+      // the solve would drag NC-wide vectors along for nothing.  Extract the live column into
+      // compact vectors and continue with the 1-column kernels (same recurrences, same scalars:
+      // the state block is addressed through P.c0); insert x back at the end.
+      double *const *cv = C.narrow;
+      KspVecs W{};
+      double *src[8] = {V.x, V.r, V.z, V.p, V.q, V.rhat, V.v, nullptr};
+      double **dst[8] = {&W.x, &W.r, &W.z, &W.p, &W.q, &W.rhat, &W.v, nullptr};
+      if (cg) src[2] = nullptr;  // no z vector: the second update kernel forms D^-1 r itself
+      if (cgs) {  // x, r, u, p, s (a recurrence: carried over), w
+        src[2] = V.u, dst[2] = &W.u;
+        src[4] = V.s, dst[4] = &W.s;
+        src[5] = V.w, dst[5] = &W.w;
+        src[6] = nullptr;
+      }
+      for (int i = 0; i < 7; ++i) {
+        *dst[i] = cv[i];
+        if (!src[i]) continue;
+        hipLaunchKernelGGL(k_extract_col, dim3(C.nb), dim3(256), 0, st, n, src[i], NC, live, cv[i]);
+        OX_LAUNCH_CHECK();
+      }
+      if (!cgs) {
+        W.s = cv[2];  // BiCGStab temporaries share the slots CG uses for z and q
+        W.t = cv[4];
+      }
+      KspParams P1 = P;
+      P1.nc = 1;
+      P1.c0 = live;
+      it += check_every;
+      if (ksp_iterate<1>(C, W, P1, check_every, ahead, it, first, H)) return -1;
+      if (cg) {  // the last x += alpha p (see k_cg_update2)
+        hipLaunchKernelGGL((k_cg_update2<1>), dim3(C.nb), dim3(256), 0, st, n, C.S, P1.c0, W.x, W.r, C.D, W.p, 1);
+        OX_LAUNCH_CHECK();
+      }
+      if (bm && hs->its[live] > 0) {
+        if (bcgsm_finish<1>(C, W, P1)) return -1;
+        // (the re-test below reads the stored residuals of all columns from the NC-wide block)
+        hipLaunchKernelGGL(k_insert_col, dim3(C.nb), dim3(256), 0, st, n, W.r, NC, live, V.r);
+        OX_LAUNCH_CHECK();
+      }
+      tail_done = true;
+      hipLaunchKernelGGL(k_insert_col, dim3(C.nb), dim3(256), 0, st, n, W.x, NC, live, x);
+      OX_LAUNCH_CHECK();
+    }
+    if (!hs->done) OX_FAIL("ox_ksp_solve: device state never reported completion");
+    if (!bm) break;
+    bool any = false;
+    for (int c = 0; c < NC; ++c) any = any || hs->its[c] > 0;
+    if (!any) break;  // every column converged on the initial (stored) residual: nothing ran, nothing to re-test
+    // the x / r update of the last iteration (skipped by `done`)
+    if (!tail_done && bcgsm_finish<NC>(C, V, P)) return -1;
+    bool retest = false;
+    for (int c = 0; c < NC; ++c)
+      retest = retest || hs->reason[c] == OX_CONVERGED_RTOL || hs->reason[c] == OX_CONVERGED_ATOL;
+    if (!retest) break;
+    hipLaunchKernelGGL((k_rr<NC>), dim3(C.nb), dim3(256), 0, st, n, V.r, C.partial);
+    OX_LAUNCH_CHECK();
+    KSP_SYNC(PH_BCGSM_FIN, C.partial, C.nb, NC);
+    if (ksp_read_state(C, H)) return -1;
+    if (hs->done) break;  // every stored residual passes (or a column ran out of iterations)
+    // resume: rhat <- r, p <- r in the re-opened columns (k_bcgs_p reads the restart flags); p = r in the others
+    hipLaunchKernelGGL((k_bcgs_p<NC>), dim3(C.nb), dim3(256), 0, st, n, C.S, P.c0, V.r, V.p, V.v, V.rhat);
+    OX_LAUNCH_CHECK();
+    it = 0;
+    for (int c = 0; c < NC; ++c) it = hs->its[c] > it ? hs->its[c] : it;
+  }
+  if (cg && !tail_done) {  // the last x += alpha p (see k_cg_update2)
+    hipLaunchKernelGGL((k_cg_update2<NC>), dim3(C.nb), dim3(256), 0, st, n, C.S, P.c0, V.x, V.r, C.D, V.p, 1);
+    OX_LAUNCH_CHECK();
+  }
+  for (int c = 0; c < NC; ++c) {
+    result->reason[c] = hs->reason[c];
+    result->its[c] = hs->its[c];
+    result->rnorm[c] = hs->rn[c];
+    result->bnorm[c] = hs->bn[c];
+    result->resumed[c] = bm ? hs->nresume[c] : 0;
+  }
+  return 0;
 }
 
 extern "C" int ox_ksp_options_default(ox_ksp_options *o) {
@@ -1910,20 +1910,17 @@ extern "C" int ox_ksp_options_default(ox_ksp_options *o) {
 
 extern "C" int ox_ksp_default_fold_blocks(void) { return ksp_fold_blocks_default(); }
 
+// What one iteration of a run-ahead batch launches (reporting: bench.py), from ksp_form.  OX_KSP_CG_MG: -1 -- its
+// count is 6 plus the V-cycle's (ox_mg_kernels_per_cycle), and the caller has the hierarchy, this function has not.
 extern "C" int ox_ksp_kernels_per_iteration(int ksp_type, const ox_sell *A, int ncomp, int check_every, int fold_blocks,
                                             int partitioned) {
-  // what cg_iterations / cgm_iterations / ... launch per iteration for this operator (reporting: bench.py)
   if (!A) return -1;
   if (ksp_type == OX_KSP_CG_MERGED && ncomp > 1) ksp_type = OX_KSP_CG;
-  const bool one = ncomp == 1 && !partitioned && A->n_rows >= 2 && ksp_fold_blocks_of(fold_blocks) > 0;
-  const int batch = check_every > 8 ? 8 : (check_every < 1 ? 1 : check_every);
+  const KspForm form =
+      ksp_form(ksp_type, A, ncomp, partitioned != 0, ksp_fold_blocks_of(fold_blocks), ksp_batch(check_every));
   switch (ksp_type) {
-    case OX_KSP_CG: {
-      if (!one) return 5;
-      return ox_spmv_dist_nparts(A, nullptr, 1) >= OX_PRERED_MIN ? 4 : 3;  // (+ the pre-reduction of many block sums)
-    }
-    case OX_KSP_CG_MERGED:
-      return (one && (batch & 1) == 0 && ox_spmv_dist_nparts(A, nullptr, 1) <= 10 * OX_FOLD_T) ? 2 : 3;
+    case OX_KSP_CG: return form == KSP_CG_FOLDED ? 3 : (form == KSP_CG_FOLDED_PRERED ? 4 : 5);
+    case OX_KSP_CG_MERGED: return form == KSP_CGM_FOLDED ? 2 : 3;
     case OX_KSP_CG_SINGLE: return 3;
     case OX_KSP_BCGS: return 8;
     case OX_KSP_BCGS_MERGED: return 6;
@@ -1931,78 +1928,19 @@ extern "C" int ox_ksp_kernels_per_iteration(int ksp_type, const ox_sell *A, int 
   }
 }
 
-extern "C" int ox_ksp_solve_opt(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x, int ncomp,
-                                const ox_ksp_options *opt, void *work, size_t work_bytes, ox_ksp_result *result,
-                                const ox_dist *dist, void *stream) {
-  if (!A || !dinv || !b || !x || !work || !result || !opt) OX_FAIL("ox_ksp_solve: null argument");
-  if (ksp_type != OX_KSP_CG && ksp_type != OX_KSP_BCGS && ksp_type != OX_KSP_CG_SINGLE && ksp_type != OX_KSP_BCGS_MERGED &&
-      ksp_type != OX_KSP_CG_MERGED)
-    OX_FAIL("ox_ksp_solve: ksp_type=%d", ksp_type);
-  if (ksp_type == OX_KSP_CG_MERGED && ncomp > 1) ksp_type = OX_KSP_CG;  // (the merged form is the one-column solver)
-  if (ncomp < 1 || ncomp > OX_MAXC) OX_FAIL("ox_ksp_solve: ncomp=%d out of range", ncomp);
-  if (work_bytes < ox_ksp_work_bytes_for(A, ncomp, ksp_type))
-    OX_FAIL("ox_ksp_solve: workspace too small (%zu < %zu)", work_bytes, ox_ksp_work_bytes_for(A, ncomp, ksp_type));
-  if (opt->dinv_code && (!opt->dinv_dict || opt->n_dinv_dict < 1 || opt->n_dinv_dict > 256))
-    OX_FAIL("ox_ksp_solve: dinv dictionary of %d entries", opt->n_dinv_dict);
-  if (!(opt->divtol > 0.0)) OX_FAIL("ox_ksp_solve: divtol=%g (must be positive; PETSc's default is 1e4)", opt->divtol);
-  const int max_it = opt->max_it < 1 ? 1 : opt->max_it;
-  const int check_every = opt->check_every < 1 ? 1 : opt->check_every;
+extern "C" int ox_ksp_solve(int ksp_type, const ox_sell *A, const double *dinv, const double *b, double *x, int ncomp,
+                            const ox_ksp_options *opt, void *work, size_t work_bytes, ox_ksp_result *result,
+                            const ox_dist *dist, void *stream) {
+  KspParams P;
+  if (ksp_check_args(ksp_type, A, dinv, b, x, ncomp, opt, work, work_bytes, result, dist, P)) return -1;
   memset(result, 0, sizeof(*result));
-  KspParams P{};
-  P.rtol = opt->rtol;
-  P.atol = opt->atol;
-  P.dtol = opt->divtol;
-  P.max_it = max_it;
-  P.nc = ncomp;
-  P.c0 = 0;
-  P.nc_total = ncomp;
-  P.max_restarts = opt->max_restarts < 0 ? 0 : opt->max_restarts;
-  hipStream_t st = ox_stream(stream);
-  char *w = static_cast<char *>(work);
-  const KspDinv D{dinv, opt->dinv_code, opt->dinv_dict, opt->dinv_code ? opt->n_dinv_dict : 0};
-  const int fold = ksp_fold_blocks_of(opt->fold_blocks), ahead = opt->run_ahead < 0 ? 1 : (opt->run_ahead ? 1 : 0);
-  const int guess = opt->nonzero_guess;
-  const double *ax0 = opt->ax0;
+  KspCtx C;
+  ksp_ctx_init(C, ksp_type, A, dinv, ncomp, opt, static_cast<char *>(work), dist, ox_stream(stream));
+  const int every = opt->check_every < 1 ? 1 : opt->check_every, guess = opt->nonzero_guess;
+  const bool ahead = opt->run_ahead != 0;  // (-1: the default, on)
   switch (ncomp) {
-    case 1: return ksp_run<1>(ksp_type, A, dinv, b, x, P, guess, check_every, w, result, dist, st, ax0, D, fold, ahead);
-    case 2: return ksp_run<2>(ksp_type, A, dinv, b, x, P, guess, check_every, w, result, dist, st, ax0, D, fold, ahead);
-    default: return ksp_run<3>(ksp_type, A, dinv, b, x, P, guess, check_every, w, result, dist, st, ax0, D, fold, ahead);
+    case 1: return ksp_run<1>(C, b, x, P, guess, opt->ax0, every, ahead, result);
+    case 2: return ksp_run<2>(C, b, x, P, guess, opt->ax0, every, ahead, result);
+    default: return ksp_run<3>(C, b, x, P, guess, opt->ax0, every, ahead, result);
   }
-}
-
-extern "C" int ox_ksp_solve_dc(int ksp_type, const ox_sell *A, const double *dinv, const double *b,
-                               double *x, int ncomp, double rtol, double atol, int max_it,
-                               int nonzero_guess, int check_every, int max_restarts, void *work,
-                               size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, void *stream,
-                               const double *ax0, const uint8_t *dinv_code, const double *dinv_dict, int n_dinv_dict) {
-  ox_ksp_options o;
-  ox_ksp_options_default(&o);
-  o.rtol = rtol;
-  o.atol = atol;
-  o.max_it = max_it;
-  o.nonzero_guess = nonzero_guess;
-  o.check_every = check_every;
-  o.max_restarts = max_restarts;
-  o.ax0 = ax0;
-  o.dinv_code = dinv_code;
-  o.dinv_dict = dinv_dict;
-  o.n_dinv_dict = n_dinv_dict;
-  return ox_ksp_solve_opt(ksp_type, A, dinv, b, x, ncomp, &o, work, work_bytes, result, dist, stream);
-}
-
-extern "C" int ox_ksp_solve_ax0(int ksp_type, const ox_sell *A, const double *dinv, const double *b,
-                                double *x, int ncomp, double rtol, double atol, int max_it,
-                                int nonzero_guess, int check_every, int max_restarts, void *work,
-                                size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, void *stream,
-                                const double *ax0) {
-  return ox_ksp_solve_dc(ksp_type, A, dinv, b, x, ncomp, rtol, atol, max_it, nonzero_guess, check_every, max_restarts,
-                         work, work_bytes, result, dist, stream, ax0, nullptr, nullptr, 0);
-}
-
-extern "C" int ox_ksp_solve(int ksp_type, const ox_sell *A, const double *dinv, const double *b,
-                            double *x, int ncomp, double rtol, double atol, int max_it,
-                            int nonzero_guess, int check_every, int max_restarts, void *work,
-                            size_t work_bytes, ox_ksp_result *result, const ox_dist *dist, void *stream) {
-  return ox_ksp_solve_dc(ksp_type, A, dinv, b, x, ncomp, rtol, atol, max_it, nonzero_guess, check_every, max_restarts,
-                         work, work_bytes, result, dist, stream, nullptr, nullptr, nullptr, 0);
 }

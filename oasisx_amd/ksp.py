@@ -511,42 +511,59 @@ class KSPSolver:
         lib = _lib.load()
         A = self._A
         nc = X.nc
-        if self._gamg(nc) or self._bjacobi_gamg(nc):
-            return self._solve_gamg(B, X, ax0)
-        meth, rtol, atol, max_it, direct = self._method()
-        if meth in (_lib.KSP_CG, _lib.KSP_CG_SINGLE) and nc == 1 and self._cg_merged():
-            meth = _lib.KSP_CG_MERGED
-        guess = bool(self._options.get("ksp_initial_guess_nonzero", False)) and not direct
         st = _lib.current_stream()
         dev = X.dev().device
-        if self._dinv is None or self._dinv.shape[0] != A.pattern.n_rows:
-            self._dinv = torch.empty(A.pattern.n_rows, dtype=torch.float64, device=dev)
-            self._dinv_version = -1
-        self._audit_options(nc)
-        pc_key = (A.version, self._pc_none())
-        if self._dinv_version != pc_key:
-            if pc_key[1]:  # pc_type none: the identity through the same kernels
-                self._dinv.fill_(1.0)
-            else:
-                _lib.check(lib.ox_jacobi_setup(A.ref(), _lib.ptr(self._dinv), st), "ox_jacobi_setup")
-            self._dinv_version = pc_key
-            # a matrix that carries a value dictionary (la.SellMatrix.freeze: it will not change any more) has
-            # few distinct diagonal values too: the CG update kernels then read one byte of dinv per row
-            self._dcode = self._ddict = None
-            if A.vcode is not None and dev.type == "cuda":
-                code = torch.empty(A.pattern.n_rows, dtype=torch.uint8, device=dev)
-                vdict = torch.zeros(256, dtype=torch.float64, device=dev)
-                nd = C.c_int(0)
-                _lib.check(lib.ox_value_dictionary(_lib.ptr(self._dinv), A.pattern.n_rows, 1, _lib.ptr(code), _lib.ptr(vdict),
-                                                   C.byref(nd), st), "ox_value_dictionary")
-                if nd.value > 0:
-                    self._dcode, self._ddict = code, vdict[: nd.value]
+        opt = _lib.ox_ksp_options()
+        _lib.check(lib.ox_ksp_options_default(C.byref(opt)), "ox_ksp_options_default")
+        if self._gamg(nc) or self._bjacobi_gamg(nc):
+            # one-column CG preconditioned by the AMG V-cycle (OX_KSP_CG_MG); on a mesh-partitioned operator (pc_type
+            # bjacobi + sub_pc_type gamg) by the V-cycle of the rank's block
+            self._audit_options(1)
+            o = self._options
+            meth, direct, dinv = _lib.KSP_CG_MG, False, None
+            opt.mg = self._hierarchy().handle
+            opt.rtol, opt.atol, opt.max_it = float(o.get("ksp_rtol", 1e-5)), float(o.get("ksp_atol", 1e-50)), int(o.get("ksp_max_it", 10000))
+            guess = bool(o.get("ksp_initial_guess_nonzero", False))
+        else:
+            meth, opt.rtol, opt.atol, opt.max_it, direct = self._method()
+            if meth in (_lib.KSP_CG, _lib.KSP_CG_SINGLE) and nc == 1 and self._cg_merged():
+                meth = _lib.KSP_CG_MERGED
+            guess = bool(self._options.get("ksp_initial_guess_nonzero", False)) and not direct
+            if self._dinv is None or self._dinv.shape[0] != A.pattern.n_rows:
+                self._dinv = torch.empty(A.pattern.n_rows, dtype=torch.float64, device=dev)
+                self._dinv_version = -1
+            self._audit_options(nc)
+            pc_key = (A.version, self._pc_none())
+            if self._dinv_version != pc_key:
+                if pc_key[1]:  # pc_type none: the identity through the same kernels
+                    self._dinv.fill_(1.0)
+                else:
+                    _lib.check(lib.ox_jacobi_setup(A.ref(), _lib.ptr(self._dinv), st), "ox_jacobi_setup")
+                self._dinv_version = pc_key
+                # a matrix that carries a value dictionary (la.SellMatrix.freeze: it will not change any more) has
+                # few distinct diagonal values too: the CG update kernels then read one byte of dinv per row
+                self._dcode = self._ddict = None
+                if A.vcode is not None and dev.type == "cuda":
+                    code = torch.empty(A.pattern.n_rows, dtype=torch.uint8, device=dev)
+                    vdict = torch.zeros(256, dtype=torch.float64, device=dev)
+                    nd = C.c_int(0)
+                    _lib.check(lib.ox_value_dictionary(_lib.ptr(self._dinv), A.pattern.n_rows, 1, _lib.ptr(code), _lib.ptr(vdict),
+                                                       C.byref(nd), st), "ox_value_dictionary")
+                    if nd.value > 0:
+                        self._dcode, self._ddict = code, vdict[: nd.value]
+            dinv = _lib.ptr(self._dinv)
+            # a direct solver never breaks down: when one was asked for, let BiCGStab re-seed its shadow
+            # residual on a rho/omega breakdown; an explicit "bcgs" behaves like PETSc's (reason -5)
+            opt.max_restarts = int(self._options.get("ksp_bcgs_restarts", 5 if direct else 0))
+            opt.fold_blocks = self._fold_blocks()
+            if getattr(self, "_dcode", None) is not None:
+                opt.dinv_code, opt.dinv_dict = _lib.ptr(self._dcode), _lib.ptr(self._ddict)
+                opt.n_dinv_dict = int(self._ddict.shape[0])
         need = lib.ox_ksp_work_bytes_for(A.ref(), nc, meth)
         if self._work is None or self._work.shape[0] < need:
             self._work = torch.empty(int(need), dtype=torch.uint8, device=dev)
         g = self._guess_for(nc)
-        nonzero, ax0_ptr = self._guess_form(g, B, X, guess, ax0)
-        res = _lib.ox_ksp_result()
+        nonzero, opt.ax0 = self._guess_form(g, B, X, guess, ax0)
         # Iterations enqueued between two host reads of the device state (a read costs ~30 us of
         # idle GPU).  One right-hand side: amortise the read over ~1.5 ms of iterations, at most 16
         # (pressure CG: 14-16).  Several in lockstep: a column that has converged should leave the
@@ -555,24 +572,12 @@ class KSPSolver:
         key = (nc, meth)
         if key not in self._every:
             self._every[key] = self._interval_for(nc, meth)
-        every = self.check_every or self._every[key]
-        # a direct solver never breaks down: when one was asked for, let BiCGStab re-seed its shadow
-        # residual on a rho/omega breakdown; an explicit "bcgs" behaves like PETSc's (reason -5)
-        restarts = int(self._options.get("ksp_bcgs_restarts", 5 if direct else 0))
-        dcode = getattr(self, "_dcode", None)
-        opt = _lib.ox_ksp_options()
-        _lib.check(lib.ox_ksp_options_default(C.byref(opt)), "ox_ksp_options_default")
-        opt.rtol, opt.atol, opt.max_it = rtol, atol, max_it
+        opt.check_every = int(self.check_every or self._every[key])
         opt.divtol = float(self._options.get("ksp_divtol", 1e4))  # PETSc's default ("divergence=10000." in -ksp_view)
-        opt.nonzero_guess, opt.check_every, opt.max_restarts = int(nonzero), int(every), restarts
-        opt.fold_blocks, opt.run_ahead = self._fold_blocks(), self._run_ahead()
-        opt.ax0 = ax0_ptr
-        if dcode is not None:
-            opt.dinv_code, opt.dinv_dict = _lib.ptr(dcode), _lib.ptr(self._ddict)
-            opt.n_dinv_dict = int(self._ddict.shape[0])
-        _lib.check(lib.ox_ksp_solve_opt(meth, A.ref(), _lib.ptr(self._dinv), B.ptr(), X.ptr(), nc, C.byref(opt),
-                                        _lib.ptr(self._work), int(self._work.shape[0]), C.byref(res), A.pattern.dist, st),
-                   "ox_ksp_solve")
+        opt.nonzero_guess, opt.run_ahead = int(nonzero), self._run_ahead()
+        res = _lib.ox_ksp_result()
+        _lib.check(lib.ox_ksp_solve(meth, A.ref(), dinv, B.ptr(), X.ptr(), nc, C.byref(opt), _lib.ptr(self._work),
+                                    int(self._work.shape[0]), C.byref(res), A.pattern.dist, st), "ox_ksp_solve")
         if A.pattern.dist is not None:  # x.scatter_forward() (reference ksp.py:77)
             _lib.check(lib.ox_halo_forward(A.pattern.dist, X.ptr(), nc, st), "ox_halo_forward")
         self.last_result = res
@@ -582,49 +587,6 @@ class KSPSolver:
             reasons = [_lib.CONVERGED_ITS if r > 0 else r for r in reasons]
         if _truthy(self._options.get("ksp_error_if_not_converged", False)) and any(r <= 0 for r in reasons):
             raise KSPConvergenceError(self._prefix, reasons, [int(res.its[c]) for c in range(nc)])
-        return reasons
-
-    def _solve_gamg(self, B: FieldStorage, X: FieldStorage, ax0):
-        """One-column CG preconditioned by the AMG V-cycle (ox_ksp_solve_mg); on a mesh-partitioned operator (pc_type
-        bjacobi + sub_pc_type gamg) by the V-cycle of the rank's block (ox_ksp_solve_mg_dist)."""
-        lib = _lib.load()
-        A = self._A
-        self._audit_options(1)
-        mg = self._hierarchy()
-        o = self._options
-        rtol, atol, max_it = float(o.get("ksp_rtol", 1e-5)), float(o.get("ksp_atol", 1e-50)), int(o.get("ksp_max_it", 10000))
-        guess = bool(o.get("ksp_initial_guess_nonzero", False))
-        g = self._guess_for(1)
-        nonzero, ax0_ptr = self._guess_form(g, B, X, guess, ax0)
-        need = lib.ox_ksp_work_bytes_for(A.ref(), 1, _lib.KSP_CG_MG)
-        if self._work is None or self._work.shape[0] < need:
-            self._work = torch.empty(int(need), dtype=torch.uint8, device=X.dev().device)
-        key = (1, _lib.KSP_CG_MG)
-        if key not in self._every:
-            self._every[key] = self._interval_for(1, _lib.KSP_CG_MG)
-        every = self.check_every or self._every[key]
-        opt = _lib.ox_ksp_options()
-        _lib.check(lib.ox_ksp_options_default(C.byref(opt)), "ox_ksp_options_default")
-        opt.rtol, opt.atol, opt.max_it = rtol, atol, max_it
-        opt.divtol = float(o.get("ksp_divtol", 1e4))
-        opt.nonzero_guess, opt.check_every = int(nonzero), int(every)
-        opt.run_ahead = self._run_ahead()
-        opt.ax0 = ax0_ptr
-        res = _lib.ox_ksp_result()
-        st = _lib.current_stream()
-        if A.pattern.dist is None:
-            _lib.check(lib.ox_ksp_solve_mg(mg.handle, A.ref(), B.ptr(), X.ptr(), C.byref(opt), _lib.ptr(self._work),
-                                           int(self._work.shape[0]), C.byref(res), st), "ox_ksp_solve_mg")
-        else:
-            _lib.check(lib.ox_ksp_solve_mg_dist(mg.handle, A.ref(), B.ptr(), X.ptr(), C.byref(opt), _lib.ptr(self._work),
-                                                int(self._work.shape[0]), C.byref(res), A.pattern.dist, st),
-                       "ox_ksp_solve_mg_dist")
-            _lib.check(lib.ox_halo_forward(A.pattern.dist, X.ptr(), 1, st), "ox_halo_forward")  # x.scatter_forward()
-        self.last_result = res
-        reasons = [int(res.reason[0])]
-        self._guess_update(g, X, reasons)
-        if _truthy(o.get("ksp_error_if_not_converged", False)) and reasons[0] <= 0:
-            raise KSPConvergenceError(self._prefix, reasons, [int(res.its[0])])
         return reasons
 
     def _interval_for(self, nc: int, meth: int) -> int:

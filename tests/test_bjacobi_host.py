@@ -90,7 +90,7 @@ def test_bjacobi_jacobi_and_none_are_silent_remaps(caplog):
 
 
 def test_a_rank_without_owned_rows_has_an_empty_block_hierarchy():
-    """A rank that owns no rows: no device hierarchy (ox_ksp_solve_mg_dist gets none and still takes part in every
+    """A rank that owns no rows: no device hierarchy (ox_ksp_solve gets ``mg = NULL`` and still takes part in every
     exchange and all-reduce), a six-launch iteration, and the check interval still goes through the all-reduce."""
     import torch
 
@@ -213,7 +213,7 @@ def _bj_apply(blocks, r):
 
 
 def _pcg(A, b, prec, rtol=1e-10, max_it=5000):
-    """The one-column PCG of ox_ksp_solve_mg: the same recurrences and the test |B r| <= rtol |B b|."""
+    """The one-column PCG of OX_KSP_CG_MG: the same recurrences and the test |B r| <= rtol |B b|."""
     x = np.zeros_like(b)
     r = b.copy()
     z = prec(r)

@@ -39,7 +39,7 @@ ksp_error_if_not_converged.  n = 198 437 gives 776 partial rows in the vector ke
 4-rows-in-flight gather of PH_CG_INIT (3 sums), PH_CG_A and PH_CG_B (2 sums).
 
 Not covered: the reductions above 2560 partial rows for these phases, and sums over more than one rank's contribution
-(``ox_ksp_solve_mg_dist`` on a partitioned operator is cut on one-rank plans by tests/test_gpu_partitioned_cuts.py).
+(``OX_KSP_CG_MG`` on a partitioned operator is cut on one-rank plans by tests/test_gpu_partitioned_cuts.py).
 
 Measured on an MI355X (worst over the cases; relative max-norm, norms relative to |B b|):
     V-cycle z 3.9e-15 (two-deg1, b2); cut solves x 6.7e-15 (five, k = 3), bnorm 1.1e-16, rnorm 4.7e-15 (five, k = 1);

@@ -1,5 +1,5 @@
 """GPU: pc_type bjacobi + sub_pc_type gamg -- one block per rank, each preconditioned by one V-cycle of the hierarchy of
-the rank's owned-by-owned block (ox_ksp_solve_mg_dist).  On one GPU the path is exactly pc_type gamg; on eight rank
+the rank's owned-by-owned block (OX_KSP_CG_MG with a halo plan).  On one GPU the path is exactly pc_type gamg; on eight rank
 threads (the 2 x 2 x 2 split) and on 2-3 processes the partitioned IPCS steps match the serial Jacobi run on owned and
 ghost entries, with the same iteration counts on every rank."""
 import os

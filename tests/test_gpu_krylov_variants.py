@@ -95,7 +95,7 @@ def test_single_reduction_cg_nonzero_guess_and_max_it(hip):
 
 @pytest.mark.parametrize("kind,single", [("cg", False), ("cg", True), ("bcgs", False)])
 def test_supplied_first_matvec_gives_the_same_iterates(hip, kind, single):
-    """ox_ksp_solve_ax0: with A x0 handed in (the velocity update has M u* from its right-hand side,
+    """ox_ksp_options.ax0: with A x0 handed in (the velocity update has M u* from its right-hand side,
     the tentative solve gets A u1 from the fused assembly) the solver skips its first mat-vec and
     produces the same iterates bit for bit."""
     from oasisx_amd.fem import FieldStorage

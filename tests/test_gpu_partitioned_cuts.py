@@ -41,7 +41,7 @@ rows (784 with the overlap: 4 rows in flight in ksp_gather_t inside the partitio
 a partitioned point, 15 sums), 4104 (the 1024-thread block of k_ksp_reduce and k_ksp_scalar_p2p, where threads =
 max(ox_red_threads, ox_p2p_ar_threads)), and the 760-row control.  r0 is about n / 3.
 
-Block-Jacobi AMG on a partitioned operator (``ox_ksp_solve_mg_dist``): the "two-deg1" system of tests/amg_steps_model.py
+Block-Jacobi AMG on a partitioned operator (``OX_KSP_CG_MG`` with a halo plan): the "two-deg1" system of tests/amg_steps_model.py
 (12 709 rows, m = 131) ghosted from r0 = 4245 (66 interior + 133 boundary slices; the float64-against-extended
 precondition of tests/test_amg_steps_host.py holds there: tests/test_partitioned_systems_host.py), cut at k = 1 and 2
 and compared with ``amg_cg_trace(A_eff, levels of the owned block A_loc[:, :n])`` to the TOL of

@@ -91,6 +91,89 @@ def test_row_assembly_checks_its_arguments_before_any_device_call():
             "row_blocks=1", "n_row_blocks=0")
 
 
+def test_krylov_solve_has_one_entry_point():
+    """Every Krylov solve is ``ox_ksp_solve`` with an ``ox_ksp_options`` block: the per-feature names (the positional
+    forms, ``_opt``, and the AMG-CG pair, whose hierarchy is now the ``mg`` field) are not declared, bound or exported
+    any more, and the binding's options structure is the header's, field by field."""
+    from oasisx_amd import _lib
+
+    removed = ["ox_ksp_solve" + f for f in ("_ax0", "_dc", "_opt", "_mg", "_mg_dist")]
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "oasisx_hip.h")).read(), flags=re.S)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in removed:
+        assert not re.search(r"\b%s\b" % name, hdr) and name not in _lib.SIGNATURES and not hasattr(lib, name), name
+    decl = re.search(r"\bint ox_ksp_solve\s*\(([^)]*)\)", hdr)
+    assert decl and len(decl.group(1).split(",")) == 12
+    assert len(_lib.SIGNATURES["ox_ksp_solve"][1]) == 12 and hasattr(lib, "ox_ksp_solve")
+    # the header's layout: member declarations in order, natural alignment (what the C compiler does on this ABI)
+    body = re.search(r"typedef struct \{([^}]*)\}\s*ox_ksp_options;", hdr).group(1)
+    sizes = {"double": 8, "int32_t": 4}
+    fields, offset, align_max = [], 0, 1
+    for member in filter(None, (m.strip() for m in body.split(";"))):
+        ctype, names = re.match(r"(?:const\s+)?(\w+)\s+(.*)", member).groups()
+        for nm in (n.strip() for n in names.split(",")):
+            size = 8 if nm.startswith("*") else sizes[ctype]
+            offset = (offset + size - 1) // size * size + size
+            align_max = max(align_max, size)
+            fields.append(nm.lstrip("*"))
+    assert fields == ["rtol", "atol", "divtol", "max_it", "nonzero_guess", "check_every", "max_restarts", "fold_blocks",
+                      "run_ahead", "ax0", "dinv_code", "dinv_dict", "n_dinv_dict", "reserved", "mg"]
+    assert [f for f, _ in _lib.ox_ksp_options._fields_] == fields
+    assert ctypes.sizeof(_lib.ox_ksp_options) == (offset + align_max - 1) // align_max * align_max == 88
+
+
+def test_krylov_solve_checks_its_arguments_before_any_device_call():
+    """``ox_ksp_solve`` refuses NULL options, a NULL ``dinv`` with a Jacobi method, an unknown method, a column count out
+    of range, ``divtol = 0``, a workspace one byte short, a ``dinv`` dictionary of 0 or 257 entries, AMG-CG on two columns
+    and AMG-CG without a hierarchy on one GPU, each with a message that names the problem -- on the host, before the first
+    HIP call (this test runs without a device)."""
+    import ctypes as C
+
+    from oasisx_amd import _lib
+    from oasisx_amd.la import SellMatrix
+
+    lib = _lib.load()
+    m = M.create_unit_square(None, 3, 3, device="cpu")
+    V = fem.FunctionSpace(m, 1, window=64)
+    A = SellMatrix(V.pattern)
+    n = V.num_dofs
+    v = torch.zeros(n, 3, dtype=torch.float64)
+    code = torch.zeros(n, dtype=torch.uint8)
+    res = _lib.ox_ksp_result()
+
+    def options(**kw):
+        opt = _lib.ox_ksp_options()
+        C.memset(C.byref(opt), 0, C.sizeof(opt))
+        assert lib.ox_ksp_options_default(C.byref(opt)) == 0 and opt.mg is None and opt.divtol == 1e4
+        for k, val in kw.items():
+            setattr(opt, k, val)
+        return opt
+
+    def solve(meth=_lib.KSP_CG, nc=1, opt=None, dinv=v.data_ptr(), short=0, null_opt=False):
+        opt = options() if opt is None else opt
+        need = int(lib.ox_ksp_work_bytes_for(A.ref(), min(max(nc, 1), 3), meth if 1 <= meth <= 6 else _lib.KSP_CG))
+        work = torch.zeros(need, dtype=torch.uint8)
+        return lib.ox_ksp_solve(meth, A.ref(), dinv, v.data_ptr(), v.data_ptr(), nc, None if null_opt else C.byref(opt),
+                                work.data_ptr(), need - short, C.byref(res), None, None)
+
+    def refused(rc, *words):
+        msg = lib.ox_last_error().decode()
+        assert rc != 0 and all(w in msg for w in ("ox_ksp_solve:",) + words), (rc, msg)
+
+    refused(solve(null_opt=True), "null argument")
+    refused(solve(dinv=None), "null argument")
+    refused(solve(meth=99), "ksp_type=99")
+    refused(solve(nc=0), "ncomp=0")
+    refused(solve(nc=4), "ncomp=4")
+    refused(solve(opt=options(divtol=0.0)), "divtol=0")
+    refused(solve(short=1), "workspace too small")
+    for nd in (0, 257):
+        refused(solve(opt=options(dinv_code=code.data_ptr(), dinv_dict=v.data_ptr(), n_dinv_dict=nd)),
+                "dinv dictionary of %d entries" % nd)
+    refused(solve(meth=_lib.KSP_CG_MG, nc=2, dinv=None), "ncomp=2", "OX_KSP_CG_MG")
+    refused(solve(meth=_lib.KSP_CG_MG, dinv=None), "no hierarchy for %d owned rows" % n)
+
+
 def test_product_fails_loudly_without_gpu():
     """No CPU fallback: a compute call on a machine without a GPU raises, it does not emulate."""
     if torch.cuda.is_available():
