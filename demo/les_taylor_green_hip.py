@@ -7,7 +7,10 @@ the same initial data: with the constant viscosity alone, and with ``viscosity_m
 assembly kernel.  Per step the kinetic energy (1/2) u^T M u and the minimum / mean / maximum of ``nut`` are printed: the
 model takes energy out of the resolved field, so its run ends below the other.
 
-    python demo/les_taylor_green_hip.py [-N 16] [--steps 10] [--dt 0.005] [--nu 0.01] [--Cs 0.1677] [--wale]
+    python demo/les_taylor_green_hip.py [-N 16] [--steps 10] [--dt 0.005] [--nu 0.01] [--Cs 0.1677] [--wale] [--periodic]
+
+``--periodic``: the box periodic in all three axes (``oasisx_amd.mesh.make_periodic``) instead of the exact velocity pinned
+on its six faces -- the set-up the Taylor-Green vortex is usually run in; no Dirichlet condition at all.
 """
 from __future__ import annotations
 
@@ -36,7 +39,7 @@ def kinetic_energy(solver) -> float:
     return 0.5 * float((u[:n] * Mu[:n]).sum())
 
 
-def run(N: int, model, steps: int, dt: float, nu: float, degree_u: int = 2):
+def run(N: int, model, steps: int, dt: float, nu: float, degree_u: int = 2, periodic: bool = False):
     """``steps`` steps on the N^3 box; returns one record per step: energy and, with a model, min / mean / max of nut."""
     import oasisx_amd as ox
     from oasisx_amd import mesh as M
@@ -51,8 +54,12 @@ def run(N: int, model, steps: int, dt: float, nu: float, degree_u: int = 2):
     mesh = M.create_box(None, [[-1.0] * 3, [1.0] * 3], [N, N, N])
     G = ox.LocatorMethod.GEOMETRICAL
     kw = {} if model is None else {"viscosity_model": model}
-    solver = ox.FractionalStep_AB_CN(mesh, ("Lagrange", degree_u), ("Lagrange", degree_u - 1), bcs_p=[],
-                                     bcs_u=[[ox.DirichletBC(velocity(c), G, on_boundary)] for c in range(3)],
+    if periodic:
+        mesh = M.make_periodic(mesh, (0, 1, 2))
+        bcs_u = [[], [], []]
+    else:
+        bcs_u = [[ox.DirichletBC(velocity(c), G, on_boundary)] for c in range(3)]
+    solver = ox.FractionalStep_AB_CN(mesh, ("Lagrange", degree_u), ("Lagrange", degree_u - 1), bcs_p=[], bcs_u=bcs_u,
                                      solver_options=KRYLOV, **kw)
     for c in range(3):
         solver._u2[c].interpolate(velocity(c, -dt))
@@ -78,6 +85,7 @@ def main(argv=None):
     ap.add_argument("--nu", type=float, default=0.01)
     ap.add_argument("--Cs", type=float, default=0.1677)
     ap.add_argument("--wale", action="store_true", help="also run WALE (Cw = 0.325)")
+    ap.add_argument("--periodic", action="store_true", help="periodic in x, y and z instead of exact Dirichlet data")
     a = ap.parse_args(argv)
     import oasisx_amd as ox
 
@@ -86,9 +94,10 @@ def main(argv=None):
         models["wale"] = ox.Wale()
     out = {}
     for name, model in models.items():
-        print(f"--- {name}: N = {a.N}, dt = {a.dt}, nu = {a.nu}" + ("" if model is None else f", {model!r}"))
+        print(f"--- {name}: N = {a.N}, dt = {a.dt}, nu = {a.nu}" + ("" if model is None else f", {model!r}")
+              + (", periodic" if a.periodic else ""))
         print(f"{'step':>5} {'kinetic energy':>20} {'nut min':>12} {'nut mean':>12} {'nut max':>12}")
-        out[name] = run(a.N, model, a.steps, a.dt, a.nu)
+        out[name] = run(a.N, model, a.steps, a.dt, a.nu, periodic=a.periodic)
         for r in out[name]:
             nut = "" if model is None else f" {r['nut_min']:>12.4e} {r['nut_mean']:>12.4e} {r['nut_max']:>12.4e}"
             print(f"{r['step']:>5} {r['energy']:>20.12e}{nut}")

@@ -306,6 +306,25 @@ int ox_mesh_create_sub(const double *coords, int64_t n_vertices, const int32_t *
                        int64_t n_cells_whole, ox_mesh **out);
 int ox_space_create_part(const ox_mesh *mesh, int degree, int window, const int32_t *owner, int64_t n_initial, int rank,
                          int64_t n_dofs_whole, ox_space **out);
+/* A mesh with PERIODIC boundaries: faces of its bounding box identified by axis-aligned translations (DESIGN.md,
+ * "Periodic boundaries").  coords / cells are the geometric mesh as for ox_mesh_create: cell order, cell geometry and
+ * everything that reads points (the cell locator, output) use them.  topo_cells [n_cells][gdim+1] int32 lists the same
+ * cells over vertex CLASSES 0 .. n_topo_vertices - 1 (identified vertices share a class; every class must occur, every
+ * id is range-checked): spaces created on the mesh take their edge keys, initial dof ids, pattern and adjacency from
+ * it, so identified vertices and edges are ONE dof and every row is assembled completely by the row kernels.  The
+ * caller guarantees that two distinct geometric edges of non-identified position never join the same two classes (at
+ * least three cells across every periodic axis).
+ *   hi_cut [3]     per axis: hi_k - tolerance on a periodic axis, +infinity (HUGE_VAL) on the others.  Dof
+ *                  coordinates (ox_space_info.x) are written from the (cell, local node) pairs whose node lies below
+ *                  hi_cut on every axis: x[:, k] is in [lo_k, hi_k) on periodic axes, and the midpoint of an edge that
+ *                  crosses the seam lies at the seam, not in the middle of the domain.
+ * On such a mesh ox_space_info.n_dofs is the reduced count, rank_initial / edge_keys are indexed by vertex class
+ * (class id, or n_topo_vertices + edge id; keys min_class * n_topo_vertices + max_class).  Degree 1 and 2, one GPU:
+ * ox_space_create with degree 3 and ox_space_create_part refuse the mesh; ox_space_create fails when some dof has no
+ * image below hi_cut on every axis (hi_cut or topo_cells do not describe the mesh). */
+int ox_mesh_create_periodic(const double *coords, int64_t n_vertices, const int32_t *cells, const int32_t *topo_cells,
+                            int64_t n_topo_vertices, int64_t n_cells, int gdim, int on_device, int tile_bits,
+                            const double *hi_cut, ox_mesh **out);
 int ox_space_view(const ox_space *space, ox_space_info *view);
 /* LDS-window stream of the space's square pattern (M, K, A share it), built on the first call and owned by the space:
  * copy the pointers into the ox_sell of every matrix on the pattern (the value codes of a dictionary matrix are
@@ -341,6 +360,11 @@ int ox_pair_stream_size(const ox_sell *A, const int32_t *row_len, int64_t *ps_pt
 int ox_window_retile(const ox_sell *A, const int64_t *wt_ptr, const void *src, int elem_bytes, void *dst, void *stream);
 int ox_pair_stream_fill(const ox_sell *A, const int32_t *row_len, int64_t *ps_ptr, uint32_t *ps_code,
                         int32_t *ps_base, int64_t *n_wide, void *stream);
+/* Unfolded copy of a field on a periodic mesh, for output: dst [n_images][ncomp] = src [n_src][ncomp] read through
+ * image_dof [n_images] (the dof of every geometric image of a node: the points a writer lists); an index outside
+ * [0, n_src) gives NaN.  All device pointers. */
+int ox_gather_images(const double *src, int64_t n_src, const int32_t *image_dof, int64_t n_images, int ncomp, double *dst,
+                     void *stream);
 /* plain device memory for callers without a device array library (numpy + ctypes) */
 int ox_malloc(size_t bytes, void **out);
 int ox_free(void *p);

@@ -273,6 +273,7 @@ SIGNATURES = {
     "ox_device_info": (_I, [C.POINTER(_I), C.c_char_p, _I]),
     "ox_mesh_create": (_I, [_P, _L, _P, _L, _I, _I, _I, C.POINTER(_P)]),
     "ox_mesh_view": (_I, [_P, C.POINTER(ox_mesh_info)]),
+    "ox_mesh_create_periodic": (_I, [_P, _L, _P, _P, _L, _L, _I, _I, _I, C.POINTER(_D), C.POINTER(_P)]),
     "ox_mesh_destroy": (_I, [_P]),
     "ox_space_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
     "ox_space_create_ordered": (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
@@ -288,6 +289,7 @@ SIGNATURES = {
     "ox_value_dictionary": (_I, [_P, _L, _I, _P, _P, C.POINTER(_I), _P]),
     "ox_pair_stream_size": (_I, [C.POINTER(ox_sell), _P, _P, C.POINTER(_L), _P]),
     "ox_pair_stream_fill": (_I, [C.POINTER(ox_sell), _P, _P, _P, _P, C.POINTER(_L), _P]),
+    "ox_gather_images": (_I, [_P, _L, _P, _L, _I, _P, _P]),
     "ox_malloc": (_I, [C.c_size_t, C.POINTER(_P)]),
     "ox_free": (_I, [_P]),
     "ox_memset": (_I, [_P, _I, C.c_size_t, _P]),

@@ -190,6 +190,10 @@ class PressureBC:
         else:
             facets = tags.find(np.int32(self._subdomain_id))
         self._facets = np.asarray(facets, dtype=np.int64)
+        per = getattr(mesh, "periodic", None)
+        if per is not None and per.is_periodic_facet(self._facets).any():
+            raise ValueError("PressureBC: some of the facets lie on an identified (periodic) face; a pressure condition "
+                             "is set on exterior facets")
         # facet -> (cell, opposite local vertex)
         _, cf = mesh._entities(d - 1)
         combos = list(itertools.combinations(range(d + 1), d))

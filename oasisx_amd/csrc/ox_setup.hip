@@ -359,6 +359,44 @@ __global__ __launch_bounds__(256) void k_dof_coords(const double *__restrict__ c
   }
 }
 
+// periodic meshes: dof coordinates from the (geometric cell, local node) pairs.  Exactly one image of a dof lies below
+// cut[k] on every periodic axis -- the master image, in [lo_k, hi_k); every pair that shows it writes the same bits (a
+// vertex's own coordinates, or 0.5 * (a + b) of one geometric edge), the other pairs write nothing.
+struct Cut3 {
+  double c[3];
+};
+__global__ __launch_bounds__(256) void k_dof_coords_periodic(const double *__restrict__ coords, const int32_t *__restrict__ cells,
+                                                             const int32_t *__restrict__ cd0, int64_t nc, int d, int nd,
+                                                             Cut3 cut, int64_t n, double *__restrict__ x) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nc * nd) return;
+  const int64_t c = i / nd;
+  const int j = (int)(i - c * nd), nv = d + 1;
+  double p[3];
+  if (j < nv) {
+    const int64_t v = cells[c * nv + j];
+    for (int k = 0; k < d; ++k) p[k] = coords[v * d + k];
+  } else {
+    const int e = j - nv;
+    const int64_t a = cells[c * nv + (d == 2 ? EDGE2[e][0] : EDGE3[e][0])], b = cells[c * nv + (d == 2 ? EDGE2[e][1] : EDGE3[e][1])];
+    for (int k = 0; k < d; ++k) p[k] = 0.5 * (coords[a * d + k] + coords[b * d + k]);
+  }
+  for (int k = 0; k < d; ++k)
+    if (!(p[k] < cut.c[k])) return;
+  const int64_t dof = cd0[i];
+  if (dof < 0 || dof >= n) return;
+  for (int k = 0; k < d; ++k) x[dof * d + k] = p[k];
+}
+
+// 1 where a dof's coordinates were left unwritten (the NaN the buffer was filled with)
+__global__ __launch_bounds__(256) void k_flag_unwritten(const double *__restrict__ x, int64_t n, int d, int32_t *__restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  int bad = 0;
+  for (int k = 0; k < d; ++k) bad |= !(x[i * d + k] == x[i * d + k]);
+  flag[i] = bad;
+}
+
 __global__ __launch_bounds__(256) void k_invert(const int32_t *__restrict__ perm, int64_t n, int32_t *__restrict__ rank) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) rank[perm[i]] = (int32_t)i;
@@ -622,6 +660,12 @@ struct ox_mesh {
   DevBuf cells;      // [nc][gdim+1] int32, KERNEL order
   DevBuf cell_perm;  // [nc] int32: kernel index -> caller's cell index
   DevBuf geom;       // [nc][gs]
+  // periodic meshes (ox_mesh_create_periodic): the cells over vertex CLASSES, what dofs are numbered from
+  DevBuf tcells;     // [nc][gdim+1] int32, KERNEL order; empty on any other mesh
+  int64_t nvt = 0;   // vertex classes
+  double cut[3] = {0, 0, 0};  // a node with x_k >= cut[k] is the hi-face image of a dof (+inf on the other axes)
+  const int32_t *topo() const { return tcells.p ? tcells.as<int32_t>() : cells.as<int32_t>(); }
+  int64_t n_topo() const { return tcells.p ? nvt : nv; }
 };
 
 struct ox_pattern_store {  // SELL-64 pattern + 16-bit stream + width bins
@@ -862,7 +906,8 @@ struct MeshFrame {
   int64_t n_cells_ref;
 };
 static int mesh_create_impl(const double *coords, int64_t n_vertices, const int32_t *cells, int64_t n_cells, int gdim,
-                            int on_device, int tile_bits, const MeshFrame *frame, ox_mesh **out) {
+                            int on_device, int tile_bits, const MeshFrame *frame, ox_mesh **out,
+                            const int32_t *topo_cells = nullptr, int64_t n_topo_vertices = 0, const double *cut = nullptr) {
   if (!coords || !cells || !out) OX_FAIL("ox_mesh_create: null argument");
   if (gdim != 2 && gdim != 3) OX_FAIL("ox_mesh_create: gdim=%d (triangles or tetrahedra)", gdim);
   if (n_vertices < gdim + 1 || n_cells < 1) OX_FAIL("ox_mesh_create: empty mesh");
@@ -963,6 +1008,18 @@ static int mesh_create_impl(const double *coords, int64_t n_vertices, const int3
   hipLaunchKernelGGL(k_gather_cells, dim3(nblk(n_cells)), dim3(256), 0, st, cells_in.as<int32_t>(), M->cell_perm.as<int32_t>(),
                      n_cells, nv, M->cells.as<int32_t>());
   OX_LAUNCH_CHECK();
+  if (topo_cells) {  // the same cells over vertex classes, in the same (kernel) order
+    DevBuf t_in;
+    OX_TRY(t_in.alloc(sizeof(int32_t) * (size_t)n_cells * nv));
+    OX_HIP(hipMemcpy(t_in.p, topo_cells, t_in.bytes, kind));
+    OX_TRY(M->tcells.alloc(sizeof(int32_t) * (size_t)n_cells * nv));
+    hipLaunchKernelGGL(k_gather_cells, dim3(nblk(n_cells)), dim3(256), 0, st, t_in.as<int32_t>(), M->cell_perm.as<int32_t>(),
+                       n_cells, nv, M->tcells.as<int32_t>());
+    OX_LAUNCH_CHECK();
+    OX_HIP(hipStreamSynchronize(st));  // (t_in is released at the end of this scope)
+    M->nvt = n_topo_vertices;
+    for (int k = 0; k < 3; ++k) M->cut[k] = k < gdim ? cut[k] : HUGE_VAL;
+  }
   const int gs = gdim == 2 ? 6 : 10;
   OX_TRY(M->geom.alloc(sizeof(double) * (size_t)n_cells * gs));
   hipLaunchKernelGGL(k_geometry, dim3(nblk(n_cells)), dim3(256), 0, st, M->coords.as<double>(), M->cells.as<int32_t>(), n_cells,
@@ -989,6 +1046,32 @@ extern "C" int ox_mesh_create_sub(const double *coords, int64_t n_vertices, cons
   for (int k = 0; k < 3; ++k) F.lo[k] = k < gdim ? lo[k] : 0.0, F.span[k] = k < gdim ? span[k] : 1.0;
   F.lattice = lattice ? 1 : 0, F.tile_bits = tile_bits, F.n_cells_ref = n_cells_whole;
   return mesh_create_impl(coords, n_vertices, cells, n_cells, gdim, on_device, tile_bits, &F, out);
+}
+
+// host copy of an index table and its range check: ids outside [0, n) would index past the dof arrays
+static int check_index_range(const int32_t *idx, int64_t count, int on_device, int64_t n, const char *who) {
+  std::vector<int32_t> h((size_t)count);
+  OX_HIP(hipMemcpy(h.data(), idx, sizeof(int32_t) * (size_t)count, on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+  std::vector<char> seen((size_t)n, 0);
+  for (int64_t i = 0; i < count; ++i) {
+    if (h[i] < 0 || h[i] >= n) OX_FAIL("%s: index %d at position %lld is outside [0, %lld)", who, h[i], (long long)i, (long long)n);
+    seen[h[i]] = 1;
+  }
+  for (int64_t v = 0; v < n; ++v)
+    if (!seen[v]) OX_FAIL("%s: vertex class %lld belongs to no cell", who, (long long)v);
+  return 0;
+}
+
+extern "C" int ox_mesh_create_periodic(const double *coords, int64_t n_vertices, const int32_t *cells, const int32_t *topo_cells,
+                                       int64_t n_topo_vertices, int64_t n_cells, int gdim, int on_device, int tile_bits,
+                                       const double *hi_cut, ox_mesh **out) {
+  if (!topo_cells || !hi_cut) OX_FAIL("ox_mesh_create_periodic: null argument");
+  if (gdim != 2 && gdim != 3) OX_FAIL("ox_mesh_create_periodic: gdim=%d (triangles or tetrahedra)", gdim);
+  if (n_cells < 1 || n_topo_vertices < 1 || n_topo_vertices > n_vertices)
+    OX_FAIL("ox_mesh_create_periodic: %lld vertex classes of %lld vertices", (long long)n_topo_vertices, (long long)n_vertices);
+  OX_TRY(check_index_range(topo_cells, n_cells * (gdim + 1), on_device, n_topo_vertices, "ox_mesh_create_periodic"));
+  return mesh_create_impl(coords, n_vertices, cells, n_cells, gdim, on_device, tile_bits, nullptr, out, topo_cells, n_topo_vertices,
+                          hi_cut);
 }
 
 extern "C" int ox_mesh_destroy(ox_mesh *M) {
@@ -1042,6 +1125,11 @@ static int space_create_impl(const ox_mesh *M, int degree, int window, const int
   if (!M || !out) OX_FAIL("ox_space_create: null argument");
   if (degree < 1 || degree > 3) OX_FAIL("ox_space_create: Lagrange degree %d (1, 2 and -- on triangles -- 3 are built)", degree);
   if (window < SLICE) window = 4096;
+  const bool periodic = M->tcells.p != nullptr;
+  if (periodic && (degree == 3 || owner)) OX_FAIL("ox_space_create: a periodic mesh takes degree 1 and 2 on one GPU");
+  // dofs are numbered from the cells over vertex classes (the cells themselves unless the mesh is periodic)
+  const int32_t *tc = M->topo();
+  const int64_t nvt = M->n_topo();
   hipStream_t st = nullptr;
   ox_space *V = new ox_space();
   struct Guard {
@@ -1064,11 +1152,11 @@ static int space_create_impl(const ox_mesh *M, int degree, int window, const int
       OX_TRY(k_out.alloc(sizeof(uint64_t) * (size_t)nk));
       OX_TRY(v_in.alloc(sizeof(int32_t) * (size_t)nk));
       OX_TRY(v_out.alloc(sizeof(int32_t) * (size_t)nk));
-      hipLaunchKernelGGL(k_edge_keys, dim3(nblk(nk)), dim3(256), 0, st, M->cells.as<int32_t>(), nc, d, M->nv, k_in.as<uint64_t>(),
+      hipLaunchKernelGGL(k_edge_keys, dim3(nblk(nk)), dim3(256), 0, st, tc, nc, d, nvt, k_in.as<uint64_t>(),
                          v_in.as<int32_t>());
       OX_LAUNCH_CHECK();
       OX_TRY(sort_pairs(k_in.as<uint64_t>(), k_out.as<uint64_t>(), v_in.as<int32_t>(), v_out.as<int32_t>(), (size_t)nk,
-                        bits_for((uint64_t)M->nv * (uint64_t)M->nv), st));
+                        bits_for((uint64_t)nvt * (uint64_t)nvt), st));
       k_in.release();
       v_in.release();
       OX_TRY(head.alloc(sizeof(int64_t) * (size_t)nk));
@@ -1119,12 +1207,12 @@ static int space_create_impl(const ox_mesh *M, int degree, int window, const int
       OX_LAUNCH_CHECK();
       OX_HIP(hipStreamSynchronize(st));
     }
-    hipLaunchKernelGGL(k_cd0, dim3(nblk(nc)), dim3(256), 0, st, M->cells.as<int32_t>(), cell_edges.as<int32_t>(), nc, d, degree,
-                       M->nv, V->n_edges, cd0.as<int32_t>(), cell_faces.as<int32_t>(), M->cell_perm.as<int32_t>());
+    hipLaunchKernelGGL(k_cd0, dim3(nblk(nc)), dim3(256), 0, st, tc, cell_edges.as<int32_t>(), nc, d, degree,
+                       nvt, V->n_edges, cd0.as<int32_t>(), cell_faces.as<int32_t>(), M->cell_perm.as<int32_t>());
     OX_LAUNCH_CHECK();
     OX_HIP(hipStreamSynchronize(st));
   }
-  const int64_t n = degree == 3 ? M->nv + 2 * V->n_edges + (d == 3 ? V->n_faces : nc) : M->nv + V->n_edges;
+  const int64_t n = degree == 3 ? M->nv + 2 * V->n_edges + (d == 3 ? V->n_faces : nc) : nvt + V->n_edges;
   if (n >= ((int64_t)1 << 31) - 64) OX_FAIL("ox_space_create: %lld dofs exceed int32", (long long)n);
   V->n = n;
   if (owner && n != n_initial)
@@ -1148,12 +1236,30 @@ static int space_create_impl(const ox_mesh *M, int degree, int window, const int
     hipLaunchKernelGGL(k_invert, dim3(nblk(nc)), dim3(256), 0, st, M->cell_perm.as<int32_t>(), nc, cell_kidx.as<int32_t>());
     OX_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_dof_coords, dim3(nblk(n)), dim3(256), 0, st, M->coords.as<double>(), V->edge_keys.as<uint64_t>(), M->nv, n,
-                     d, xL.as<double>(), degree, V->n_edges, M->cells.as<int32_t>(), V->face_keys.as<uint64_t>(),
-                     cell_kidx.as<int32_t>());
+  if (periodic) {
+    Cut3 cut;
+    for (int k = 0; k < 3; ++k) cut.c[k] = M->cut[k];
+    OX_HIP(hipMemsetAsync(xL.p, 0xFF, xL.bytes, st));  // (NaN: a dof no pair wrote would show)
+    hipLaunchKernelGGL(k_dof_coords_periodic, dim3(nblk(nc * nd)), dim3(256), 0, st, M->coords.as<double>(), M->cells.as<int32_t>(),
+                       cd0.as<int32_t>(), nc, d, nd, cut, n, xL.as<double>());
+  } else
+    hipLaunchKernelGGL(k_dof_coords, dim3(nblk(n)), dim3(256), 0, st, M->coords.as<double>(), V->edge_keys.as<uint64_t>(), M->nv, n,
+                       d, xL.as<double>(), degree, V->n_edges, M->cells.as<int32_t>(), V->face_keys.as<uint64_t>(),
+                       cell_kidx.as<int32_t>());
   OX_LAUNCH_CHECK();
   OX_HIP(hipStreamSynchronize(st));  // (cell_kidx is released at the end of this scope's caller: finish the launch first)
   OX_LAUNCH_CHECK();
+  if (periodic) {  // every dof must have a master image below hi_cut: a wrong hi_cut or table would order garbage silently
+    DevBuf flag;
+    int64_t n_bad = 0;
+    OX_TRY(flag.alloc(sizeof(int32_t) * (size_t)n));
+    hipLaunchKernelGGL(k_flag_unwritten, dim3(nblk(n)), dim3(256), 0, st, xL.as<double>(), n, d, flag.as<int32_t>());
+    OX_LAUNCH_CHECK();
+    OX_TRY(reduce_sum_i32(flag.as<int32_t>(), n, &n_bad, st));
+    if (n_bad)
+      OX_FAIL("ox_space_create: %lld of %lld dofs of the periodic mesh have no image below hi_cut on every axis (hi_cut or "
+              "topo_cells do not describe the mesh)", (long long)n_bad, (long long)n);
+  }
   OX_TRY(rank1.alloc(sizeof(int32_t) * (size_t)n));
   {
     const KeySpec K = key_spec(M, M->tile_bits, owner ? n_dofs_whole : n, brick != 0);
@@ -2032,6 +2138,31 @@ extern "C" int ox_pair_stream_fill(const ox_sell *A, const int32_t *row_len, int
   OX_HIP(hipMemcpyAsync(&h, cnt.p, sizeof(h), hipMemcpyDeviceToHost, st));
   OX_HIP(hipStreamSynchronize(st));
   if (n_wide) *n_wide = (int64_t)h;
+  return 0;
+}
+
+// ---- unfolded output of a periodic field (include/oasisx_hip.h, ox_gather_images) --------------------------
+namespace {
+__global__ __launch_bounds__(256) void k_gather_images(const double *__restrict__ src, int64_t n_src,
+                                                       const int32_t *__restrict__ image_dof, int64_t n_images, int ncomp,
+                                                       double *__restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_images * ncomp) return;
+  const int64_t g = i / ncomp;
+  const int c = (int)(i - g * ncomp);
+  const int64_t dof = image_dof[g];
+  dst[i] = (dof >= 0 && dof < n_src) ? src[dof * ncomp + c] : __longlong_as_double(0x7ff8000000000000ll);
+}
+}  // namespace
+
+extern "C" int ox_gather_images(const double *src, int64_t n_src, const int32_t *image_dof, int64_t n_images, int ncomp,
+                                double *dst, void *stream) {
+  if (n_images <= 0) return 0;
+  if (!src || !image_dof || !dst) OX_FAIL("ox_gather_images: null argument");
+  if (ncomp < 1 || n_src < 1) OX_FAIL("ox_gather_images: ncomp=%d, n_src=%lld", ncomp, (long long)n_src);
+  hipLaunchKernelGGL(k_gather_images, dim3(nblk(n_images * ncomp)), dim3(256), 0, ox_stream(stream), src, n_src, image_dof,
+                     n_images, ncomp, dst);
+  OX_LAUNCH_CHECK();
   return 0;
 }
 

@@ -215,6 +215,26 @@ def row_blocks(widths: np.ndarray):
     return np.asarray(blk, dtype=np.int32), int(big)
 
 
+def periodic_dof_coordinates(mesh: Mesh, local_cells, cd0, n: int, degree: int) -> torch.Tensor:
+    """Coordinates of the initial dofs of a periodic mesh, written from the (geometric cell, local node) pairs: the vertex
+    coordinates of an edge key would put the midpoint of an edge across the seam into the middle of the domain.  Of
+    the images of a dof exactly one lies in [lo_k, hi_k) on every periodic axis k -- the master image; every pair that
+    shows it writes the same bits, the others write nothing (csrc/ox_setup.hip, k_dof_coords_periodic, is the twin)."""
+    per, d, dev = mesh.periodic, mesh.gdim, mesh.device
+    X = mesh.coords[mesh.cells[local_cells]]  # (nc, d+1, d)
+    if degree == 2:
+        ea = torch.tensor([e[0] for e in local_edges(d)], device=dev)
+        eb = torch.tensor([e[1] for e in local_edges(d)], device=dev)
+        X = torch.cat([X, 0.5 * (X[:, ea] + X[:, eb])], dim=1)
+    cut = torch.full((d,), float("inf"), dtype=torch.float64, device=dev)
+    for k in per.axes:
+        cut[k] = float(per.hi[k] - per.atol[k])
+    keep = (X < cut).all(dim=2)
+    x = torch.full((n, d), float("nan"), dtype=torch.float64, device=dev)
+    x[cd0[keep]] = X[keep]
+    return x
+
+
 class SellPattern:
     """SELL-64 sparsity pattern shared by every matrix on one (row space, col space)."""
 
@@ -511,6 +531,13 @@ class FunctionSpace:
         if brick is None:
             brick = _os.environ.get("OX_BRICK", "0") == "1"
         self.brick = bool(brick) and part is None
+        per = getattr(mesh, "periodic", None)
+        if per is not None:
+            # (before any collective or device work, as the partition refusals)
+            if part is not None or getattr(mesh.comm, "size", 1) > 1:
+                raise NotImplementedError("a periodic mesh on more than one rank: periodic spaces are built on one GPU")
+            if degree == 3:
+                raise NotImplementedError("Lagrange degree 3 on a periodic mesh: degree 1 and 2 are built")
         self.mesh = mesh
         self.degree = degree
         self.element = _Element(degree, mesh.gdim)
@@ -530,7 +557,8 @@ class FunctionSpace:
             raise NotImplementedError("Lagrange degree 3 spaces are built by the library (GPU hosts); the torch twin "
                                       "of the set-up covers degree 1 and 2")
         d = mesh.gdim
-        nverts = mesh.num_vertices
+        # initial dof ids count vertex CLASSES on a periodic mesh (mesh.topological_cells), vertices otherwise
+        nverts = mesh.num_vertices if per is None else per.n_free_vertices
         rank = 0 if part is None else part.rank
         # ---- 1. global initial dof ids: vertices, then edges; restricted to the local cells ----
         lo = mesh.coords.min(dim=0).values
@@ -543,7 +571,7 @@ class FunctionSpace:
         # kernel-side cell order: tiled order of the centroids (index i of every per-cell array = this list's i)
         self.local_cells = cell_ids[torch.argsort(ckey, stable=True)]
         del ckey
-        cells = mesh.cells[self.local_cells]
+        cells = mesh.topological_cells()[self.local_cells]
         nc = int(cells.shape[0])
         if degree == 1:
             cd0g = cells
@@ -583,10 +611,13 @@ class FunctionSpace:
         ids = torch.arange(n_glob, device=dev) if gl is None else gl
         isv = ids < nverts
         xL = torch.empty((nL, d), dtype=torch.float64, device=dev)
-        xL[isv] = mesh.coords[ids[isv]]
-        if degree == 2:
-            ek = self._edge_keys[ids[~isv] - nverts]
-            xL[~isv] = 0.5 * (mesh.coords[torch.div(ek, nverts, rounding_mode="floor")] + mesh.coords[ek % nverts])
+        if per is not None:
+            xL = periodic_dof_coordinates(mesh, self.local_cells, cd0g, nL, degree)
+        else:
+            xL[isv] = mesh.coords[ids[isv]]
+            if degree == 2:
+                ek = self._edge_keys[ids[~isv] - nverts]
+                xL[~isv] = 0.5 * (mesh.coords[torch.div(ek, nverts, rounding_mode="floor")] + mesh.coords[ek % nverts])
         del isv
         # ---- 2. owned dofs in tiled spatial order, then ghosts by (owner, global id) --------------
         kb = default_key_bits(self.num_dofs_global, mesh.gdim, tb)
@@ -812,7 +843,17 @@ class FunctionSpace:
 
     # ---------------------------------------------------------------------------------
     def global_to_local(self, gids: torch.Tensor) -> torch.Tensor:
-        """Final local dof of global initial dof ids (-1 where the dof is not local)."""
+        """Final local dof of global initial dof ids (-1 where the dof is not local).  On a periodic mesh an id below
+        ``mesh.num_vertices`` is a GEOMETRIC vertex id, on either face (its class's dof is returned); ``num_vertices`` + e is
+        edge class e of the space's (topological) edge keys."""
+        per = getattr(self.mesh, "periodic", None)
+        if per is not None:
+            nvg = self.mesh.num_vertices
+            vt = getattr(self, "_vertex_topo", None)
+            if vt is None:
+                vt = self._vertex_topo = torch.from_numpy(per.vertex_topo).to(gids.device)
+            isv = gids < nvg
+            gids = torch.where(isv, vt[gids.clamp_max(nvg - 1)], gids - (nvg - per.n_free_vertices))
         if self._gl is None:
             return self._rank_initial[gids]
         pos = torch.searchsorted(self._gl, gids).clamp_max(self._gl.shape[0] - 1)
@@ -1040,9 +1081,12 @@ class FunctionSpace:
         ev, _ = mesh._entities(dim)
         verts = ev[np.asarray(entities, dtype=np.int64)].reshape(len(entities), -1)
         gids = [torch.from_numpy(verts.ravel().astype(np.int64)).to(dev)]
+        per = getattr(mesh, "periodic", None)
         if self.degree >= 2 and verts.shape[1] >= 2:
             ek = self._edge_keys
             nv = mesh.num_vertices
+            if per is not None:  # geometric entities of either face: the edge CLASS of the two vertex classes
+                verts, nv = per.vertex_topo[verts], per.n_free_vertices
             for a, b in itertools.combinations(range(verts.shape[1]), 2):
                 lo = torch.from_numpy(np.minimum(verts[:, a], verts[:, b]).astype(np.int64)).to(dev)
                 hi = torch.from_numpy(np.maximum(verts[:, a], verts[:, b]).astype(np.int64)).to(dev)
@@ -1050,7 +1094,7 @@ class FunctionSpace:
                 pos = torch.searchsorted(ek, key).clamp_max(max(int(ek.shape[0]) - 1, 0))
                 hit = ek[pos] == key  # (a partitioned space knows the edges of its window only)
                 if self.degree == 2:
-                    gids.append((nv + pos)[hit])
+                    gids.append((mesh.num_vertices + pos)[hit])
                 else:  # degree 3: two dofs per edge
                     gids.append((nv + 2 * pos)[hit])
                     gids.append((nv + 2 * pos + 1)[hit])
@@ -1264,6 +1308,8 @@ class HighOrderLagrangeSpace:
     def __init__(self, mesh: Mesh, degree: int):
         if degree < 3:
             raise ValueError("HighOrderLagrangeSpace: degree >= 3 (use FunctionSpace for 1 and 2)")
+        if getattr(mesh, "periodic", None) is not None:  # (dofs here are numbered from the geometric entities: not identified)
+            raise NotImplementedError(f"Lagrange degree {int(degree)} on a periodic mesh: degree 1 and 2 are built")
         self.mesh, self.degree = mesh, int(degree)
         self.num_sub_spaces = 0
         self.element = _Element(degree, mesh.gdim)

@@ -151,6 +151,12 @@ class FractionalStep_AB_CN:
         if (u_deg, p_deg) not in ((1, 1), (2, 1), (3, 2)):
             raise NotImplementedError(f"Lagrange P{u_deg}-P{p_deg}: the built pairs are P1-P1, P2-P1 and P3-P2")
         window = int((options or {}).get("sell_window", 4096))
+        if getattr(mesh, "periodic", None) is not None:  # (mesh.make_periodic; refused before any collective)
+            if getattr(getattr(mesh, "comm", None), "size", 1) > 1:
+                raise NotImplementedError("a periodic mesh on a mesh-partitioned solver (comm.size > 1): identified dofs are "
+                                          "numbered on one GPU")
+            if u_deg == 3:
+                raise NotImplementedError("Lagrange P3-P2 on a periodic mesh: the periodic numbering covers P1-P1 and P2-P1")
 
         # ---- spaces (reference fracstep.py:186-216) ----------------------------------------
         comm = getattr(mesh, "comm", None)

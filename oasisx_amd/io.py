@@ -78,6 +78,10 @@ class VTXWriter:
     def _build_topology(self):
         V = self._V
         d, deg = V.mesh.gdim, V.degree
+        self._image_dof = None
+        if getattr(V.mesh, "periodic", None) is not None:
+            self._build_unfolded_topology()
+            return
         X = np.zeros((V.num_dofs, 3))
         X[:, :d] = V.tabulate_dof_coordinates()[:, :d]
         cd = V.cell_dofs.cpu().numpy().astype(np.int64)
@@ -89,6 +93,60 @@ class VTXWriter:
         offsets = (np.arange(conn.shape[0], dtype=np.int64) + 1) * nper
         types = np.full(conn.shape[0], _VTK_TYPE[(d, deg)], dtype=np.uint8)
         self._topology = (X, conn.reshape(-1), offsets, types)
+
+    def _build_unfolded_topology(self):
+        """Periodic mesh: the UNFOLDED field -- the points of every geometric image of a node (the mesh's vertices, plus
+        the midpoints of its geometric edges for P2) and the connectivity of the geometric cells; ``_image_dof`` names
+        the dof of every point, the values are gathered through it on the device (``ox_gather_images``)."""
+        import torch
+
+        from .fem import local_edges
+
+        V = self._V
+        mesh = V.mesh
+        d, deg = mesh.gdim, V.degree
+        cells = V.cells_in_kernel_order().astype(np.int64)
+        cd = V.cell_dofs.cpu().numpy().astype(np.int64)
+        xv = mesh.coords.cpu().numpy()
+        nv = mesh.num_vertices
+        nodes, pts = cells, xv
+        if deg == 2:
+            a = np.stack([cells[:, e[0]] for e in local_edges(d)], axis=1)
+            b = np.stack([cells[:, e[1]] for e in local_edges(d)], axis=1)
+            key = np.minimum(a, b) * np.int64(nv) + np.maximum(a, b)
+            uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
+            nodes = np.concatenate([cells, nv + inv.reshape(key.shape)], axis=1)
+            pts = np.concatenate([xv, 0.5 * (xv[uniq // nv] + xv[uniq % nv])], axis=0)
+        X = np.zeros((pts.shape[0], 3))
+        X[:, :d] = pts
+        image_dof = np.full(pts.shape[0], -1, dtype=np.int32)
+        image_dof[nodes.reshape(-1)] = cd.reshape(-1)
+        if (image_dof < 0).any():
+            raise RuntimeError("VTXWriter: a vertex of the periodic mesh belongs to no cell")
+        self._image_dof = torch.from_numpy(image_dof).to(mesh.device)
+        conn = nodes[:, _VTK_PERM[(d, deg)]]
+        nper = conn.shape[1]
+        offsets = (np.arange(conn.shape[0], dtype=np.int64) + 1) * nper
+        types = np.full(conn.shape[0], _VTK_TYPE[(d, deg)], dtype=np.uint8)
+        self._topology = (X, conn.reshape(-1), offsets, types)
+
+    def _values(self, f: Function) -> np.ndarray:
+        """(points, components) host values of ``f``'s block: the storage itself, or -- periodic -- its unfolded copy."""
+        if self._image_dof is None:
+            return f._storage.rhost()  # (a read: the block is not checked out)
+        import torch
+
+        idx = self._image_dof
+        if idx.device.type != "cuda":  # CPU meshes (host tests)
+            return f._storage.rhost()[idx.numpy().astype(np.int64)]
+        from . import _lib
+
+        src = f._storage.rdev()
+        n_src, ncomp = int(f._storage.n), int(src.shape[1])  # (the block may be allocated longer than its n rows)
+        dst = torch.empty((int(idx.shape[0]), ncomp), dtype=torch.float64, device=idx.device)
+        _lib.check(_lib.load().ox_gather_images(_lib.ptr(src), n_src, _lib.ptr(idx), int(idx.shape[0]), ncomp, _lib.ptr(dst),
+                                                _lib.current_stream()), "ox_gather_images")
+        return dst.cpu().numpy()
 
     def _piece_name(self, step: int) -> str:
         part = f"_p{self._rank}" if self._size > 1 else ""
@@ -107,7 +165,7 @@ class VTXWriter:
                '</DataArray></FieldData>\n',
                f'<Piece NumberOfPoints="{X.shape[0]}" NumberOfCells="{offsets.shape[0]}">\n<PointData>\n']
         for f in self._fns:
-            h = f._storage.rhost()  # (a read: the block is not checked out)
+            h = self._values(f)
             if f._comp is None:  # blocked function: vector data, padded to 3 components
                 v = np.zeros((h.shape[0], 3))
                 v[:, : h.shape[1]] = h

@@ -113,6 +113,8 @@ class Mesh:
         self.comm = comm
         self._x3 = None
         self._ent = {}
+        self._tcells = None
+        self.periodic = None  # a PeriodicMap on meshes made by make_periodic
         self.geometry = Geometry(self)
         self.topology = Topology(self)
 
@@ -143,9 +145,29 @@ class Mesh:
         return res
 
     def exterior_facets(self) -> np.ndarray:
+        """Facets of one cell, without the facets a periodic mesh identifies (``periodic_facets``)."""
         _, cf = self._entities(self.gdim - 1)
         counts = np.bincount(cf.ravel())
-        return np.nonzero(counts == 1)[0].astype(np.int32)
+        ext = np.nonzero(counts == 1)[0].astype(np.int32)
+        if self.periodic is not None:
+            ext = np.setdiff1d(ext, self.periodic.facets).astype(np.int32)
+        return ext
+
+    def periodic_facets(self) -> np.ndarray:
+        """Facets on the identified faces of a periodic mesh (both images), ascending; empty on any other mesh."""
+        if self.periodic is None:
+            return np.zeros(0, dtype=np.int32)
+        return self.periodic.facets
+
+    def topological_cells(self) -> torch.Tensor:
+        """Cell -> vertex CLASS ids (0 .. n_free_vertices - 1) of a periodic mesh: the table dofs are numbered from.
+        ``cells`` itself on any other mesh."""
+        if self.periodic is None:
+            return self.cells
+        if self._tcells is None:
+            vt = torch.from_numpy(self.periodic.vertex_topo).to(self.device)
+            self._tcells = vt[self.cells].contiguous()
+        return self._tcells
 
     def h(self, dim, entities) -> np.ndarray:
         """Largest vertex distance of each cell (dolfinx.mesh.Mesh.h for cells)."""
@@ -535,6 +557,146 @@ def create_delaunay_box(comm, points, n, seed: int = 0, jitter: float = 0.35, de
 
 def create_unit_cube(comm, nx, ny, nz, cell_type=CellType.tetrahedron, device=None, **kwargs) -> Mesh:
     return create_box(comm, [[0.0, 0.0, 0.0], [1.0, 1.0, 1.0]], [nx, ny, nz], cell_type, device=device)
+
+
+# ---- periodic boundaries --------------------------------------------------------------------
+
+
+class PeriodicMap:
+    """Identification of the faces ``x_k = hi_k`` and ``x_k = lo_k`` of a mesh's bounding box, k in ``axes``.
+
+    ``vertex_master`` (int64, all vertices, idempotent) names the image of a vertex that lies at ``lo`` on every
+    periodic axis; ``vertex_topo`` numbers the classes 0 .. ``n_free_vertices`` - 1 in ascending master id;
+    ``period`` holds the translation of every periodic axis (0 on the others); ``facets`` the identified facets."""
+
+    def __init__(self, mesh, axes, lo, hi, period, atol, vertex_master, face_masks):
+        self._mesh, self._face_masks, self._facets = mesh, face_masks, None
+        self.axes = tuple(int(k) for k in axes)
+        self.lo, self.hi, self.period, self.atol = lo, hi, period, atol
+        self.vertex_master = vertex_master
+        free = np.nonzero(vertex_master == np.arange(vertex_master.shape[0]))[0]
+        self.n_free_vertices = int(free.shape[0])
+        compact = np.full(vertex_master.shape[0], -1, dtype=np.int64)
+        compact[free] = np.arange(free.shape[0])
+        self.vertex_topo = compact[vertex_master]
+
+    @property
+    def facets(self) -> np.ndarray:
+        """Ids (of ``mesh._entities(gdim - 1)``) of the facets on the identified faces, both images, ascending.  Found on
+        first use: the facet table of a large mesh is built only for callers that name facets."""
+        if self._facets is None:
+            fv, _ = self._mesh._entities(self._mesh.gdim - 1)
+            hit = np.zeros(fv.shape[0], dtype=bool)
+            for on in self._face_masks:  # (all vertices on one face of the bounding box: a facet of one cell)
+                hit |= on[fv].all(axis=1)
+            self._facets = np.nonzero(hit)[0].astype(np.int32)
+        return self._facets
+
+    def is_periodic_facet(self, facets) -> np.ndarray:
+        return np.isin(np.asarray(facets), self.facets)
+
+
+def make_periodic(mesh: Mesh, axes, tol=None) -> Mesh:
+    """``mesh`` with the face ``x_k = hi_k`` of its bounding box identified with ``x_k = lo_k`` for every k in ``axes``
+    (translation by ``hi_k - lo_k``).  ``coords`` and ``cells`` stay the geometric mesh; the result carries
+    ``mesh.periodic`` (:class:`PeriodicMap`), and function spaces on it number one dof per class of identified
+    vertices, edges and faces.  ``tol``: matching tolerance relative to the span of each axis (default 1e-8).
+
+    Raises ``ValueError`` naming the axis when the two faces do not carry matching vertices and matching facets, or
+    when the mesh is fewer than three cells across the axis (two distinct edges would then join the same two vertex
+    classes).  ``create_rectangle`` and ``create_box`` meshes match on every axis; a ``create_delaunay_box`` mesh
+    jitters its face points independently, so its faces do not match and it is refused."""
+    axes = tuple(sorted(set(int(k) for k in axes)))
+    d = mesh.gdim
+    if not axes or min(axes) < 0 or max(axes) >= d:
+        raise ValueError(f"make_periodic: axes {axes} on a {d}-D mesh")
+    if mesh.periodic is not None:
+        raise ValueError("make_periodic: the mesh is periodic already")
+    x = mesh.coords.cpu().numpy()
+    cells = mesh.cells.cpu().numpy()
+    nv = mesh.num_vertices
+    lo, hi = x.min(axis=0), x.max(axis=0)
+    span = hi - lo
+    rtol = 1e-8 if tol is None else float(tol)
+    atol = rtol * span
+    vm = np.arange(nv, dtype=np.int64)
+    period = np.zeros(d)
+    masks = []
+    others_of = {k: [j for j in range(d) if j != k] for k in axes}
+    for k in axes:
+        if not span[k] > 0.0:
+            raise ValueError(f"make_periodic: axis {k}: the mesh has no extent")
+        period[k] = span[k]
+        on_lo, on_hi = np.abs(x[:, k] - lo[k]) <= atol[k], np.abs(x[:, k] - hi[k]) <= atol[k]
+        il, ih = np.nonzero(on_lo)[0], np.nonzero(on_hi)[0]
+        if il.shape[0] != ih.shape[0]:
+            raise ValueError(f"make_periodic: axis {k}: {il.shape[0]} vertices on the lo face, {ih.shape[0]} on the hi face: "
+                             "the vertices of the two faces do not match")
+        oth = others_of[k]
+        # pair every hi vertex with the lo vertex at the same place of the face: a grid of cells at least 2 atol wide over
+        # the other coordinates, and a look into the neighbouring cells, so that round-off across a cell border (an
+        # imported mesh) cannot separate a pair
+        w = np.maximum(np.maximum(2.0 * atol[oth], 2e-9 * span[oth]), 1e-300)
+        cl = np.floor((x[il][:, oth] - lo[oth]) / w).astype(np.int64) + 1
+        ch = np.floor((x[ih][:, oth] - lo[oth]) / w).astype(np.int64) + 1
+        stride = np.int64(max(int(cl.max(initial=0)), int(ch.max(initial=0))) + 3)
+
+        def cell_key(c):
+            key = np.zeros(c.shape[0], dtype=np.int64)
+            for j in range(c.shape[1]):
+                key = key * stride + c[:, j]
+            return key
+        kl = cell_key(cl)
+        srt = np.argsort(kl, kind="stable")
+        kls = kl[srt]
+        partner = np.full(ih.shape[0], -1, dtype=np.int64)
+        for off in itertools.product((-1, 0, 1), repeat=len(oth)):
+            kq = cell_key(ch + np.asarray(off, dtype=np.int64))
+            p0, p1 = np.searchsorted(kls, kq, side="left"), np.searchsorted(kls, kq, side="right")
+            for r in range(int((p1 - p0).max(initial=0))):  # (cells hold one vertex unless vertices nearly coincide)
+                cand = np.minimum(p0 + r, kls.shape[0] - 1)
+                ok = (p0 + r < p1) & (partner < 0)
+                j = srt[cand]
+                ok &= (np.abs(x[il[j]][:, oth] - x[ih][:, oth]) <= atol[oth]).all(axis=1)
+                partner[ok] = j[ok]
+        if (partner < 0).any():
+            bad = int(np.argmax(partner < 0))
+            raise ValueError(f"make_periodic: axis {k}: the vertices of the two faces do not match (vertex {int(ih[bad])} at "
+                             f"{x[ih[bad]].tolist()} has no image on the lo face)")
+        if np.unique(partner).shape[0] != partner.shape[0]:
+            raise ValueError(f"make_periodic: axis {k}: the vertices of the two faces do not match one to one (two vertices of "
+                             "the hi face share an image on the lo face)")
+        il = il[partner]
+        mk = np.arange(nv, dtype=np.int64)
+        mk[ih] = il
+        # facets: every facet of the hi face must be, vertex for vertex, a facet of the lo face.  A facet in a face of
+        # the bounding box belongs to one cell, which has its other vertex off the face: read from the cells, without the
+        # facet table of the whole mesh
+        def face_keys(on, relabel):
+            c = cells[on[cells].sum(axis=1) == d]  # cells with a facet in the face
+            v = np.sort(relabel[c[on[c]].reshape(-1, d)], axis=1)  # (row-major mask: each cell's d face vertices)
+            key = np.zeros(v.shape[0], dtype=np.int64)
+            for j in range(d):
+                key = key * np.int64(nv) + v[:, j]
+            return np.sort(key)
+        kl, kh = face_keys(on_lo, np.arange(nv, dtype=np.int64)), face_keys(on_hi, mk)
+        if kl.shape[0] != kh.shape[0] or (kl != kh).any():
+            raise ValueError(f"make_periodic: axis {k}: the facets of the two faces do not match "
+                             f"({kl.shape[0]} on the lo face, {kh.shape[0]} on the hi face, "
+                             f"{int(np.intersect1d(kl, kh).shape[0])} in common)")
+        # three cells across: no vertex may share cells with vertices of both faces
+        near_lo, near_hi = np.zeros(nv, dtype=bool), np.zeros(nv, dtype=bool)
+        near_lo[cells[on_lo[cells].any(axis=1)].ravel()] = True
+        near_hi[cells[on_hi[cells].any(axis=1)].ravel()] = True
+        if (near_lo & near_hi).any():
+            raise ValueError(f"make_periodic: axis {k}: fewer than three cells across (vertex "
+                             f"{int(np.argmax(near_lo & near_hi))} shares cells with both faces): distinct edges would be identified")
+        vm = mk[vm]
+        masks += [on_lo, on_hi]
+    out = Mesh(mesh.coords, mesh.cells, mesh.comm)
+    out._ent = dict(mesh._ent)
+    out.periodic = PeriodicMap(out, axes, lo, hi, period, atol, vm, masks)
+    return out
 
 
 # ---- entity location and tags ------------------------------------------------------------

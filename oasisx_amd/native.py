@@ -64,8 +64,18 @@ class NativeMesh:
         lib = _lib.load()
         out = C.c_void_p()
         cells32 = mesh.cells.to(torch.int32).contiguous()
-        _lib.check(lib.ox_mesh_create(_lib.ptr(mesh.coords), mesh.num_vertices, _lib.ptr(cells32), mesh.num_cells,
-                                      mesh.gdim, 1, int(tile_bits), C.byref(out)), "ox_mesh_create")
+        per = getattr(mesh, "periodic", None)
+        if per is not None:  # the geometric cells plus the same cells over vertex classes (mesh.make_periodic)
+            topo32 = mesh.topological_cells().to(torch.int32).contiguous()
+            cut = (C.c_double * 3)(float("inf"), float("inf"), float("inf"))
+            for k in per.axes:
+                cut[k] = float(per.hi[k] - per.atol[k])
+            _lib.check(lib.ox_mesh_create_periodic(_lib.ptr(mesh.coords), mesh.num_vertices, _lib.ptr(cells32), _lib.ptr(topo32),
+                                                   per.n_free_vertices, mesh.num_cells, mesh.gdim, 1, int(tile_bits), cut,
+                                                   C.byref(out)), "ox_mesh_create_periodic")
+        else:
+            _lib.check(lib.ox_mesh_create(_lib.ptr(mesh.coords), mesh.num_vertices, _lib.ptr(cells32), mesh.num_cells,
+                                          mesh.gdim, 1, int(tile_bits), C.byref(out)), "ox_mesh_create")
         self.handle = _Handle(out, lib.ox_mesh_destroy)
         v = _lib.ox_mesh_info()
         _lib.check(lib.ox_mesh_view(out, C.byref(v)), "ox_mesh_view")

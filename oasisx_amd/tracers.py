@@ -52,7 +52,10 @@ class Tracers:
     field is continuous).  ``sort_every = k > 0``: every k advances the particle storage is re-sorted by kernel-cell
     position (a stable ``argsort`` and a gather on the current stream); every getter returns id order whatever the
     storage order, and the results are bit-identical with and without sorting; 0: never.  The defaults are the fastest
-    of the measured combinations.  One GPU."""
+    of the measured combinations.  One GPU.
+
+    On a periodic mesh (``mesh.make_periodic``) particles do NOT wrap: a particle that leaves through an identified face
+    leaves the geometric mesh and freezes with status 1, as at any other boundary."""
 
     def __init__(self, velocity, points, scheme: str = "rk4", substeps: int = 1, tol: float = G.DEFAULT_TOL,
                  hint: bool = True, sort_every: int = 8, allow_missing: bool = False):

@@ -47,6 +47,11 @@ def facet_table(mesh, facets, who: str = "WallStress", what: str = "wall stresse
     if interior.size:
         raise ValueError(f"{who}: {interior.size} of the facets are interior facets (the first: {int(interior[0])}); "
                          f"{what} are evaluated on exterior facets")
+    per = getattr(mesh, "periodic", None)
+    if per is not None and per.is_periodic_facet(facets).any():
+        seam = facets[per.is_periodic_facet(facets)]
+        raise ValueError(f"{who}: {seam.size} of the facets lie on an identified (periodic) face (the first: {int(seam[0])}); "
+                         f"{what} are evaluated on exterior facets")
     combos = list(itertools.combinations(range(d + 1), d))
     opp_of_combo = np.array([[a for a in range(d + 1) if a not in c][0] for c in combos])
     fcell, fslot = np.nonzero(np.isin(cf, facets))
