@@ -533,6 +533,23 @@ int ox_flow_reduce(int64_t n_blocks, const double *partials, double *ring, int64
  * W_old == 0: mean = x, cov = 0 (whatever they held).  w > 0.  One thread per dof, no atomics. */
 int ox_stats_accumulate(int ncomp, int64_t n, const double *x, int64_t ldx, double w, double W_old, double *mean,
                         double *cov, void *stream);
+/* Slab-averaged statistics.  The joint vector q has nq components (1, or gdim .. gdim + 2): the
+ * first nc0 = (nq == 1 ? 1 : gdim) lie side by side in source 0 (row i at src[0] + i ld[0]), every further one is the
+ * first value of row i of its own source; n_src = 1 + nq - nc0 <= 3 (src, ld: HOST arrays), all on cell_dofs [n_cells][nd]
+ * of `degree`.  order (device int32): the sampled cells sorted by bin; chunks (device int32 [n_chunks][4], 16-byte
+ * aligned) = {first entry of order, cells (<= 256), bin, 1 if those cells are consecutive}, no chunk crossing a bin.
+ * One block per chunk, one lane per cell; with delta_i = q_i - shift[bin] (shift: device [n_bins][nq] or NULL = 0)
+ *   partials[c] = [sum |cell|, s1 (nq), s2 (nq (nq + 1) / 2)],  s1[k] = sum int delta[k],  s2[k][l] = sum int delta[k]
+ *   delta[l] for k <= l row by row, exact for the element.  Fixed reduction tree, no atomics. */
+int ox_profile_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, int nq, int n_src,
+                     const double *const *src, const int64_t *ld, const int32_t *order, const int32_t *chunks,
+                     int64_t n_chunks, const double *shift, double *partials, void *stream);
+/* One wave per bin b: V, S1, S2 = the sum of the partial rows bin_chunk_ptr[b] .. bin_chunk_ptr[b + 1] (fixed order), then
+ * with d = S1 / V, g = shift[b] + d, a = w / (W_old + w):  mean[b] += a (g - mean[b]),  m2[b] += w (S2 / V - d d^T) +
+ * W_old a (g - mean[b]) (g - mean[b])^T (upper triangle),  vol[b] = V.  shift may be mean itself.  seed != 0: mean[b] = d
+ * and vol[b] = V alone (w, W_old and m2 unused).  sums (optional): [n_bins][1 + nq + nq (nq + 1) / 2] = V, S1, S2. */
+int ox_profile_update(int nq, int64_t n_bins, const int32_t *bin_chunk_ptr, const double *partials, const double *shift,
+                      double w, double W_old, int seed, double *mean, double *m2, double *vol, double *sums, void *stream);
 
 /* ---- A6 / A8: assemble_vector(p * v.dx(i) * dx) and (dp.dx(i) * v * dx), all i at once
  *      (fracstep.py:487-497 and :618).  kind 0: out[r][i] = base[r][i] + scale * int p d_i(phi_r)

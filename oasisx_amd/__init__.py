@@ -7,7 +7,7 @@ import logging
 
 from . import fem, geometry, io, mesh  # noqa: F401
 from .bcs import DirichletBC, LocatorMethod, PressureBC
-from .diagnostics import FlowDiagnostics, FlowStatistics
+from .diagnostics import FlowDiagnostics, FlowStatistics, ProfileStatistics, slab_bins
 from .fracstep import FractionalStep_AB_CN
 from .function import Projector
 from .geometry import Probes  # noqa: F401
@@ -43,4 +43,6 @@ __all__ = [
     "Tracers",
     "FlowDiagnostics",
     "FlowStatistics",
+    "ProfileStatistics",
+    "slab_bins",
 ]

@@ -316,6 +316,8 @@ SIGNATURES = {
     "ox_flow_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _D, _D, _P, _P, _P, _P]),
     "ox_flow_reduce": (_I, [_L, _P, _P, _L, _L, _P]),
     "ox_stats_accumulate": (_I, [_I, _L, _P, _L, _D, _D, _P, _P, _P]),
+    "ox_profile_cells": (_I, [_I, C.POINTER(ox_cells), _P, _I, _I, C.POINTER(_P), C.POINTER(_L), _P, _P, _L, _P, _P, _P]),
+    "ox_profile_update": (_I, [_I, _L, _P, _P, _P, _D, _D, _I, _P, _P, _P, _P, _P]),
     "ox_assemble_grad_vector": (_I, [_I, _I, _I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P,
                                      _P, _D, _P, _P]),
     "ox_assemble_div_vector": (_I, [_I, _I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P, _D,

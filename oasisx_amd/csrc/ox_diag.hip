@@ -23,6 +23,11 @@
 //
 // ox_stats_accumulate: West's (1979) weighted incremental update of mean and upper-triangular covariance sums per dof,
 // one thread per dof (pure streaming, 16-byte accesses where the interleaved layout allows, no atomics).
+//
+// ox_profile_cells / ox_profile_update: the moments of a joint vector q over the cells of a bin (a
+// slab of a homogeneous direction), exact for the element through the same mean mass matrix, taken about a per-bin shift;
+// cells reach their bin through a sorted permutation cut into chunks of <= 256 that never cross a bin, one block per
+// chunk, one wave per bin for the merge into the running mean and second moment.  No atomics either.
 #define OX_DIAG_RULE_QUAL __constant__
 #include "fe_tables_d.h"
 #include "ox_element.h"
@@ -337,7 +342,228 @@ __global__ __launch_bounds__(256) void k_stats(int64_t n, const double *__restri
   }
 }
 
+// ---- slab-averaged statistics -----------------------------------------------------------------
+// The joint vector q of a group has NQ components: the first NC0 = (NQ == 1 ? 1 : GDIM) lie side by side in source 0 (the
+// velocity block, or a pressure / a scalar alone), every further one is a column of its own (a scalar inside the block of
+// its group).  A partial row is [vol, s1 (NQ), s2 (NQ (NQ + 1) / 2, upper triangle row by row)].
+__host__ __device__ constexpr int ox_prof_nr(int nq) { return 1 + nq + nq * (nq + 1) / 2; }
+
+struct ProfSrc {
+  const double *p[3];
+  int64_t ld[3];
+};
+
+// the mean of basis function i over the cell: the row sum of the mean mass matrix (sum_j phi_j = 1)
+template <int GDIM, int DEG>
+__host__ __device__ constexpr double prof_mrow(int i) {
+  double s = 0.0;
+  for (int j = 0; j < ox_nd(GDIM, DEG); ++j) s += Diag<GDIM, DEG>::mass(i, j);
+  return s;
+}
+
+// One 256-lane block per chunk (chunk[c] = {first entry of order, cells, bin, 1 if the cells are consecutive}), one lane
+// per cell e = order[first + lane]; with delta_i = q_i - shift[bin] at the cell's nodes
+//   s1[k] = |c| sum_i m_i delta_i[k],   s2[k][l] = |c| sum_i delta_i[k] (M delta[:, l])_i,  k <= l,
+// summed over the chunk by the fixed tree of ox_block_sum_256 into partials[c].
+template <int GDIM, int DEG, int NQ>
+__global__ __launch_bounds__(256) void k_profile_cells(ox_cells cells, const int32_t *__restrict__ cell_dofs, ProfSrc src,
+                                                       const int32_t *__restrict__ order, const int4 *__restrict__ chunk,
+                                                       const double *__restrict__ shift, double *__restrict__ partials) {
+  using E = Diag<GDIM, DEG>;
+  constexpr int ND = ox_nd(GDIM, DEG), NR = ox_prof_nr(NQ), NC0 = NQ == 1 ? 1 : GDIM;
+  __shared__ double lds[4 * NR];
+  const int4 ch = chunk[blockIdx.x];
+  const int len = ch.y < 256 ? ch.y : 256;
+  double v[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) v[i] = 0.0;
+  int64_t e = -1;
+  if ((int)threadIdx.x < len) e = ch.w ? (int64_t)order[ch.x] + threadIdx.x : (int64_t)order[(int64_t)ch.x + threadIdx.x];
+  if (e >= 0 && e < cells.n_cells) {
+    int32_t dd[ND];
+    ox_load_dofs<ND>(cell_dofs, e, dd);
+    const double adet = ox_geom_adet<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM));
+    double q[ND][NQ];
+    if (src.ld[0] == NC0) {
+      double q0[ND][NC0];
+      ox_gather<ND, NC0>(dd, src.p[0], q0);
+#pragma unroll
+      for (int i = 0; i < ND; ++i)
+#pragma unroll
+        for (int c = 0; c < NC0; ++c) q[i][c] = q0[i][c];
+    } else {
+#pragma unroll
+      for (int i = 0; i < ND; ++i)
+#pragma unroll
+        for (int c = 0; c < NC0; ++c) q[i][c] = src.p[0][(size_t)dd[i] * src.ld[0] + c];
+    }
+#pragma unroll
+    for (int k = NC0; k < NQ; ++k)
+#pragma unroll
+      for (int i = 0; i < ND; ++i) q[i][k] = src.p[1 + k - NC0][(size_t)dd[i] * src.ld[1 + k - NC0]];
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+      const double sh = shift ? shift[(size_t)ch.z * NQ + k] : 0.0;
+#pragma unroll
+      for (int i = 0; i < ND; ++i) q[i][k] -= sh;
+    }
+    const double vol = GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0);
+    v[0] = vol;
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < ND; ++i)
+        if (prof_mrow<GDIM, DEG>(i) != 0.0) s = fma(prof_mrow<GDIM, DEG>(i), q[i][k], s);
+      v[1 + k] = vol * s;
+    }
+    double s2[NR - 1 - NQ];
+#pragma unroll
+    for (int m = 0; m < NR - 1 - NQ; ++m) s2[m] = 0.0;
+#pragma unroll
+    for (int l = 0; l < NQ; ++l)
+#pragma unroll
+      for (int i = 0; i < ND; ++i) {
+        double r = 0.0;
+#pragma unroll
+        for (int j = 0; j < ND; ++j)
+          if (E::mass(i, j) != 0.0) r = fma(E::mass(i, j), q[j][l], r);
+#pragma unroll
+        for (int k = 0; k <= l; ++k) {  // (k, l), k <= l, sits at k NQ - k (k - 1) / 2 + l - k of the upper triangle
+          const int m = k * NQ - k * (k - 1) / 2 + l - k;
+          s2[m] = fma(q[i][k], r, s2[m]);
+        }
+      }
+#pragma unroll
+    for (int m = 0; m < NR - 1 - NQ; ++m) v[1 + NQ + m] = vol * s2[m];
+  }
+  ox_block_sum_256<NR>(v, lds);
+  if (threadIdx.x == 0) {
+    double *__restrict__ p = partials + (size_t)blockIdx.x * NR;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) p[i] = v[i];
+  }
+}
+
+// One wave per bin: the bin's chunk rows lane-strided in ascending order, a wave sum, and in lane 0 the weighted merge
+// (a = w / (W + w), b = W a;  d = S1 / V, g = shift + d):
+//   mean' = mean + a (g - mean),   M2' = M2 + w (S2 / V - d d^T) + b (g - mean) (g - mean)^T.
+// seed: mean := S1 / V alone (the sums of a run with shift 0).  shift may BE mean (read before it is written).
+template <int NQ>
+__global__ __launch_bounds__(64) void k_profile_update(const int32_t *__restrict__ bin_chunk_ptr,
+                                                       const double *__restrict__ partials, const double *shift, double w,
+                                                       double a, double b, int seed, double *mean, double *__restrict__ m2,
+                                                       double *__restrict__ vol, double *__restrict__ sums) {
+  constexpr int NR = ox_prof_nr(NQ), NV = NQ * (NQ + 1) / 2;
+  const int64_t bin = blockIdx.x;
+  const int c0 = bin_chunk_ptr[bin], c1 = bin_chunk_ptr[bin + 1];
+  double v[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) v[i] = 0.0;
+  for (int c = c0 + (int)threadIdx.x; c < c1; c += 64) {
+    const double *__restrict__ p = partials + (size_t)c * NR;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) v[i] += p[i];
+  }
+#pragma unroll
+  for (int i = 0; i < NR; ++i) v[i] = ox_wave_sum(v[i]);
+  if (threadIdx.x != 0) return;
+  if (sums) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) sums[(size_t)bin * NR + i] = v[i];
+  }
+  vol[bin] = v[0];
+  const double inv = 1.0 / v[0];
+  double d[NQ], dl[NQ];
+#pragma unroll
+  for (int k = 0; k < NQ; ++k) d[k] = v[1 + k] * inv;
+  if (seed) {
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) mean[(size_t)bin * NQ + k] = d[k];
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < NQ; ++k) {
+    const double mk = mean[(size_t)bin * NQ + k];
+    const double g = (shift ? shift[(size_t)bin * NQ + k] : 0.0) + d[k];
+    dl[k] = g - mk;
+    mean[(size_t)bin * NQ + k] = fma(a, dl[k], mk);
+  }
+  int m = 0;
+#pragma unroll
+  for (int k = 0; k < NQ; ++k)
+#pragma unroll
+    for (int l = k; l < NQ; ++l, ++m) {
+      const double c = fma(-d[k], d[l], v[1 + NQ + m] * inv);
+      m2[(size_t)bin * NV + m] = fma(b * dl[k], dl[l], fma(w, c, m2[(size_t)bin * NV + m]));
+    }
+}
+
 }  // namespace
+
+extern "C" int ox_profile_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, int nq, int n_src,
+                                const double *const *src, const int64_t *ld, const int32_t *order, const int32_t *chunks,
+                                int64_t n_chunks, const double *shift, double *partials, void *stream) {
+  if (!cells || !cell_dofs || !src || !ld || !order || !chunks || !partials || !cells->geom)
+    OX_FAIL("ox_profile_cells: null argument");
+  if (cells->n_cells <= 0 || cells->n_cells > (int64_t)0x7fffffff)
+    OX_FAIL("ox_profile_cells: %lld cells", (long long)cells->n_cells);
+  if (n_chunks <= 0 || n_chunks > (int64_t)0x7fffffff) OX_FAIL("ox_profile_cells: n_chunks=%lld", (long long)n_chunks);
+  const int g = cells->gdim;
+  if (!(nq == 1 || (nq >= g && nq <= g + 2))) OX_FAIL("ox_profile_cells: nq=%d on gdim=%d (1 or gdim .. gdim + 2)", nq, g);
+  const int nc0 = nq == 1 ? 1 : g;
+  if (n_src != 1 + nq - nc0) OX_FAIL("ox_profile_cells: nq=%d takes %d sources, not %d", nq, 1 + nq - nc0, n_src);
+  ProfSrc s{};
+  for (int i = 0; i < n_src; ++i) {
+    if (!src[i] || ld[i] < (i == 0 ? nc0 : 1)) OX_FAIL("ox_profile_cells: source %d: null or ld=%lld", i, (long long)ld[i]);
+    s.p[i] = src[i], s.ld[i] = ld[i];
+  }
+  hipStream_t st = ox_stream(stream);
+  const int4 *ch = reinterpret_cast<const int4 *>(chunks);
+#define OX_PROF_LAUNCH(GD, DG, NQ_)                                                                                     \
+  if (nq == NQ_) {                                                                                                      \
+    hipLaunchKernelGGL((k_profile_cells<GD, DG, NQ_>), dim3((unsigned)n_chunks), dim3(256), 0, st, *cells, cell_dofs, s, \
+                       order, ch, shift, partials);                                                                     \
+  }
+#define OX_PROF_CASE(GD, DG)                                                                                    \
+  if (g == GD && degree == DG) {                                                                                \
+    if (ox_prof_on) ox_prof_start(OX_TAG_PROFILE_CELLS, st, n_chunks);                                          \
+    OX_PROF_LAUNCH(GD, DG, 1)                                                                                   \
+    OX_PROF_LAUNCH(GD, DG, GD) OX_PROF_LAUNCH(GD, DG, GD + 1) OX_PROF_LAUNCH(GD, DG, GD + 2)                    \
+    if (ox_prof_on) ox_prof_stop(st);                                                                           \
+    OX_LAUNCH_CHECK();                                                                                          \
+    return 0;                                                                                                   \
+  }
+  OX_FOR_GDIM_DEG(OX_PROF_CASE)
+#undef OX_PROF_CASE
+#undef OX_PROF_LAUNCH
+  OX_FAIL("ox_profile_cells: unsupported gdim=%d degree=%d", g, degree);
+}
+
+extern "C" int ox_profile_update(int nq, int64_t n_bins, const int32_t *bin_chunk_ptr, const double *partials,
+                                 const double *shift, double w, double W_old, int seed, double *mean, double *m2, double *vol,
+                                 double *sums, void *stream) {
+  if (!bin_chunk_ptr || !partials || !mean || !vol || (!seed && !m2)) OX_FAIL("ox_profile_update: null argument");
+  if (nq < 1 || nq > 5) OX_FAIL("ox_profile_update: nq=%d", nq);
+  if (n_bins <= 0 || n_bins > (int64_t)0x7fffffff) OX_FAIL("ox_profile_update: n_bins=%lld", (long long)n_bins);
+  double a = 0.0, b = 0.0;
+  if (!seed) {
+    if (!(w > 0.0) || !std::isfinite(w)) OX_FAIL("ox_profile_update: w=%g", w);
+    if (!(W_old >= 0.0) || !std::isfinite(W_old)) OX_FAIL("ox_profile_update: W_old=%g", W_old);
+    a = w / (W_old + w), b = W_old * a;
+  }
+  hipStream_t st = ox_stream(stream);
+  if (ox_prof_on) ox_prof_start(OX_TAG_PROFILE_UPDATE, st, n_bins);
+#define OX_PROF_UPD(NQ_)                                                                                                  \
+  if (nq == NQ_)                                                                                                          \
+    hipLaunchKernelGGL((k_profile_update<NQ_>), dim3((unsigned)n_bins), dim3(64), 0, st, bin_chunk_ptr, partials, shift, w, \
+                       a, b, seed, mean, m2, vol, sums);
+  OX_PROF_UPD(1) OX_PROF_UPD(2) OX_PROF_UPD(3) OX_PROF_UPD(4) OX_PROF_UPD(5)
+#undef OX_PROF_UPD
+  if (ox_prof_on) ox_prof_stop(st);
+  OX_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int ox_flow_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *u, const double *nut,
                              double dt, double nu, double *fields, double *cell_integrals, double *partials, void *stream) {

@@ -141,6 +141,8 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_FLOW_CELLS 162       // ox_flow_cells (key = cells)
 #define OX_TAG_FLOW_REDUCE 163      // ox_flow_reduce (key = partial rows)
 #define OX_TAG_STATS_ACCUMULATE 164 // ox_stats_accumulate (key = dofs x components)
+#define OX_TAG_PROFILE_CELLS 165    // ox_profile_cells (key = chunks)
+#define OX_TAG_PROFILE_UPDATE 166   // ox_profile_update (key = bins)
 #define OX_TAG_WALL_STRESS 170     // ox_wall_stress (key = facets)
 #define OX_TAG_WALL_FORCES 171     // ox_wall_forces (key = tags)
 #define OX_TAG_OUTLET_FLUX 180     // ox_outlet_flux (key = facets)
