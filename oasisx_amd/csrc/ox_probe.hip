@@ -52,10 +52,10 @@ __global__ __launch_bounds__(256) void k_loc_geom(int64_t n, int64_t n_verts, in
                                                   const int64_t *__restrict__ ids, double tol, double pad_abs,
                                                   double *__restrict__ x0, double *__restrict__ grad,
                                                   double *__restrict__ box, double *__restrict__ partial) {
-  __shared__ double red[4 * 2 * D];
-  double mn[D], mx[D];
+  __shared__ double red[4 * 3 * D];
+  double mn[D], mx[D], sm[D];
 #pragma unroll
-  for (int k = 0; k < D; ++k) mn[k] = INFINITY, mx[k] = -INFINITY;
+  for (int k = 0; k < D; ++k) mn[k] = INFINITY, mx[k] = -INFINITY, sm[k] = 0.0;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) {
     const int64_t c = ids ? ids[i] : i;
@@ -99,41 +99,49 @@ __global__ __launch_bounds__(256) void k_loc_geom(int64_t n, int64_t n_verts, in
       l -= pad, h += pad;
       x0[i * D + k] = x[0][k];
       box[i * 2 * D + k] = l, box[i * 2 * D + D + k] = h;
-      if (ok) mn[k] = l, mx[k] = h;
+      if (ok) mn[k] = l, mx[k] = h, sm[k] = h - l;
     }
   }
-  // the block's box: minima then maxima (fixed order; min / max do not depend on it anyway)
+  // the block's box and the sum of its cells' padded extents: minima, maxima, sums (a fixed order: the sums are the same
+  // on every run)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < D; ++k) {
-    double a = mn[k], b = mx[k];
+    double a = mn[k], b = mx[k], c = sm[k];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a = fmin(a, __shfl_down(a, off, 64)), b = fmax(b, __shfl_down(b, off, 64));
-    if (lane == 0) red[wave * 2 * D + k] = a, red[wave * 2 * D + D + k] = b;
+    for (int off = 32; off > 0; off >>= 1)
+      a = fmin(a, __shfl_down(a, off, 64)), b = fmax(b, __shfl_down(b, off, 64)), c += __shfl_down(c, off, 64);
+    if (lane == 0) red[wave * 3 * D + k] = a, red[wave * 3 * D + D + k] = b, red[wave * 3 * D + 2 * D + k] = c;
   }
   __syncthreads();
-  if (threadIdx.x < 2 * D) {
+  if (threadIdx.x < 3 * D) {
     const int k = threadIdx.x;
     double v = red[k];
-    for (int w = 1; w < 4; ++w) v = k < D ? fmin(v, red[w * 2 * D + k]) : fmax(v, red[w * 2 * D + k]);
-    partial[(size_t)blockIdx.x * 2 * D + k] = v;
+    for (int w = 1; w < 4; ++w) {
+      const double p = red[w * 3 * D + k];
+      v = k < D ? fmin(v, p) : (k < 2 * D ? fmax(v, p) : v + p);
+    }
+    partial[(size_t)blockIdx.x * 3 * D + k] = v;
   }
 }
 
-// out[k] = min (k < D) / max (k >= D) over the blocks' partial boxes; one block
+// out[k] = min (k < D) / max (D <= k < 2 D) / sum (k >= 2 D) over the blocks' partial records; one block
 template <int D>
 __global__ __launch_bounds__(256) void k_loc_box(const double *__restrict__ partial, int nblk, double *__restrict__ out) {
   __shared__ double red[256];
-  for (int k = 0; k < 2 * D; ++k) {
-    double v = k < D ? INFINITY : -INFINITY;
+  for (int k = 0; k < 3 * D; ++k) {
+    double v = k < D ? INFINITY : (k < 2 * D ? -INFINITY : 0.0);
     for (int b = threadIdx.x; b < nblk; b += 256) {
-      const double p = partial[(size_t)b * 2 * D + k];
-      v = k < D ? fmin(v, p) : fmax(v, p);
+      const double p = partial[(size_t)b * 3 * D + k];
+      v = k < D ? fmin(v, p) : (k < 2 * D ? fmax(v, p) : v + p);
     }
     red[threadIdx.x] = v;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) red[threadIdx.x] = k < D ? fmin(red[threadIdx.x], red[threadIdx.x + s]) : fmax(red[threadIdx.x], red[threadIdx.x + s]);
+      if ((int)threadIdx.x < s) {
+        const double p = red[threadIdx.x + s];
+        red[threadIdx.x] = k < D ? fmin(red[threadIdx.x], p) : (k < 2 * D ? fmax(red[threadIdx.x], p) : red[threadIdx.x] + p);
+      }
       __syncthreads();
     }
     if (threadIdx.x == 0) out[k] = red[0];
@@ -627,7 +635,7 @@ static int loc_create(ox_locator *L, const double *coords, int64_t n_verts, cons
                       const int64_t *ids, double padding, hipStream_t st) {
   const int64_t n = L->n_cells;
   const int nblk = (int)((n + 255) / 256);
-  const size_t dbl = (size_t)n * (D + D * D + 2 * D) + (size_t)nblk * 2 * D + 2 * D;
+  const size_t dbl = (size_t)n * (D + D * D + 2 * D) + (size_t)nblk * 3 * D + 3 * D;
   const size_t bytes = dbl * sizeof(double) + (ids ? (size_t)n * sizeof(int64_t) : 0);
   if (hipMalloc(&L->mem, bytes) != hipSuccess) OX_FAIL("ox_locator_create: hipMalloc of %zu bytes failed", bytes);
   double *p = static_cast<double *>(L->mem);
@@ -635,9 +643,9 @@ static int loc_create(ox_locator *L, const double *coords, int64_t n_verts, cons
   L->grad = p, p += (size_t)n * D * D;
   L->box = p, p += (size_t)n * 2 * D;
   double *partial = p;
-  p += (size_t)nblk * 2 * D;
+  p += (size_t)nblk * 3 * D;
   double *gbox = p;
-  p += 2 * D;
+  p += 3 * D;
   if (ids) {
     L->ids = reinterpret_cast<int64_t *>(p);
     OX_HIP(hipMemcpyAsync(L->ids, ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -647,25 +655,29 @@ static int loc_create(ox_locator *L, const double *coords, int64_t n_verts, cons
   OX_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_loc_box<D>, dim3(1), dim3(256), 0, st, partial, nblk, gbox);
   OX_LAUNCH_CHECK();
-  double hb[2 * D];
+  double hb[3 * D];
   OX_HIP(hipMemcpyAsync(hb, gbox, sizeof(hb), hipMemcpyDeviceToHost, st));
   OX_HIP(hipStreamSynchronize(st));
-  // bins per axis from the extents: about one cell per bin
+  // bins per axis, about one cell per bin on stretched domains too: r_k = (extent of the box) / (mean padded extent of a
+  // cell) cells span axis k; the bins are r_k scaled by one factor that makes their product n.  (Cells of one size on
+  // every axis, mean_k = m: r_k (n / prod r)^(1/d) = ext_k / (vol / n)^(1/d), the isotropic length.)
   LocGrid &G = L->grid;
-  double vol = 1.0;
+  double r[D], prod = 1.0;
   int nz = 0;
   for (int k = 0; k < D; ++k) {
     if (!(hb[k] <= hb[D + k])) OX_FAIL("ox_locator_create: the cells have no finite bounding box");
     G.lo[k] = hb[k], G.hi[k] = hb[D + k];
-    const double ext = G.hi[k] - G.lo[k];
-    if (ext > 0.0) vol *= ext, ++nz;
+    const double ext = G.hi[k] - G.lo[k], mean = hb[2 * D + k] / (double)n;
+    r[k] = ext > 0.0 && mean > 0.0 ? ext / mean : 0.0;
+    if (!(r[k] >= 1.0)) r[k] = 0.0;  // (a flat or empty axis, or a NaN: one bin)
+    if (r[k] > 0.0) prod *= r[k], ++nz;
   }
-  const double h = nz ? pow(vol / (double)n, 1.0 / nz) : 1.0;
+  const double scale = nz ? pow((double)n / prod, 1.0 / nz) : 1.0;
   int64_t nbins = 1;
   for (int k = 0; k < 3; ++k) G.nb[k] = 1;
   for (int k = 0; k < D; ++k) {
     const double ext = G.hi[k] - G.lo[k];
-    double q = ext > 0.0 && h > 0.0 ? ceil(ext / h) : 1.0;
+    double q = r[k] > 0.0 && scale > 0.0 ? ceil(r[k] * scale) : 1.0;
     if (!(q >= 1.0)) q = 1.0;
     if (q > 1024.0) q = 1024.0;
     G.nb[k] = (int)q;
