@@ -496,6 +496,22 @@ int ox_assemble_first(const ox_cells *cells, const ox_space_info *space, const o
  * [n_cells][nd] of the velocity component space of `degree` (1, 2, 3).  One lane per cell. */
 int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
                       double coefficient, double *nut, void *stream);
+/* The Smagorinsky model with van Driest wall damping, arguments as ox_eddy_viscosity (model 0 only):
+ *   nut[e] = (coefficient Delta D)^2 sqrt(2 S:S),  D = 1 - exp(-y+ / a_plus),  y+ = dist[e] u_tau / nu
+ * dist[e], nearest[e] (device, kernel cell order): the wall distance of the cell's centroid and the position of its
+ * nearest wall facet (ox_walldist_query); u_tau = sqrt(|wss[nearest[e]]|) with wss (device [n_facets][gdim]) the kinematic
+ * wall shear of those facets (ox_wall_stress), or the constant u_tau where wss is NULL.  nearest[e] outside
+ * [0, n_facets) writes NaN and reads nothing; wss = 0 gives D = 0 and nut = 0. */
+typedef struct {
+  const double *dist;      /* [n_cells]                                       */
+  const int32_t *nearest;  /* [n_cells]                                       */
+  const double *wss;       /* [n_facets][gdim] or NULL                        */
+  double u_tau;            /* used where wss is NULL; finite, >= 0            */
+  double nu, a_plus;       /* > 0                                             */
+  int64_t n_facets;
+} ox_vandriest;
+int ox_eddy_viscosity_damped(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
+                             double coefficient, const ox_vandriest *vd, double *nut, void *stream);
 /* ---- generalised-Newtonian laws and the full stress form ---- */
 /* nut[e] = max(nu(gd_e) - base, 0), gd = sqrt(2 S:S) with S = sym(grad uab) at the cell's centroid (the quantity of
  * ox_eddy_viscosity's Smagorinsky model), arguments as there.  law 2, Carreau-Yasuda, params = {nu0, nu_inf, lam, n, a}:
@@ -783,6 +799,26 @@ typedef struct ox_tracer_args {
   double *age, *path, *t_exit;
 } ox_tracer_args;
 int ox_tracer_advance(const ox_tracer_args *args, void *stream);
+
+/* ---- Distance to the nearest wall facet (ox_probe.hip) ------------------------------------------
+ * facet_xyz (device [n_facets][gdim][gdim]): the vertices of the wall facets, segments in 2-D and triangles in 3-D;
+ * n_facets >= 1.  The object copies them, lays the locator's uniform grid over their bounding box (an axis without
+ * extent gets one bin) and keeps per bin the ascending list of the facets whose box overlaps it.  bins3 (host int[3],
+ * 1..1024 each, or NULL): the bins per axis instead of the computed ones; (1, 1, 1) is a brute-force search by the same
+ * kernel.  Creation synchronises `stream`; queries are stream-ordered and read nothing back.
+ *   ox_walldist_query: one lane per point x[i][gdim] (+ shift[gdim], host, NULL = 0): rings of bins of growing Chebyshev
+ *       radius around the point's (clamped) bin until nothing outside them can be nearer; points outside the grid are
+ *       legal.  dist[i] = the distance to the closest point of the nearest facet, nearest[i] = its position in
+ *       facet_xyz; of facets at the same distance (bit for bit) the LOWEST position.  Both are the same bits whatever
+ *       the grid.  A non-finite point: dist = NaN, nearest = -1.  merge != 0: (dist, nearest) hold an earlier result; it
+ *       is kept where it is not larger (equal distance: the lower position) -- how periodic images are searched. */
+typedef struct ox_walldist ox_walldist;
+int ox_walldist_create(int gdim, const double *facet_xyz, int64_t n_facets, const int *bins3, void *stream,
+                       ox_walldist **out);
+int ox_walldist_destroy(ox_walldist *wd);
+int ox_walldist_info(const ox_walldist *wd, int64_t *n_facets, int64_t *n_bins, int64_t *n_list, int *bins_per_axis3);
+int ox_walldist_query(const ox_walldist *wd, int64_t n_points, const double *x, const double *shift, int merge,
+                      double *dist, int32_t *nearest, void *stream);
 
 /* ---- Passive scalar transport (ox_scalar.hip) ------------------------------------------------------------------------
  * The Crank-Nicolson system of a group of 1..OX_MAXC scalars (same diffusivity kappa, same Dirichlet rows) from the

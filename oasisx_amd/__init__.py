@@ -10,12 +10,12 @@ from .bcs import DirichletBC, LocatorMethod, PressureBC
 from .diagnostics import FlowDiagnostics, FlowStatistics, ProfileStatistics, slab_bins
 from .fracstep import FractionalStep_AB_CN
 from .function import Projector
-from .geometry import Probes  # noqa: F401
+from .geometry import Probes, WallDistance  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
 from .scalar import ScalarFlux, ScalarTransport
 from .tracers import Tracers
-from .viscosity import CarreauYasuda, CellViscosity, Cross, PowerLaw, Smagorinsky, Wale
+from .viscosity import CarreauYasuda, CellViscosity, Cross, PowerLaw, Smagorinsky, VanDriest, Wale
 from .wall import WallStress
 
 logging.basicConfig()
@@ -32,6 +32,8 @@ __all__ = [
     "ScalarFlux",
     "Smagorinsky",
     "Wale",
+    "VanDriest",
+    "WallDistance",
     "CellViscosity",
     "CarreauYasuda",
     "Cross",

@@ -171,6 +171,18 @@ class ox_first_args(C.Structure):
     ]
 
 
+class ox_vandriest(C.Structure):
+    _fields_ = [
+        ("dist", C.c_void_p),
+        ("nearest", C.c_void_p),
+        ("wss", C.c_void_p),
+        ("u_tau", C.c_double),
+        ("nu", C.c_double),
+        ("a_plus", C.c_double),
+        ("n_facets", C.c_int64),
+    ]
+
+
 class ox_mg_level(C.Structure):
     _fields_ = [
         ("A", ox_sell),
@@ -311,6 +323,7 @@ SIGNATURES = {
     "ox_assemble_first": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), C.POINTER(ox_sell),
                                C.POINTER(ox_sell), C.POINTER(ox_first_args), _I, _P]),
     "ox_eddy_viscosity": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, _P, _P]),
+    "ox_eddy_viscosity_damped": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, C.POINTER(ox_vandriest), _P, _P]),
     "ox_viscosity_law": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, C.POINTER(_D), _I, _P, _P]),
     "ox_assemble_stress_transpose": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P, _P, _D, _P, _P]),
     "ox_flow_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _D, _D, _P, _P, _P, _P]),
@@ -353,6 +366,10 @@ SIGNATURES = {
     "ox_eval_points": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P]),
     "ox_probe_sample": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _L, _L, _P]),
     "ox_tracer_advance": (_I, [C.POINTER(ox_tracer_args), _P]),
+    "ox_walldist_create": (_I, [_I, _P, _L, C.POINTER(_I), _P, C.POINTER(_P)]),
+    "ox_walldist_destroy": (_I, [_P]),
+    "ox_walldist_info": (_I, [_P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),
+    "ox_walldist_query": (_I, [_P, _L, _P, C.POINTER(_D), _I, _P, _P, _P]),
     "ox_scalar_rows": (_I, [C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _D, _D, _I,
                             _P, _P, _P, _P, _P]),
     "ox_buoyancy_rows": (_I, [C.POINTER(ox_sell), _I, _I, C.POINTER(ox_buoy_term), _P, _P]),

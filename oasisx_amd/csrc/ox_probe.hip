@@ -46,13 +46,39 @@ struct ox_locator {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // set-up kernels
+// the block's box and the sum of its items' extents: minima, maxima, sums into partial[blockIdx.x][3 D] (a fixed order: the
+// sums are the same on every run)
+template <int D>
+__device__ __forceinline__ void loc_block_box(const double (&mn)[D], const double (&mx)[D], const double (&sm)[D],
+                                              double *__restrict__ partial) {
+  __shared__ double red[4 * 3 * D];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    double a = mn[k], b = mx[k], c = sm[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+      a = fmin(a, __shfl_down(a, off, 64)), b = fmax(b, __shfl_down(b, off, 64)), c += __shfl_down(c, off, 64);
+    if (lane == 0) red[wave * 3 * D + k] = a, red[wave * 3 * D + D + k] = b, red[wave * 3 * D + 2 * D + k] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 * D) {
+    const int k = threadIdx.x;
+    double v = red[k];
+    for (int w = 1; w < 4; ++w) {
+      const double p = red[w * 3 * D + k];
+      v = k < D ? fmin(v, p) : (k < 2 * D ? fmax(v, p) : v + p);
+    }
+    partial[(size_t)blockIdx.x * 3 * D + k] = v;
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(256) void k_loc_geom(int64_t n, int64_t n_verts, int64_t n_mesh_cells,
                                                   const double *__restrict__ coords, const int64_t *__restrict__ cells,
                                                   const int64_t *__restrict__ ids, double tol, double pad_abs,
                                                   double *__restrict__ x0, double *__restrict__ grad,
                                                   double *__restrict__ box, double *__restrict__ partial) {
-  __shared__ double red[4 * 3 * D];
   double mn[D], mx[D], sm[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) mn[k] = INFINITY, mx[k] = -INFINITY, sm[k] = 0.0;
@@ -102,27 +128,7 @@ __global__ __launch_bounds__(256) void k_loc_geom(int64_t n, int64_t n_verts, in
       if (ok) mn[k] = l, mx[k] = h, sm[k] = h - l;
     }
   }
-  // the block's box and the sum of its cells' padded extents: minima, maxima, sums (a fixed order: the sums are the same
-  // on every run)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    double a = mn[k], b = mx[k], c = sm[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-      a = fmin(a, __shfl_down(a, off, 64)), b = fmax(b, __shfl_down(b, off, 64)), c += __shfl_down(c, off, 64);
-    if (lane == 0) red[wave * 3 * D + k] = a, red[wave * 3 * D + D + k] = b, red[wave * 3 * D + 2 * D + k] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3 * D) {
-    const int k = threadIdx.x;
-    double v = red[k];
-    for (int w = 1; w < 4; ++w) {
-      const double p = red[w * 3 * D + k];
-      v = k < D ? fmin(v, p) : (k < 2 * D ? fmax(v, p) : v + p);
-    }
-    partial[(size_t)blockIdx.x * 3 * D + k] = v;
-  }
+  loc_block_box<D>(mn, mx, sm, partial);
 }
 
 // out[k] = min (k < D) / max (D <= k < 2 D) / sum (k >= 2 D) over the blocks' partial records; one block
@@ -630,8 +636,85 @@ static void loc_free(ox_locator *L) {
   delete L;
 }
 
+// Bins per axis, about one item per bin on stretched domains too: r_k = (extent of the box) / (mean extent of an item)
+// items span axis k; the bins are r_k scaled by one factor that makes their product n.  (Items of one size on every axis,
+// mean_k = m: r_k (n / prod r)^(1/d) = ext_k / (vol / n)^(1/d), the isotropic length.)  hb: minima, maxima and summed
+// extents of the n items, [3 D].  bins3 (may be null) overrides the count on every axis that has an extent.
 template <int D>
-static int loc_create(ox_locator *L, const double *coords, int64_t n_verts, const int64_t *cells, int64_t n_mesh_cells,
+static int loc_size_grid(const char *who, LocGrid &G, const double *hb, int64_t n, const int *bins3, int64_t *n_bins) {
+  double r[D], prod = 1.0;
+  int nz = 0;
+  for (int k = 0; k < D; ++k) {
+    if (!(hb[k] <= hb[D + k])) OX_FAIL("%s: the cells have no finite bounding box", who);
+    G.lo[k] = hb[k], G.hi[k] = hb[D + k];
+    const double ext = G.hi[k] - G.lo[k], mean = hb[2 * D + k] / (double)n;
+    r[k] = ext > 0.0 && mean > 0.0 ? ext / mean : 0.0;
+    if (!(r[k] >= 1.0)) r[k] = 0.0;  // (a flat or empty axis, or a NaN: one bin)
+    if (r[k] > 0.0) prod *= r[k], ++nz;
+  }
+  const double scale = nz ? pow((double)n / prod, 1.0 / nz) : 1.0;
+  int64_t nbins = 1;
+  for (int k = 0; k < 3; ++k) G.nb[k] = 1;
+  for (int k = 0; k < D; ++k) {
+    const double ext = G.hi[k] - G.lo[k];
+    double q = r[k] > 0.0 && scale > 0.0 ? ceil(r[k] * scale) : 1.0;
+    if (bins3 && ext > 0.0) q = (double)bins3[k];
+    if (!(q >= 1.0)) q = 1.0;
+    if (q > 1024.0) q = 1024.0;
+    G.nb[k] = (int)q;
+    G.inv_h[k] = ext > 0.0 ? q / ext : 0.0;
+    nbins *= G.nb[k];
+  }
+  for (int k = D; k < 3; ++k) G.lo[k] = G.hi[k] = G.inv_h[k] = 0.0;
+  if (nbins > OX_LOC_MAX_BINS) OX_FAIL("%s: %lld bins", who, (long long)nbins);
+  *n_bins = nbins;
+  return 0;
+}
+
+// Per bin the ASCENDING list of the items whose box [n][2 D] overlaps it: count, scan, fill, sort.  Allocates *mem_grid
+// (bin_ptr and the scan's work space) and *mem_list; synchronises the stream.
+template <int D>
+static int loc_build_lists(const char *who, const LocGrid &G, const double *box, int64_t n, int64_t nbins, hipStream_t st,
+                           void **mem_grid, int64_t **bin_ptr_out, void **mem_list, int32_t **list_out,
+                           int64_t *n_list_out) {
+  const int nblk = (int)((n + 255) / 256);
+  const int64_t ntiles = (nbins + OX_LOC_SCAN_TILE - 1) / OX_LOC_SCAN_TILE;
+  const size_t gbytes = (size_t)(nbins + 1 + ntiles + 1) * sizeof(int64_t) + (size_t)nbins * sizeof(int);
+  if (hipMalloc(mem_grid, gbytes) != hipSuccess) OX_FAIL("%s: hipMalloc of %zu bytes failed", who, gbytes);
+  int64_t *bin_ptr = static_cast<int64_t *>(*mem_grid);
+  *bin_ptr_out = bin_ptr;
+  int64_t *tile_sum = bin_ptr + nbins + 1, *total = tile_sum + ntiles;
+  int *cursor = reinterpret_cast<int *>(total + 1);
+  OX_HIP(hipMemsetAsync(cursor, 0, (size_t)nbins * sizeof(int), st));
+  hipLaunchKernelGGL((k_loc_bins<D, 0>), dim3(nblk), dim3(256), 0, st, n, G, box, nbins, bin_ptr, cursor, nullptr, (int64_t)0);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, st, nbins, cursor, bin_ptr, tile_sum);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_scan_sums, dim3(1), dim3(64), 0, st, ntiles, tile_sum, total);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_scan_add, dim3((unsigned)((nbins + 1 + 255) / 256)), dim3(256), 0, st, nbins, bin_ptr, tile_sum, total);
+  OX_LAUNCH_CHECK();
+  int64_t n_list = 0;
+  OX_HIP(hipMemcpyAsync(&n_list, total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  OX_HIP(hipStreamSynchronize(st));
+  if (n_list < 0) OX_FAIL("%s: list size %lld", who, (long long)n_list);
+  *n_list_out = n_list;
+  const size_t lbytes = (size_t)(n_list > 0 ? n_list : 1) * sizeof(int32_t);
+  if (hipMalloc(mem_list, lbytes) != hipSuccess) OX_FAIL("%s: hipMalloc of %zu bytes failed", who, lbytes);
+  int32_t *list = static_cast<int32_t *>(*mem_list);
+  *list_out = list;
+  OX_HIP(hipMemsetAsync(list, 0xff, lbytes, st));  // (-1: skipped by the queries)
+  OX_HIP(hipMemsetAsync(cursor, 0, (size_t)nbins * sizeof(int), st));
+  hipLaunchKernelGGL((k_loc_bins<D, 1>), dim3(nblk), dim3(256), 0, st, n, G, box, nbins, bin_ptr, cursor, list, n_list);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_sort, dim3((unsigned)((nbins + 255) / 256)), dim3(256), 0, st, nbins, bin_ptr, list, n_list);
+  OX_LAUNCH_CHECK();
+  OX_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+template <int D>
+static int loc_create(ox_locator *L,const double *coords, int64_t n_verts, const int64_t *cells, int64_t n_mesh_cells,
                       const int64_t *ids, double padding, hipStream_t st) {
   const int64_t n = L->n_cells;
   const int nblk = (int)((n + 255) / 256);
@@ -658,66 +741,9 @@ static int loc_create(ox_locator *L, const double *coords, int64_t n_verts, cons
   double hb[3 * D];
   OX_HIP(hipMemcpyAsync(hb, gbox, sizeof(hb), hipMemcpyDeviceToHost, st));
   OX_HIP(hipStreamSynchronize(st));
-  // bins per axis, about one cell per bin on stretched domains too: r_k = (extent of the box) / (mean padded extent of a
-  // cell) cells span axis k; the bins are r_k scaled by one factor that makes their product n.  (Cells of one size on
-  // every axis, mean_k = m: r_k (n / prod r)^(1/d) = ext_k / (vol / n)^(1/d), the isotropic length.)
-  LocGrid &G = L->grid;
-  double r[D], prod = 1.0;
-  int nz = 0;
-  for (int k = 0; k < D; ++k) {
-    if (!(hb[k] <= hb[D + k])) OX_FAIL("ox_locator_create: the cells have no finite bounding box");
-    G.lo[k] = hb[k], G.hi[k] = hb[D + k];
-    const double ext = G.hi[k] - G.lo[k], mean = hb[2 * D + k] / (double)n;
-    r[k] = ext > 0.0 && mean > 0.0 ? ext / mean : 0.0;
-    if (!(r[k] >= 1.0)) r[k] = 0.0;  // (a flat or empty axis, or a NaN: one bin)
-    if (r[k] > 0.0) prod *= r[k], ++nz;
-  }
-  const double scale = nz ? pow((double)n / prod, 1.0 / nz) : 1.0;
-  int64_t nbins = 1;
-  for (int k = 0; k < 3; ++k) G.nb[k] = 1;
-  for (int k = 0; k < D; ++k) {
-    const double ext = G.hi[k] - G.lo[k];
-    double q = r[k] > 0.0 && scale > 0.0 ? ceil(r[k] * scale) : 1.0;
-    if (!(q >= 1.0)) q = 1.0;
-    if (q > 1024.0) q = 1024.0;
-    G.nb[k] = (int)q;
-    G.inv_h[k] = ext > 0.0 ? q / ext : 0.0;
-    nbins *= G.nb[k];
-  }
-  for (int k = D; k < 3; ++k) G.lo[k] = G.hi[k] = G.inv_h[k] = 0.0;
-  if (nbins > OX_LOC_MAX_BINS) OX_FAIL("ox_locator_create: %lld bins", (long long)nbins);
-  L->n_bins = nbins;
-  const int64_t ntiles = (nbins + OX_LOC_SCAN_TILE - 1) / OX_LOC_SCAN_TILE;
-  const size_t gbytes = (size_t)(nbins + 1 + ntiles + 1) * sizeof(int64_t) + (size_t)nbins * sizeof(int);
-  if (hipMalloc(&L->mem_grid, gbytes) != hipSuccess) OX_FAIL("ox_locator_create: hipMalloc of %zu bytes failed", gbytes);
-  L->bin_ptr = static_cast<int64_t *>(L->mem_grid);
-  int64_t *tile_sum = L->bin_ptr + nbins + 1, *total = tile_sum + ntiles;
-  int *cursor = reinterpret_cast<int *>(total + 1);
-  OX_HIP(hipMemsetAsync(cursor, 0, (size_t)nbins * sizeof(int), st));
-  hipLaunchKernelGGL((k_loc_bins<D, 0>), dim3(nblk), dim3(256), 0, st, n, G, L->box, nbins, L->bin_ptr, cursor, nullptr, (int64_t)0);
-  OX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_loc_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, st, nbins, cursor, L->bin_ptr, tile_sum);
-  OX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_loc_scan_sums, dim3(1), dim3(64), 0, st, ntiles, tile_sum, total);
-  OX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_loc_scan_add, dim3((unsigned)((nbins + 1 + 255) / 256)), dim3(256), 0, st, nbins, L->bin_ptr, tile_sum, total);
-  OX_LAUNCH_CHECK();
-  int64_t n_list = 0;
-  OX_HIP(hipMemcpyAsync(&n_list, total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  OX_HIP(hipStreamSynchronize(st));
-  if (n_list < 0) OX_FAIL("ox_locator_create: list size %lld", (long long)n_list);
-  L->n_list = n_list;
-  const size_t lbytes = (size_t)(n_list > 0 ? n_list : 1) * sizeof(int32_t);
-  if (hipMalloc(&L->mem_list, lbytes) != hipSuccess) OX_FAIL("ox_locator_create: hipMalloc of %zu bytes failed", lbytes);
-  L->list = static_cast<int32_t *>(L->mem_list);
-  OX_HIP(hipMemsetAsync(L->list, 0xff, lbytes, st));  // (-1: skipped by find)
-  OX_HIP(hipMemsetAsync(cursor, 0, (size_t)nbins * sizeof(int), st));
-  hipLaunchKernelGGL((k_loc_bins<D, 1>), dim3(nblk), dim3(256), 0, st, n, G, L->box, nbins, L->bin_ptr, cursor, L->list, n_list);
-  OX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_loc_sort, dim3((unsigned)((nbins + 255) / 256)), dim3(256), 0, st, nbins, L->bin_ptr, L->list, n_list);
-  OX_LAUNCH_CHECK();
-  OX_HIP(hipStreamSynchronize(st));
-  return 0;
+  if (loc_size_grid<D>("ox_locator_create", L->grid, hb, n, nullptr, &L->n_bins)) return -1;
+  return loc_build_lists<D>("ox_locator_create", L->grid, L->box, n, L->n_bins, st, &L->mem_grid, &L->bin_ptr, &L->mem_list,
+                            &L->list, &L->n_list);
 }
 
 extern "C" int ox_locator_create(int gdim, const double *coords, int64_t n_vertices, const int64_t *cells, int64_t n_cells,
@@ -876,6 +902,304 @@ extern "C" int ox_tracer_advance(const ox_tracer_args *a, void *stream) {
     case 32: hipLaunchKernelGGL((k_tracer_advance<3, 2>), grid, blk, 0, st, P); break;
     default: hipLaunchKernelGGL((k_tracer_advance<3, 3>), grid, blk, 0, st, P); break;
   }
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Distance to the nearest wall facet.  The locator's grid over the bounding box of the facets
+// (segments in 2-D, triangles in 3-D), per bin the ascending list of the facets whose box overlaps it.  A query takes one
+// lane per point: the bin of the point (clamped into the grid: points outside are legal), then rings of bins of growing
+// Chebyshev radius r around it.  Kept: (d2, position), ties to the lower position -- a minimum that does not depend on the
+// order of the visits.  After ring r a facet that was not met lies, on some axis, wholly in bins below b - r or above
+// b + r: it is at least min_k min(x_k - edge(b_k - r), edge(b_k + r + 1) - x_k) away (sides that leave the grid do not
+// count), less a rounding allowance; the walk stops when d2 <= that bound squared, or when the rings cover the grid.
+// The per-facet distance forms the closest point q and d2 = |x - q|^2 from the difference vector: exact zeros on the
+// vertices, an error of eps L elsewhere.  It is a pure function of (x, facet), so (dist, nearest) are the same bits
+// whatever the grid.  No atomics, no LDS, no scratch.
+struct ox_walldist {
+  int gdim;
+  int64_t n_f, n_bins, n_list;
+  LocGrid grid;
+  double h[3];       // bin widths (1 on an axis without extent: one bin, never an edge to measure against)
+  void *mem;         // xyz, box
+  void *mem_grid;    // bin_ptr
+  void *mem_list;
+  double *xyz;       // [n_f][D][D] vertices
+  double *box;       // [n_f][2 D]
+  int64_t *bin_ptr;  // [n_bins + 1]
+  int32_t *list;     // [n_list] facet positions, ascending inside every bin
+};
+
+struct WdVec {
+  double v[3];
+};
+
+// boxes of the facets and the block's box and summed extents (k_loc_geom's record for k_loc_box)
+template <int D>
+__global__ __launch_bounds__(256) void k_wd_geom(int64_t n, const double *__restrict__ xyz, double *__restrict__ box,
+                                                 double *__restrict__ partial) {
+  double mn[D], mx[D], sm[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) mn[k] = INFINITY, mx[k] = -INFINITY, sm[k] = 0.0;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      double l = xyz[i * D * D + k], h = l;
+#pragma unroll
+      for (int a = 1; a < D; ++a) l = fmin(l, xyz[(i * D + a) * D + k]), h = fmax(h, xyz[(i * D + a) * D + k]);
+      const bool ok = isfinite(l) && isfinite(h);  // (a facet with a non-finite vertex: in no bin, never the nearest)
+      box[i * 2 * D + k] = ok ? l : INFINITY, box[i * 2 * D + D + k] = ok ? h : -INFINITY;
+      if (ok) mn[k] = l, mx[k] = h, sm[k] = h - l;
+    }
+  }
+  loc_block_box<D>(mn, mx, sm, partial);
+}
+
+// squared distance of x to the segment (a, b): the clamped projection
+__device__ __forceinline__ double wd_facet_d2(const double *__restrict__ f, const double (&x)[2]) {
+  const double a[2] = {f[0], f[1]}, b[2] = {f[2], f[3]};
+  const double ab[2] = {b[0] - a[0], b[1] - a[1]}, ap[2] = {x[0] - a[0], x[1] - a[1]};
+  const double num = fma(ap[1], ab[1], ap[0] * ab[0]), den = fma(ab[1], ab[1], ab[0] * ab[0]);
+  double q[2];
+  if (!(num > 0.0)) q[0] = a[0], q[1] = a[1];
+  else if (num >= den) q[0] = b[0], q[1] = b[1];
+  else {
+    const double t = num / den;
+    q[0] = fma(t, ab[0], a[0]), q[1] = fma(t, ab[1], a[1]);
+  }
+  const double d0 = x[0] - q[0], d1 = x[1] - q[1];
+  return fma(d1, d1, d0 * d0);
+}
+
+__device__ __forceinline__ double wd_dot3(const double (&u)[3], const double (&v)[3]) {
+  return fma(u[2], v[2], fma(u[1], v[1], u[0] * v[0]));
+}
+
+// squared distance of x to the triangle (a, b, c): the closest point by its seven regions (three vertices, three edges,
+// the face)
+__device__ __forceinline__ double wd_facet_d2(const double *__restrict__ f, const double (&x)[3]) {
+  double a[3], b[3], c[3], ab[3], ac[3], ap[3], bp[3], cp[3], q[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    a[k] = f[k], b[k] = f[3 + k], c[k] = f[6 + k];
+    ab[k] = b[k] - a[k], ac[k] = c[k] - a[k];
+    ap[k] = x[k] - a[k], bp[k] = x[k] - b[k], cp[k] = x[k] - c[k];
+  }
+  const double d1 = wd_dot3(ab, ap), d2 = wd_dot3(ac, ap), d3 = wd_dot3(ab, bp), d4 = wd_dot3(ac, bp);
+  const double d5 = wd_dot3(ab, cp), d6 = wd_dot3(ac, cp);
+  const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+  if (d1 <= 0.0 && d2 <= 0.0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = a[k];
+  } else if (d3 >= 0.0 && d4 <= d3) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = b[k];
+  } else if (d6 >= 0.0 && d5 <= d6) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = c[k];
+  } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+    const double t = d1 / (d1 - d3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = fma(t, ab[k], a[k]);
+  } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+    const double t = d2 / (d2 - d6);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = fma(t, ac[k], a[k]);
+  } else if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
+    const double t = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = fma(t, c[k] - b[k], b[k]);
+  } else {
+    const double den = 1.0 / (va + vb + vc), v = vb * den, w = vc * den;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = fma(w, ac[k], fma(v, ab[k], a[k]));
+  }
+  double d[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[k] = x[k] - q[k];
+  return wd_dot3(d, d);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_wd_query(int64_t n, const double *__restrict__ xs, WdVec shift, int merge, LocGrid G,
+                                                  WdVec H, int64_t n_f, int64_t n_bins,
+                                                  const int64_t *__restrict__ bin_ptr, const int32_t *__restrict__ list,
+                                                  int64_t n_list, const double *__restrict__ xyz,
+                                                  double *__restrict__ dist, int32_t *__restrict__ nearest) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double x[D];
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    x[k] = xs[i * D + k] + shift.v[k];
+    finite = finite && isfinite(x[k]);
+  }
+  if (!finite) {  // touches no table
+    dist[i] = NAN, nearest[i] = -1;
+    return;
+  }
+  double old_d = INFINITY;
+  int32_t old_f = -1;
+  if (merge) {
+    old_d = dist[i], old_f = nearest[i];
+    if (!(old_d >= 0.0) || old_f < 0) old_d = INFINITY, old_f = -1;  // (nothing kept yet)
+  }
+  // b: the point's bin, clamped; slack: what the roundings of loc_bin and of the edges below can move an edge by
+  int b0 = 0, b1 = 0, b2 = 0;
+  double slack = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const int b = loc_bin(G, k, x[k]);
+    if (k == 0) b0 = b;
+    else if (k == 1) b1 = b;
+    else b2 = b;
+    slack = fmax(slack, 1e-14 * (fabs(x[k]) + fabs(G.lo[k]) + fabs(G.hi[k])));
+  }
+  const int nb0 = G.nb[0], nb1 = G.nb[1], nb2 = G.nb[2];
+  double best = INFINITY;
+  int32_t best_f = -1;
+  auto visit = [&](int64_t bin) {
+    if (bin < 0 || bin >= n_bins) return;
+    int64_t s0 = bin_ptr[bin], s1 = bin_ptr[bin + 1];
+    if (s0 < 0) s0 = 0;
+    if (s1 > n_list) s1 = n_list;
+    for (int64_t s = s0; s < s1; ++s) {
+      const int32_t f = list[s];
+      if (f < 0 || (int64_t)f >= n_f) continue;
+      const double d2 = wd_facet_d2(xyz + (size_t)f * D * D, x);
+      if (d2 < best || (d2 == best && f < best_f)) best = d2, best_f = f;  // (NaN: never)
+    }
+  };
+  const int rmax = max(nb0, max(nb1, nb2));
+  for (int r = 0; r < rmax; ++r) {
+    const int z0 = max(b2 - r, 0), z1 = min(b2 + r, nb2 - 1), y0 = max(b1 - r, 0), y1 = min(b1 + r, nb1 - 1);
+    const int x0 = max(b0 - r, 0), x1 = min(b0 + r, nb0 - 1);
+    for (int z = z0; z <= z1; ++z)
+      for (int y = y0; y <= y1; ++y) {
+        const int64_t row = ((int64_t)z * nb1 + y) * nb0;
+        if (abs(z - b2) == r || abs(y - b1) == r) {  // a row of the shell's faces: all of it
+          for (int xx = x0; xx <= x1; ++xx) visit(row + xx);
+        } else {  // the shell's two end bins of the row
+          if (b0 - r >= 0) visit(row + b0 - r);
+          if (b0 + r < nb0) visit(row + b0 + r);
+        }
+      }
+    if (x0 == 0 && x1 == nb0 - 1 && y0 == 0 && y1 == nb1 - 1 && z0 == 0 && z1 == nb2 - 1) break;  // the whole grid
+    // the nearest a facet met in no ring so far can be
+    double bound = INFINITY;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int bk = k == 0 ? b0 : (k == 1 ? b1 : b2), nbk = k == 0 ? nb0 : (k == 1 ? nb1 : nb2);
+      if (bk - r > 0) bound = fmin(bound, x[k] - fma((double)(bk - r), H.v[k], G.lo[k]));
+      if (bk + r < nbk - 1) bound = fmin(bound, fma((double)(bk + r + 1), H.v[k], G.lo[k]) - x[k]);
+    }
+    bound -= slack;
+    if (bound > 0.0 && (best <= bound * bound || old_d < bound)) break;
+  }
+  double d = sqrt(best);
+  int32_t f = best_f;
+  if (best_f < 0) d = NAN;  // (no facet with a finite distance)
+  if (old_f >= 0 && (f < 0 || old_d < d || (old_d == d && old_f < f))) d = old_d, f = old_f;
+  dist[i] = d, nearest[i] = f;
+}
+
+static void wd_free(ox_walldist *W) {
+  if (!W) return;
+  if (W->mem) (void)hipFree(W->mem);
+  if (W->mem_grid) (void)hipFree(W->mem_grid);
+  if (W->mem_list) (void)hipFree(W->mem_list);
+  delete W;
+}
+
+template <int D>
+static int wd_create(ox_walldist *W, const double *facet_xyz, const int *bins3, hipStream_t st) {
+  const int64_t n = W->n_f;
+  const int nblk = (int)((n + 255) / 256);
+  const size_t dbl = (size_t)n * (D * D + 2 * D) + (size_t)nblk * 3 * D + 3 * D;
+  if (hipMalloc(&W->mem, dbl * sizeof(double)) != hipSuccess)
+    OX_FAIL("ox_walldist_create: hipMalloc of %zu bytes failed", dbl * sizeof(double));
+  double *p = static_cast<double *>(W->mem);
+  W->xyz = p, p += (size_t)n * D * D;
+  W->box = p, p += (size_t)n * 2 * D;
+  double *partial = p;
+  p += (size_t)nblk * 3 * D;
+  double *gbox = p;
+  OX_HIP(hipMemcpyAsync(W->xyz, facet_xyz, (size_t)n * D * D * sizeof(double), hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k_wd_geom<D>, dim3(nblk), dim3(256), 0, st, n, W->xyz, W->box, partial);
+  OX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_loc_box<D>, dim3(1), dim3(256), 0, st, partial, nblk, gbox);
+  OX_LAUNCH_CHECK();
+  double hb[3 * D];
+  OX_HIP(hipMemcpyAsync(hb, gbox, sizeof(hb), hipMemcpyDeviceToHost, st));
+  OX_HIP(hipStreamSynchronize(st));
+  if (loc_size_grid<D>("ox_walldist_create", W->grid, hb, n, bins3, &W->n_bins)) return -1;
+  for (int k = 0; k < 3; ++k) {
+    const double ext = W->grid.hi[k] - W->grid.lo[k];
+    W->h[k] = k < D && ext > 0.0 ? ext / (double)W->grid.nb[k] : 1.0;
+  }
+  return loc_build_lists<D>("ox_walldist_create", W->grid, W->box, n, W->n_bins, st, &W->mem_grid, &W->bin_ptr, &W->mem_list,
+                            &W->list, &W->n_list);
+}
+
+extern "C" int ox_walldist_create(int gdim, const double *facet_xyz, int64_t n_facets, const int *bins3, void *stream,
+                                  ox_walldist **out) {
+  if (!out) OX_FAIL("ox_walldist_create: null argument");
+  *out = nullptr;
+  if (gdim != 2 && gdim != 3) OX_FAIL("ox_walldist_create: gdim=%d", gdim);
+  if (!facet_xyz || n_facets < 1) OX_FAIL("ox_walldist_create: no wall facets (n_facets=%lld)", (long long)n_facets);
+  if (n_facets >= ((int64_t)1 << 31) - 256) OX_FAIL("ox_walldist_create: %lld facets", (long long)n_facets);
+  if (bins3)
+    for (int k = 0; k < gdim; ++k)
+      if (bins3[k] < 1 || bins3[k] > 1024) OX_FAIL("ox_walldist_create: bins3[%d]=%d (1..1024)", k, bins3[k]);
+  ox_walldist *W = new ox_walldist();
+  memset(W, 0, sizeof(*W));
+  W->gdim = gdim, W->n_f = n_facets;
+  hipStream_t st = ox_stream(stream);
+  const int rc = gdim == 2 ? wd_create<2>(W, facet_xyz, bins3, st) : wd_create<3>(W, facet_xyz, bins3, st);
+  if (rc) {
+    wd_free(W);
+    return -1;
+  }
+  *out = W;
+  return 0;
+}
+
+extern "C" int ox_walldist_destroy(ox_walldist *W) {
+  wd_free(W);
+  return 0;
+}
+
+extern "C" int ox_walldist_info(const ox_walldist *W, int64_t *n_facets, int64_t *n_bins, int64_t *n_list, int *bins_per_axis) {
+  if (!W) OX_FAIL("ox_walldist_info: null handle");
+  if (n_facets) *n_facets = W->n_f;
+  if (n_bins) *n_bins = W->n_bins;
+  if (n_list) *n_list = W->n_list;
+  if (bins_per_axis)
+    for (int k = 0; k < 3; ++k) bins_per_axis[k] = W->grid.nb[k];
+  return 0;
+}
+
+extern "C" int ox_walldist_query(const ox_walldist *W, int64_t n_points, const double *x, const double *shift, int merge,
+                                 double *dist, int32_t *nearest, void *stream) {
+  if (!W || (n_points > 0 && (!x || !dist || !nearest))) OX_FAIL("ox_walldist_query: null argument");
+  if (n_points <= 0) return 0;
+  WdVec s{{0.0, 0.0, 0.0}}, H{{W->h[0], W->h[1], W->h[2]}};
+  if (shift)
+    for (int k = 0; k < W->gdim; ++k) {
+      if (!std::isfinite(shift[k])) OX_FAIL("ox_walldist_query: shift[%d] is not finite", k);
+      s.v[k] = shift[k];
+    }
+  hipStream_t st = ox_stream(stream);
+  const dim3 grid((unsigned)((n_points + 255) / 256));
+  if (W->gdim == 2)
+    hipLaunchKernelGGL(k_wd_query<2>, grid, dim3(256), 0, st, n_points, x, s, merge ? 1 : 0, W->grid, H, W->n_f, W->n_bins,
+                       W->bin_ptr, W->list, W->n_list, W->xyz, dist, nearest);
+  else
+    hipLaunchKernelGGL(k_wd_query<3>, grid, dim3(256), 0, st, n_points, x, s, merge ? 1 : 0, W->grid, H, W->n_f, W->n_bins,
+                       W->bin_ptr, W->list, W->n_list, W->xyz, dist, nearest);
   OX_LAUNCH_CHECK();
   return 0;
 }

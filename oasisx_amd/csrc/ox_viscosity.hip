@@ -36,10 +36,15 @@ struct LawParams {
 template <int MODEL>
 using NutArg = std::conditional_t<(MODEL >= OX_NUT_CARREAU_YASUDA), LawParams, double>;
 
-template <int GDIM, int DEG, int MODEL>
+// van Driest damping: the tables of ox_vandriest by value; nothing where the flag is off
+struct NoDamping {};
+template <int VD>
+using DampArg = std::conditional_t<(VD != 0), ox_vandriest, NoDamping>;
+
+template <int GDIM, int DEG, int MODEL, int VD = 0>
 __global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const int32_t *__restrict__ cell_dofs,
                                                         const double *__restrict__ uab, NutArg<MODEL> coef2,
-                                                        double *__restrict__ nut) {
+                                                        double *__restrict__ nut, DampArg<VD> vd) {
   constexpr int ND = ox_nd(GDIM, DEG);
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= cells.n_cells) return;
@@ -62,7 +67,27 @@ __global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const in
     delta2 = h * h;
   }
   double out;
-  if constexpr (MODEL == OX_NUT_SMAGORINSKY) {
+  if constexpr (MODEL == OX_NUT_SMAGORINSKY && VD != 0) {
+    // D = 1 - exp(-y+ / A+), y+ = d u_tau / nu, u_tau = sqrt(|wss|) of the centroid's nearest wall facet
+    const int32_t f = vd.nearest[e];
+    if (f < 0 || (int64_t)f >= vd.n_facets) {
+      out = __longlong_as_double(0x7ff8000000000000LL);
+    } else {
+      double ut = vd.u_tau;
+      if (vd.wss) {
+        double m2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < GDIM; ++k) {
+          const double w = vd.wss[(size_t)f * GDIM + k];
+          m2 = fma(w, w, m2);
+        }
+        ut = sqrt(sqrt(m2));
+      }
+      const double yp = vd.dist[e] * ut / vd.nu;
+      const double dmp = -expm1(-yp / vd.a_plus);
+      out = coef2 * delta2 * (dmp * dmp) * sqrt(2.0 * ss);
+    }
+  } else if constexpr (MODEL == OX_NUT_SMAGORINSKY) {
     out = coef2 * delta2 * sqrt(2.0 * ss);
   } else if constexpr (MODEL == OX_NUT_CARREAU_YASUDA) {
     const double gd = sqrt(2.0 * ss);
@@ -123,7 +148,8 @@ extern "C" int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, c
 #define OX_NUT_CASE(GD, DG, MD)                                                                                        \
   if (g == GD && degree == DG && model == MD) {                                                                        \
     if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                          \
-    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, c2, nut); \
+    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, c2, nut, \
+                       NoDamping{});                                                                                   \
     if (ox_prof_on) ox_prof_stop(st);                                                                                  \
     OX_LAUNCH_CHECK();                                                                                                 \
     return 0;                                                                                                          \
@@ -132,6 +158,39 @@ extern "C" int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, c
   OX_NUT_CASE(3, 1, OX_NUT_WALE) OX_NUT_CASE(3, 2, OX_NUT_WALE) OX_NUT_CASE(3, 3, OX_NUT_WALE)
 #undef OX_NUT_CASE
   OX_FAIL("ox_eddy_viscosity: unsupported gdim=%d degree=%d", g, degree);
+}
+
+// Smagorinsky with van Driest damping: k_eddy_viscosity with the damping flag; 12 B more per cell are streamed (dist,
+// nearest) and gdim doubles of wss gathered.
+extern "C" int ox_eddy_viscosity_damped(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs,
+                                        const double *uab, double coefficient, const ox_vandriest *vd, double *nut,
+                                        void *stream) {
+  if (!cells || !cell_dofs || !uab || !nut || !cells->geom || !vd) OX_FAIL("ox_eddy_viscosity_damped: null argument");
+  if (!vd->dist || !vd->nearest) OX_FAIL("ox_eddy_viscosity_damped: null argument (dist, nearest)");
+  if (!(coefficient >= 0.0)) OX_FAIL("ox_eddy_viscosity_damped: coefficient=%g", coefficient);
+  if (model != OX_NUT_SMAGORINSKY) OX_FAIL("ox_eddy_viscosity_damped: model=%d (0: Smagorinsky)", model);
+  if (!(vd->nu > 0.0) || !std::isfinite(vd->nu)) OX_FAIL("ox_eddy_viscosity_damped: nu=%g", vd->nu);
+  if (!(vd->a_plus > 0.0) || !std::isfinite(vd->a_plus)) OX_FAIL("ox_eddy_viscosity_damped: a_plus=%g", vd->a_plus);
+  if (!vd->wss && (!(vd->u_tau >= 0.0) || !std::isfinite(vd->u_tau))) OX_FAIL("ox_eddy_viscosity_damped: u_tau=%g", vd->u_tau);
+  if (vd->n_facets < 1 || vd->n_facets > (int64_t)0x7fffffff)
+    OX_FAIL("ox_eddy_viscosity_damped: n_facets=%lld", (long long)vd->n_facets);
+  const int64_t nblk = ox_cell_blocks("ox_eddy_viscosity_damped", cells);
+  if (nblk <= 0) return (int)nblk;
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const double c2 = coefficient * coefficient;
+#define OX_NUT_VD_CASE(GD, DG)                                                                                        \
+  if (g == GD && degree == DG) {                                                                                      \
+    if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                         \
+    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, OX_NUT_SMAGORINSKY, 1>), dim3(nblk), dim3(256), 0, st, *cells,       \
+                       cell_dofs, uab, c2, nut, *vd);                                                                 \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                 \
+    OX_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                         \
+  }
+  OX_FOR_GDIM_DEG(OX_NUT_VD_CASE)
+#undef OX_NUT_VD_CASE
+  OX_FAIL("ox_eddy_viscosity_damped: unsupported gdim=%d degree=%d", g, degree);
 }
 
 // nut[e] = max(nu(gd_e) - base, 0) of a generalised-Newtonian law (include/oasisx_hip.h): the centroid gradient of
@@ -170,7 +229,8 @@ extern "C" int ox_viscosity_law(int law, int degree, const ox_cells *cells, cons
 #define OX_LAW_CASE(GD, DG, MD)                                                                                       \
   if (g == GD && degree == DG && law == MD) {                                                                         \
     if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                         \
-    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, P, nut); \
+    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, P, nut, \
+                       NoDamping{});                                                                                  \
     if (ox_prof_on) ox_prof_stop(st);                                                                                 \
     OX_LAUNCH_CHECK();                                                                                                \
     return 0;                                                                                                         \

@@ -27,7 +27,7 @@ from .fem import DGSpace, Function, FunctionSpace, HighOrderLagrangeSpace, Vecto
 from .native import _Handle
 
 __all__ = ["bb_tree", "compute_collisions_points", "compute_colliding_cells", "AdjacencyList", "BoundingBoxTree",
-           "Probes", "DEFAULT_TOL"]
+           "Probes", "WallDistance", "DEFAULT_TOL"]
 
 DEFAULT_TOL = 1e-10  # on the (dimensionless) barycentric coordinates
 
@@ -148,6 +148,106 @@ def compute_colliding_cells(mesh, candidates: AdjacencyList, x) -> AdjacencyList
     if n != candidates.num_nodes:
         raise ValueError(f"compute_colliding_cells: {n} points, candidates for {candidates.num_nodes}")
     return candidates
+
+
+# ---- wall distance ----------------------------------------------------------------------------------------------------
+class WallDistance:
+    """Distance to the nearest wall facet and that facet, for any point, on the device (``ox_walldist_*``,
+    csrc/ox_probe.hip).
+
+    Args:
+        mesh: one GPU (``comm.size > 1`` raises ``NotImplementedError``)
+        facets: ``None``: all exterior facets (on a ``make_periodic`` mesh without the identified faces);
+            ``(meshtags, id)`` / ``(meshtags, (id, ...))``: the facets of those values; an array of facet ids.  An empty
+            selection raises ``ValueError``.  Order: by tag, then by facet id (``wall.select_facets``) -- ``.facets``
+        bins: bins per axis of the background grid instead of the computed ones; ``(1, 1, 1)`` searches every facet
+
+    The distance is to the closest point of the facet (a segment or a triangle), not to its plane.  On a periodic mesh every
+    query is the minimum over the images ``x + s * period``, ``s in {-1, 0, 1}`` per periodic axis.
+    """
+
+    def __init__(self, mesh, facets=None, bins=None, _selection=None):
+        from .wall import select_facets
+
+        comm = getattr(mesh, "comm", None)
+        if comm is not None and getattr(comm, "size", 1) > 1:
+            raise NotImplementedError("WallDistance on a mesh partition (comm.size > 1): the search is built for one GPU")
+        d = mesh.gdim
+        # (_selection: facet ids a caller has ordered by select_facets already -- VanDriest shares them with its FacetSet)
+        ids = select_facets(mesh, facets, "WallDistance")[0] if _selection is None else np.asarray(_selection, dtype=np.int64)
+        if ids.shape[0] == 0:
+            raise ValueError("WallDistance: the selection holds no facet")
+        fv, _ = mesh._entities(d - 1)
+        if ids.min() < 0 or ids.max() >= fv.shape[0]:
+            raise ValueError("WallDistance: facet ids are indices of the mesh's facets")
+        b3 = None
+        if bins is not None:
+            b = [int(v) for v in np.atleast_1d(bins)]
+            if len(b) not in (d, 3) or min(b) < 1 or max(b) > 1024:
+                raise ValueError(f"WallDistance: bins = {bins!r}: {d} counts in 1..1024")
+            b3 = (C.c_int * 3)(*(b[:d] + [1] * (3 - d)))
+        self.mesh, self.gdim = mesh, d
+        self.facets, self.n_facets = ids, int(ids.shape[0])
+        per = getattr(mesh, "periodic", None)
+        self._shifts = [None]
+        if per is not None:
+            import itertools
+
+            period = np.asarray(per.period, dtype=np.float64).reshape(-1)
+            self._shifts = []
+            for s in itertools.product((0, -1, 1), repeat=len(per.axes)):  # (the unshifted search first)
+                v = np.zeros(3)
+                for k, sk in zip(per.axes, s):
+                    v[k] = sk * period[k]
+                self._shifts.append(v if any(s) else None)
+        if mesh.device.type != "cuda":
+            raise _lib.OasisxHipError("WallDistance: the search runs on the GPU (a mesh on a CUDA/HIP device); oasisx_amd "
+                                      "has no CPU fallback")
+        lib = _lib.load()
+        xyz = mesh.coords[torch.from_numpy(fv[ids].astype(np.int64)).to(mesh.device)].to(torch.float64).contiguous()
+        h = C.c_void_p()
+        _lib.check(lib.ox_walldist_create(d, _lib.ptr(xyz), self.n_facets, b3, _lib.current_stream(), C.byref(h)),
+                   "ox_walldist_create")
+        self._owner = _Handle(h, lib.ox_walldist_destroy)
+        self._h = h
+
+    def info(self) -> dict:
+        n, nb, nl = C.c_int64(), C.c_int64(), C.c_int64()
+        per = (C.c_int * 3)()
+        _lib.check(_lib.load().ox_walldist_info(self._h, C.byref(n), C.byref(nb), C.byref(nl), per), "ox_walldist_info")
+        return {"facets": n.value, "bins": nb.value, "list": nl.value, "bins_per_axis": list(per)[: self.gdim]}
+
+    def query(self, x):
+        """(dist, nearest): per point the distance to the nearest wall facet, float64 (n,), and that facet's position in
+        ``.facets``, int32 (n,) -- the lowest among facets at the same distance; both on the device.  A non-finite point:
+        NaN and -1."""
+        X = as_points(x, self.gdim, self.mesh.device)
+        n = int(X.shape[0])
+        dist = torch.empty(n, dtype=torch.float64, device=X.device)
+        near = torch.empty(n, dtype=torch.int32, device=X.device)
+        if n == 0:
+            return dist, near
+        lib, st = _lib.load(), _lib.current_stream()
+        for k, s in enumerate(self._shifts):
+            sh = None if s is None else (C.c_double * 3)(*s)
+            _lib.check(lib.ox_walldist_query(self._h, n, _lib.ptr(X), sh, int(k > 0), _lib.ptr(dist), _lib.ptr(near), st),
+                       "ox_walldist_query")
+        return dist, near
+
+    def cells(self):
+        """(dist, nearest) at the cell centroids, in the mesh's cell order."""
+        m = self.mesh
+        return self.query(m.coords[m.cells.to(torch.int64)].mean(dim=1))
+
+    def function(self, V) -> Function:
+        """A ``Function`` on the scalar Lagrange space ``V`` holding the distance at ``V``'s dof coordinates."""
+        Vs = scalar_space(V)
+        if Vs is not V:
+            raise TypeError("WallDistance.function: a scalar FunctionSpace")
+        f = Function(V, name="wall_distance")
+        dist, _ = self.query(V.x)
+        f._storage.dev()[: int(dist.shape[0]), 0].copy_(dist)  # (device to device: nothing is read back)
+        return f
 
 
 # ---- spaces -----------------------------------------------------------------------------------------------------------

@@ -22,6 +22,12 @@ Per ``assemble_first``: one kernel writes ``nut_c`` from ``grad u_ab`` at the ce
 csrc/ox_viscosity.hip; :class:`CellViscosity` has nothing to evaluate), then the fused assembly kernel adds
 ``nut_c K_c`` to the convection rows it forms anyway (``ox_assemble_first`` with ``ox_first_args.nut``): no second pass over the pattern, no
 second matrix.  ``Delta_c = |cell|^(1/gdim)``.
+
+Wall damping: ``Smagorinsky(Cs, damping=VanDriest(walls))`` multiplies the length scale by
+``D_c = 1 - exp(-y+_c / A_plus)``, ``y+_c = d_c u_tau,c / nu``: ``d_c`` the distance of the cell's centroid to the nearest
+wall facet (:class:`oasisx_amd.geometry.WallDistance`, fixed when the solver is built) and ``u_tau,c = sqrt(|wss|)`` of that
+facet, the kinematic facet-mean shear of ``u_ab`` with the molecular ``nu`` (one ``ox_wall_stress`` launch per
+``assemble_first``), so that ``nut`` vanishes at the wall instead of peaking there.
 """
 from __future__ import annotations
 
@@ -30,7 +36,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["Smagorinsky", "Wale", "CellViscosity", "CarreauYasuda", "Cross", "PowerLaw"]
+__all__ = ["Smagorinsky", "Wale", "CellViscosity", "CarreauYasuda", "Cross", "PowerLaw", "VanDriest"]
 
 
 def _coefficient(what, v):
@@ -51,7 +57,7 @@ class _KernelModel:
     def bind(self, solver):
         pass
 
-    def evaluate(self, solver, nut: torch.Tensor):
+    def evaluate(self, solver, nut: torch.Tensor, nu=None):
         Vi = solver._Vi[0][0]
         import ctypes as C
 
@@ -60,15 +66,126 @@ class _KernelModel:
                                                  _lib.current_stream()), "ox_eddy_viscosity")
 
 
+class VanDriest:
+    """Van Driest wall damping of the Smagorinsky length scale: ``D_c = 1 - exp(-y+_c / A_plus)``, ``y+_c = d_c u_tau,c / nu``.
+
+    Args:
+        facets: the walls -- ``None``: all exterior facets (on a ``make_periodic`` mesh without the identified faces);
+            ``(meshtags, id | ids)``; an array of facet ids.  Interior facets raise ``ValueError``, as for ``WallStress``
+        A_plus: the damping constant (26 in the channel-flow literature)
+        u_tau: ``None``: ``sqrt(|wss|)`` of the nearest wall facet, evaluated from ``u_ab`` in every ``assemble_first``;
+            a float: that constant friction velocity everywhere (no wall-stress launch)
+
+    ``d_c`` and the nearest facet of every centroid are found once, when the solver is built."""
+
+    def __init__(self, facets=None, A_plus: float = 26.0, u_tau=None):
+        self.facets_arg = facets
+        self.A_plus = float(A_plus)
+        if not np.isfinite(self.A_plus) or self.A_plus <= 0.0:
+            raise ValueError(f"VanDriest: A_plus must be finite and > 0 (got {A_plus})")
+        self.u_tau = None if u_tau is None else float(u_tau)
+        if self.u_tau is not None and (not np.isfinite(self.u_tau) or self.u_tau < 0.0):
+            raise ValueError(f"VanDriest: u_tau must be finite and >= 0 (got {u_tau})")
+        self.wall_distance = None
+        self._nu = None
+
+    def check(self, mesh):
+        """What can be refused without the library: an empty wall selection."""
+        from .wall import select_facets
+
+        sel = select_facets(mesh, self.facets_arg, "VanDriest")
+        if sel[0].shape[0] == 0:
+            raise ValueError("VanDriest: the wall selection holds no facet")
+        return sel
+
+    def bind(self, solver):
+        from .geometry import WallDistance
+        from .wall import FacetSet
+
+        mesh = solver._mesh
+        ids, tag_of, tags = self.check(mesh)
+        fs = FacetSet(solver, ids, tag_of, tags.shape[0], "VanDriest", "the friction velocity of the wall damping is")
+        self.wall_distance = WallDistance(mesh, _selection=ids)
+        self.facets, self.n_facets = ids, fs.n_facets
+        self.cells, self.local_facets = fs.cells, fs.local_facets  # (mesh cell, opposite local vertex) per wall facet
+        self._rec = fs.rec
+        Vi = solver._Vi[0][0]
+        lc = Vi.local_cells.to(torch.int64)
+        cen = mesh.coords[mesh.cells.to(torch.int64)[lc]].mean(dim=1)
+        self._dist, self._nearest = self.wall_distance.query(cen)  # kernel cell order
+        d, dev = mesh.gdim, mesh.device
+        self._t, self._wss, self._ft = (torch.zeros((fs.n_facets, d), dtype=torch.float64, device=dev) for _ in range(3))
+
+    def evaluate(self, solver, coefficient: float, nut: torch.Tensor, nu):
+        import ctypes as C
+
+        if nu is None or not float(nu) > 0.0:
+            raise ValueError(f"VanDriest: y+ needs the molecular viscosity (viscosity_assemble(nu), got nu = {nu})")
+        nu = float(nu)
+        Vi, Q = solver._Vi[0][0], solver._Q
+        lib, st = solver._lib, _lib.current_stream()
+        if self.u_tau is None:  # wss of u_ab with the molecular nu alone; the pressure drops out of the shear
+            _lib.check(lib.ox_wall_stress(Vi.degree, Q.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
+                                          _lib.ptr(Q.cell_dofs), self.n_facets, _lib.ptr(self._rec), solver._UAB.rptr(),
+                                          solver._P.rptr(), None, nu, 0.0, _lib.ptr(self._t), _lib.ptr(self._wss),
+                                          _lib.ptr(self._ft), None, None, None, st), "ox_wall_stress")
+        vd = _lib.ox_vandriest(self._dist.data_ptr(), self._nearest.data_ptr(),
+                               self._wss.data_ptr() if self.u_tau is None else None,
+                               0.0 if self.u_tau is None else self.u_tau, nu, self.A_plus, self.n_facets)
+        _lib.check(lib.ox_eddy_viscosity_damped(0, Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
+                                                solver._UAB.rptr(), coefficient, C.byref(vd), _lib.ptr(nut), st),
+                   "ox_eddy_viscosity_damped")
+        self._nu = nu
+
+    def friction_velocity(self) -> torch.Tensor:
+        """``u_tau`` per wall facet of the last ``assemble_first`` (the constant where one was given)."""
+        if self.u_tau is not None:
+            return torch.full((self.n_facets,), self.u_tau, dtype=torch.float64, device=self._dist.device)
+        return torch.sqrt(torch.sqrt((self._wss * self._wss).sum(dim=1)))
+
+    def wall_units(self, solver):
+        """``(y_plus, damping)`` per cell of the last ``assemble_first``, device tensors in the MESH's cell order."""
+        if self.wall_distance is None or self._nu is None:
+            raise RuntimeError("VanDriest.wall_units: no assemble_first has run with this damping")
+        yp_k = self._dist * self.friction_velocity()[self._nearest.to(torch.int64)] / self._nu
+        lc = solver._Vi[0][0].local_cells.to(torch.int64)
+        yp = torch.zeros(int(solver._mesh.num_cells), dtype=torch.float64, device=yp_k.device)
+        yp[lc] = yp_k
+        return yp, -torch.expm1(-yp / self.A_plus)
+
+    def __repr__(self):
+        return f"VanDriest(A_plus={self.A_plus}, u_tau={self.u_tau})"
+
+
 class Smagorinsky(_KernelModel):
-    """``nut_c = (Cs Delta_c)^2 sqrt(2 S:S)``, ``S = sym(grad u_ab)`` at the cell centroid.  2-D and 3-D, P1 / P2 / P3."""
+    """``nut_c = (Cs Delta_c)^2 sqrt(2 S:S)``, ``S = sym(grad u_ab)`` at the cell centroid.  2-D and 3-D, P1 / P2 / P3.
+    ``damping``: a :class:`VanDriest` object: ``nut_c = (Cs Delta_c D_c)^2 sqrt(2 S:S)`` (``ox_eddy_viscosity_damped``);
+    ``None``: the calls of the undamped model, nothing else."""
 
     model_id = 0
 
-    def __init__(self, Cs: float = 0.1677):
+    def __init__(self, Cs: float = 0.1677, damping=None):
         self.coefficient = _coefficient("Smagorinsky", Cs)
+        if damping is not None and not isinstance(damping, VanDriest):
+            raise TypeError(f"Smagorinsky: damping is a VanDriest object or None (got {type(damping).__name__})")
+        self.damping = damping
+
+    def check_mesh(self, mesh):
+        if self.damping is not None:
+            self.damping.check(mesh)
+
+    def bind(self, solver):
+        if self.damping is not None:
+            self.damping.bind(solver)
+
+    def evaluate(self, solver, nut: torch.Tensor, nu=None):
+        if self.damping is None:
+            return super().evaluate(solver, nut)
+        self.damping.evaluate(solver, self.coefficient, nut, nu)
 
     def __repr__(self):
+        if self.damping is not None:
+            return f"Smagorinsky(Cs={self.coefficient}, damping={self.damping!r})"
         return f"Smagorinsky(Cs={self.coefficient})"
 
 
@@ -81,8 +198,11 @@ class Wale(_KernelModel):
 
     model_id = 1
 
-    def __init__(self, Cw: float = 0.325):
+    def __init__(self, Cw: float = 0.325, damping=None):
         self.coefficient = _coefficient("Wale", Cw)
+        if damping is not None:
+            raise ValueError("Wale: wall damping is refused -- the model's operator vanishes at a wall by construction "
+                             "(nut ~ y^3); damping= belongs to Smagorinsky")
 
     def check(self, gdim: int):
         if gdim != 3:
@@ -110,7 +230,7 @@ class _LawModel(_KernelModel):
     base_viscosity = None
     params = ()
 
-    def evaluate(self, solver, nut: torch.Tensor):
+    def evaluate(self, solver, nut: torch.Tensor, nu=None):
         Vi = solver._Vi[0][0]
         import ctypes as C
 
@@ -228,7 +348,7 @@ class CellViscosity:
         v = torch.from_numpy(self.values(solver._mesh)).to(solver._mesh.device)
         self._kernel_order = v[Vi.local_cells.to(torch.int64)].contiguous()
 
-    def evaluate(self, solver, nut: torch.Tensor):
+    def evaluate(self, solver, nut: torch.Tensor, nu=None):
         nut.copy_(self._kernel_order)
 
     def __repr__(self):
@@ -252,5 +372,7 @@ def check_model(model, mesh, rotational: bool, scalars) -> None:
         raise NotImplementedError("viscosity_model on a mesh partition (comm.size > 1): the per-cell viscosity is built for "
                                   "one GPU")
     model.check(mesh.geometry.dim)
+    if getattr(model, "damping", None) is not None:
+        model.check_mesh(mesh)  # an empty wall selection fails here
     if isinstance(model, CellViscosity):
         model.values(mesh)  # a callable or an array of the wrong length / sign fails here, not in the first step
