@@ -833,6 +833,18 @@ int ox_walldist_query(const ox_walldist *wd, int64_t n_points, const double *x, 
  * fixed order of sums: two runs give the same bits. */
 int ox_scalar_rows(const ox_sell *A, const ox_sell *M, const ox_sell *K, const ox_sell *Ac, double s, double dt, int ncomp,
                    const double *c1, const double *b0, double *b, double *a_c1, void *stream);
+/* The same system on a solver with a per-cell viscosity nut (ox_first_args.nut; ox_assemble.hip):
+ * there A = M/dt + C/2 + nu K/2 + K_t/2 with K_t = sum_c nut[c] K_c, which is stored nowhere.  ONE launch set in the shapes
+ * of ox_assemble_first (row_blocks as there) forms the rows of K_t once more in LDS -- the stiffness contraction alone, no
+ * u_ab gathers, no convection turns -- and streams the slices as ox_scalar_rows does:
+ *   A_c = A + s K + t K_t     per entry v = fma(t, kt, fma(s, k, a));   s = (kappa - nu)/2,  t = (1/Sc_t - 1)/2
+ *   b, a_c1 as for ox_scalar_rows (a_c1 bit-identical to ox_spmv(Ac, c1)).
+ * nut: device [n_cells] in kernel cell order, read-only (the array the last ox_assemble_first read).  cells / space: those
+ * of ox_assemble_first.  nut == 0 everywhere gives the bits of ox_scalar_rows.  No atomics to global memory, fixed order. */
+int ox_scalar_rows_cellvisc(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
+                            const ox_sell *K, const ox_sell *Ac, const double *nut, double s, double t, double dt,
+                            int ncomp, const double *c1, const double *b0, double *b, double *a_c1, int row_blocks,
+                            void *stream);
 
 /* ---- Scalars that drive the flow, scalar fluxes through walls (ox_scalar.hip) ------------------
  * Boussinesq force of 1..OX_MAXC coupled scalars onto the interleaved (n, gdim) block b (b_first of the velocity step), in
@@ -860,6 +872,11 @@ int ox_buoyancy_rows(const ox_sell *M, int gdim, int n_terms, const ox_buoy_term
 int ox_scalar_flux(int degree, const ox_cells *cells, const int32_t *cell_dofs, int64_t n_facets, const int32_t *facet_rec,
                    const double *c, int nc, int col, double kappa, double weight, double *q, double *fq, double *cbar,
                    double *acc_q, void *stream);
+/* The same with a per-cell diffusivity: q[i] = -(kappa + nut[cell] inv_sct) n . gbar, one fused multiply-add for the
+ * coefficient.  nut: device [n_cells] in kernel cell order (read-only); inv_sct = 1 / Sc_t >= 0 (0: no turbulent part). */
+int ox_scalar_flux_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, int64_t n_facets,
+                         const int32_t *facet_rec, const double *c, int nc, int col, double kappa, const double *nut,
+                         double inv_sct, double weight, double *q, double *fq, double *cbar, double *acc_q, void *stream);
 
 /* ---- Wall shear stress, traction and boundary forces on exterior facets (ox_wall.hip) ----------
  * Facet i -- the caller passes the facets SORTED by tag -- belongs to the cell at kernel position facet_rec[2 i] and lies

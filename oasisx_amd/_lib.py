@@ -271,6 +271,7 @@ class ox_buoy_term(C.Structure):
 
 
 PROF_TAG_BUOYANCY_ROWS = 190  # OX_TAG_BUOYANCY_ROWS of csrc/ox_kernels.h (ox_profile_get: key = 2 x terms + dictionary)
+PROF_TAG_SCALAR_ROWS_CELLVISC = 192  # OX_TAG_SCALAR_ROWS_CELLVISC (ox_profile_get: key = columns)
 
 _P = C.c_void_p
 _I = C.c_int
@@ -372,8 +373,11 @@ SIGNATURES = {
     "ox_walldist_query": (_I, [_P, _L, _P, C.POINTER(_D), _I, _P, _P, _P]),
     "ox_scalar_rows": (_I, [C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), C.POINTER(ox_sell), _D, _D, _I,
                             _P, _P, _P, _P, _P]),
+    "ox_scalar_rows_cellvisc": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), C.POINTER(ox_sell),
+                                     C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _D, _D, _D, _I, _P, _P, _P, _P, _I, _P]),
     "ox_buoyancy_rows": (_I, [C.POINTER(ox_sell), _I, _I, C.POINTER(ox_buoy_term), _P, _P]),
     "ox_scalar_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
+    "ox_scalar_flux_cells": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _P, _D, _D, _P, _P, _P, _P, _P]),
     "ox_wall_stress": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _L, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
     "ox_wall_forces": (_I, [_I, _I, _P, _P, _D, _P, _L, _L, _P]),
     "ox_outlet_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P]),

@@ -810,6 +810,318 @@ extern "C" int ox_assemble_first(const ox_cells *cells, const ox_space_info *spa
 }
 
 // ---------------------------------------------------------------------------------------
+// Scalars under a per-cell viscosity.  With a viscosity model the velocity matrix holds
+// A = M/dt + C/2 + nu K/2 + K_t/2, K_t = sum_c nut_c K_c, and K_t is stored nowhere.  A scalar with molecular diffusivity
+// kappa and turbulent Schmidt number Sc_t needs
+//   A_c = A + s K + t K_t,   s = (kappa - nu)/2,   t = (1/Sc_t - 1)/2
+// so the rows of K_t are formed once more -- the launch shapes and the StiffTab contraction of the NUT branch of
+// assemble_slice, WITHOUT its u_ab gathers, cell-dof loads and ND convection turns -- into the wave-private LDS
+// accumulator, and the epilogue is the stream of k_scalar_rows (csrc/ox_scalar.hip) with one more operand from LDS:
+//   v = fma(t, kt, fma(s, k, a));   sa, sm in the stored entry order with the operations of k_spmv, from 0.
+// P3 tetrahedra: the quadrature form weighted by nut_c (the NUT lines of the QUAD branch: rolled loop over the 70 points,
+// d(phi_j) through wave-uniform loads of QT33), nothing staged in LDS.  No atomics to global memory, fixed order.
+// ---------------------------------------------------------------------------------------
+struct ScalarVisArgs {
+  const double *Mv, *Kv, *nut, *c1, *b0;
+  double *Acv, *b, *a_c1;
+  double s, t, two_idt;
+  const uint8_t *Mc, *Kc;
+  const double *Md, *Kd;
+  int nMd, nKd;
+};
+
+template <int GDIM, int DEG, int PW, int NC, bool DICT>
+__device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, const ox_adj &adj,
+                                                      const uint8_t *__restrict__ adj_pos, const ox_sell &A,
+                                                      const ScalarVisArgs &F, const int slice, double *acc, const int lane,
+                                                      const double *tst, const double *dM, const double *dK) {
+  using E = Elem<GDIM, DEG>;
+  constexpr int ND = E::ND, GS = E::GS;
+  constexpr bool QUAD = OX_CONV_BY_QUADRATURE<GDIM, DEG>;
+  constexpr int NCB = QUAD ? 1 : COMBOS<GDIM, DEG>.n;
+  constexpr int SS = NCB * (GDIM + 1) + 2;
+  const int64_t base = A.slice_ptr[slice];
+  const int width = (int)((A.slice_ptr[slice + 1] - base) >> 6);
+  for (int k = 0; k < width; ++k) acc[k * 64 + lane] = 0.0;
+  const int64_t abase = adj.adj_ptr[slice];
+  const int T = (int)((adj.adj_ptr[slice + 1] - abase) >> 6);
+  for (int t0 = 0; t0 < T; ++t0) {
+    const int64_t pidx = abase + (int64_t)t0 * 64 + lane;
+    int e = adj.adj_cell[pidx];
+    const bool ok = e >= 0;
+    if (!ok) e = 0;  // loads stay unconditional (cell 0), the result is not accumulated
+    const int i = adj.adj_loc[pidx];
+    uint8_t pos[PW];
+    if constexpr (PW == 32) {
+      *reinterpret_cast<uint4 *>(pos) = *reinterpret_cast<const uint4 *>(adj_pos + pidx * 32);
+      *reinterpret_cast<uint4 *>(pos + 16) = *reinterpret_cast<const uint4 *>(adj_pos + pidx * 32 + 16);
+    } else if constexpr (PW == 16) {
+      *reinterpret_cast<uint4 *>(pos) = *reinterpret_cast<const uint4 *>(adj_pos + pidx * 16);
+    } else if constexpr (PW == 8) {
+      *reinterpret_cast<uint2 *>(pos) = *reinterpret_cast<const uint2 *>(adj_pos + pidx * 8);
+    } else {
+      *reinterpret_cast<uint32_t *>(pos) = *reinterpret_cast<const uint32_t *>(adj_pos + pidx * 4);
+    }
+    const double nutv = F.nut[e];
+    double G[GDIM + 1][GDIM], adet;
+    ox_load_geom<GDIM>(cells.geom + (size_t)e * GS, G, adet);
+    double c[ND];
+#pragma unroll
+    for (int j = 0; j < ND; ++j) c[j] = 0.0;
+    if constexpr (QUAD) {
+      // nut K_e[i][j] / |J| = nut sum_q w_q grad(phi_i) . grad(phi_j) (the lambda_0 column of the tabulation is zero)
+      const auto &R = rt<GDIM, DEG>();
+      for (int q = 0; q < E::NQ; ++q) {
+        double gi[GDIM];
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) {
+          gi[d] = 0.0;
+#pragma unroll
+          for (int b = 1; b <= GDIM; ++b) gi[d] = fma(R.dphi[i][q][b], G[b][d], gi[d]);
+        }
+        const double wn = QW33.w[q] * nutv;
+        double sb[GDIM];
+#pragma unroll
+        for (int b = 1; b <= GDIM; ++b) {
+          double h = 0.0;
+#pragma unroll
+          for (int d = 0; d < GDIM; ++d) h = fma(G[b][d], gi[d], h);
+          sb[b - 1] = wn * h;
+        }
+#pragma unroll
+        for (int j = 0; j < ND; ++j) {
+#pragma unroll
+          for (int b = 0; b < GDIM; ++b) c[j] = fma(QT33.dphi[q][j][b], sb[b], c[j]);
+        }
+      }
+    } else {
+      // nut K_e[i][j] / |J| = sum_(a, b) S[i][a][(j, b)] (nut G[a] . G[b]) (StiffTab): GDIM + 1 turns over NCB accumulators
+      constexpr auto CB = COMBOS<GDIM, DEG>;
+      const double *__restrict__ si = tst + i * SS;
+      double gg[GDIM + 1][GDIM + 1];
+#pragma unroll
+      for (int a = 0; a <= GDIM; ++a)
+#pragma unroll
+        for (int b = a; b <= GDIM; ++b) {
+          double v = 0.0;
+#pragma unroll
+          for (int d = 0; d < GDIM; ++d) v = fma(G[a][d], G[b][d], v);
+          gg[a][b] = gg[b][a] = nutv * v;
+        }
+      double cm[NCB];
+#pragma unroll
+      for (int m = 0; m < NCB; ++m) cm[m] = 0.0;
+#pragma unroll
+      for (int a = 0; a <= GDIM; ++a)
+#pragma unroll
+        for (int m = 0; m < NCB; ++m) cm[m] = fma(si[a * NCB + m], gg[a][CB.b[m]], cm[m]);
+#pragma unroll
+      for (int m = 0; m < NCB; ++m) c[CB.j[m]] += cm[m];
+    }
+    if (ok) {
+#pragma unroll
+      for (int j = 0; j < ND; ++j)  // the slot is private to this lane (LDS, wave scope: no atomic reaches global memory)
+        __hip_atomic_fetch_add(&acc[(int)pos[j] * 64 + lane], adet * c[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+  }
+  // epilogue: the stream of k_scalar_rows, kt from the accumulator
+  typedef double v2d __attribute__((ext_vector_type(2)));
+  typedef int v2i __attribute__((ext_vector_type(2)));
+  const int64_t row = (int64_t)slice * 64 + lane;
+  const int npair = width >> 1;
+  const v2d *__restrict__ av = reinterpret_cast<const v2d *>(A.vals + base) + lane;
+  const v2d *__restrict__ mv = reinterpret_cast<const v2d *>(F.Mv + base) + lane;
+  const v2d *__restrict__ kv = reinterpret_cast<const v2d *>(F.Kv + base) + lane;
+  const v2i *__restrict__ cp = reinterpret_cast<const v2i *>(A.cols + base) + lane;
+  v2d *__restrict__ ov = reinterpret_cast<v2d *>(F.Acv + base) + lane;
+  const unsigned short *__restrict__ mc = DICT ? reinterpret_cast<const unsigned short *>(F.Mc + base) + lane : nullptr;
+  const unsigned short *__restrict__ kc = DICT ? reinterpret_cast<const unsigned short *>(F.Kc + base) + lane : nullptr;
+  const double s = F.s, tt = F.t;
+  double sa[NC], sm[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) sa[c] = sm[c] = 0.0;
+  constexpr int EU = 4;  // entry pairs per turn: streams -> c_1 gathers -> arithmetic in the stored order -> stores
+  for (int k0 = 0; k0 < npair; k0 += EU) {
+    v2d a[EU], m[EU], kk[EU];
+    v2i col[EU];
+#pragma unroll
+    for (int q = 0; q < EU; ++q) {
+      const int k = min(k0 + q, npair - 1);  // unconditional loads inside the slice; the surplus is not used
+      a[q] = __builtin_nontemporal_load(av + (size_t)k * 64);
+      if constexpr (DICT) {
+        const unsigned cm = __builtin_nontemporal_load(mc + (size_t)k * 64), ck = __builtin_nontemporal_load(kc + (size_t)k * 64);
+        m[q].x = dM[cm & 0xff], m[q].y = dM[cm >> 8];
+        kk[q].x = dK[ck & 0xff], kk[q].y = dK[ck >> 8];
+      } else {
+        m[q] = __builtin_nontemporal_load(mv + (size_t)k * 64);
+        kk[q] = __builtin_nontemporal_load(kv + (size_t)k * 64);
+      }
+      col[q] = __builtin_nontemporal_load(cp + (size_t)k * 64);
+    }
+    double x0[EU][NC], x1[EU][NC];
+#pragma unroll
+    for (int q = 0; q < EU; ++q)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        x0[q][c] = F.c1[(size_t)col[q].x * NC + c];
+        x1[q][c] = F.c1[(size_t)col[q].y * NC + c];
+      }
+#pragma unroll
+    for (int q = 0; q < EU; ++q) {
+      const int k = k0 + q;
+      if (k < npair) {
+        v2d v;
+        v.x = fma(tt, acc[(2 * k) * 64 + lane], fma(s, kk[q].x, a[q].x));
+        v.y = fma(tt, acc[(2 * k + 1) * 64 + lane], fma(s, kk[q].y, a[q].y));
+        __builtin_nontemporal_store(v, ov + (size_t)k * 64);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sa[c] = fma(v.x, x0[q][c], sa[c]);  // entry order and operations of k_spmv
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sa[c] = fma(v.y, x1[q][c], sa[c]);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sm[c] = fma(m[q].y, x1[q][c], fma(m[q].x, x0[q][c], sm[c]));
+      }
+    }
+  }
+  if (row < A.n_rows) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) F.b[row * NC + c] = fma(F.two_idt, sm[c], -sa[c]) + F.b0[row * NC + c];
+    if (F.a_c1) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) F.a_c1[row * NC + c] = sa[c];
+    }
+  }
+}
+
+template <int GDIM, int DEG, int PW, int NC, bool DICT, bool BLK>
+__global__ __launch_bounds__(BLK ? 512 : 256) void k_scalar_rows_cellvisc(ox_cells cells, ox_adj adj,
+                                                                          const uint8_t *__restrict__ adj_pos, ox_sell A,
+                                                                          ScalarVisArgs F,
+                                                                          const int32_t *__restrict__ slice_list, int n_list,
+                                                                          int bin_width) {
+  using E = Elem<GDIM, DEG>;
+  constexpr int ND = E::ND;
+  constexpr bool QUAD = OX_CONV_BY_QUADRATURE<GDIM, DEG>;
+  constexpr int NCB = QUAD ? 1 : COMBOS<GDIM, DEG>.n;
+  constexpr int SS = NCB * (GDIM + 1) + 2;  // doubles per row dof of the stiffness tensor, padded as in k_assemble_rows
+  extern __shared__ double acc_all[];       // [waves][bin_width][64]  (BLK: the row block's slices back to back)
+  __shared__ double dM[DICT ? 256 : 1], dK[DICT ? 256 : 1];
+  __shared__ __attribute__((aligned(16))) double tst[QUAD ? 2 : ND * SS];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nthr = blockDim.x, nwave = blockDim.x >> 6;
+  if constexpr (DICT) {
+    for (int i = threadIdx.x; i < F.nMd; i += nthr) dM[i] = F.Md[i];
+    for (int i = threadIdx.x; i < F.nKd; i += nthr) dK[i] = F.Kd[i];
+  }
+  if constexpr (!QUAD) {
+    const double *src = &st_tab<GDIM, DEG>().t[0][0][0];
+    constexpr int PER_I = (GDIM + 1) * NCB;
+    for (int idx = threadIdx.x; idx < ND * PER_I; idx += nthr) {
+      const int i = idx / PER_I;
+      tst[i * SS + (idx - i * PER_I)] = src[idx];
+    }
+  }
+  if constexpr (DICT || !QUAD) __syncthreads();
+  if constexpr (BLK) {
+    const int b = ox_xcd_remap(blockIdx.x, gridDim.x);  // (gridDim.x == n_list)
+    const int s0 = slice_list[b];
+    const int slice = s0 + wave;
+    if (slice >= slice_list[b + 1]) return;
+    scalar_cellvisc_slice<GDIM, DEG, PW, NC, DICT>(cells, adj, adj_pos, A, F, slice,
+                                                   acc_all + (A.slice_ptr[slice] - A.slice_ptr[s0]), lane, tst, dM, dK);
+  } else {
+    const int li = ox_xcd_remap(blockIdx.x, gridDim.x) * nwave + wave;
+    if (li >= n_list) return;
+    scalar_cellvisc_slice<GDIM, DEG, PW, NC, DICT>(cells, adj, adj_pos, A, F, slice_list[li],
+                                                   acc_all + (size_t)wave * bin_width * 64, lane, tst, dM, dK);
+  }
+}
+
+template <int GDIM, int DEG, int PW, int NC, bool DICT>
+static int launch_scalar_cellvisc_t(const RowLaunch &L, const ox_sell *A, const ScalarVisArgs &F) {
+  const ox_space_info &V = *L.V;
+  const ox_pattern_info &P = V.pattern;
+  auto go = [&](auto kern, unsigned grid, unsigned block, size_t lds, const int32_t *list, int n_list, int width) -> int {
+    if (lds > 32 * 1024)
+      OX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, L.st, *L.cells, V.adj, V.adj_pos, *A, F, list, n_list, width);
+    OX_LAUNCH_CHECK();
+    return 0;
+  };
+  if (!L.blocks) {
+    for (int b = 0; b < P.n_bins; ++b) {
+      const int64_t cnt = P.bin_ptr_host[b + 1] - P.bin_ptr_host[b];
+      if (cnt <= 0) continue;
+      const int width = P.bin_width_host[b];
+      constexpr size_t CAP = OX_ROW_BLOCK_LDS;  // (as the NUT launches of ox_assemble_first: tables of up to 11 KB beside it)
+      int nw = 4;
+      while (nw > 1 && (size_t)nw * width * 64 * sizeof(double) > CAP) nw >>= 1;
+      const size_t lds = (size_t)nw * width * 64 * sizeof(double);
+      if (lds > CAP) OX_FAIL("ox_scalar_rows_cellvisc: row width %d needs %zu B of LDS", width, lds);
+      const int rc = go(k_scalar_rows_cellvisc<GDIM, DEG, PW, NC, DICT, false>, (unsigned)((cnt + nw - 1) / nw), 64u * nw, lds,
+                        P.bin_slices + P.bin_ptr_host[b], (int)cnt, width);
+      if (rc) return rc;
+    }
+    return 0;
+  }
+  const size_t lds = (size_t)P.row_blk_entries * sizeof(double);
+  if (lds > OX_ROW_BLOCK_LDS)
+    OX_FAIL("ox_scalar_rows_cellvisc: a row block needs %zu B of LDS (limit %d)", lds, OX_ROW_BLOCK_LDS);
+  return go(k_scalar_rows_cellvisc<GDIM, DEG, PW, NC, DICT, true>, (unsigned)P.n_row_blocks, 512u, lds, P.row_blk_ptr,
+            (int)P.n_row_blocks, 0);
+}
+
+template <int GDIM, int DEG, int PW>
+static int launch_scalar_cellvisc(const RowLaunch &L, const ox_sell *A, const ScalarVisArgs &F, int ncomp) {
+  const bool dict = F.Mc && F.Kc && F.Md && F.Kd && F.nMd >= 1 && F.nMd <= 256 && F.nKd >= 1 && F.nKd <= 256;
+#define OX_SCV_NC(N)                                                                        \
+  case N:                                                                                   \
+    return dict ? launch_scalar_cellvisc_t<GDIM, DEG, PW, N, true>(L, A, F)                 \
+                : launch_scalar_cellvisc_t<GDIM, DEG, PW, N, false>(L, A, F);
+  switch (ncomp) {
+    OX_SCV_NC(1)
+    OX_SCV_NC(2)
+    default:
+      OX_SCV_NC(3)
+  }
+#undef OX_SCV_NC
+}
+
+extern "C" int ox_scalar_rows_cellvisc(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
+                                       const ox_sell *K, const ox_sell *Ac, const double *nut, double s, double t, double dt,
+                                       int ncomp, const double *c1, const double *b0, double *b, double *a_c1, int row_blocks,
+                                       void *stream) {
+  if (!cells || !cells->geom || !space || !A || !M || !K || !Ac || !A->vals || !M->vals || !K->vals || !Ac->vals || !nut ||
+      !c1 || !b0 || !b)
+    OX_FAIL("ox_scalar_rows_cellvisc: null argument");
+  if (row_launch_check("ox_scalar_rows_cellvisc", space, row_blocks)) return -1;
+  if (M->slice_ptr != A->slice_ptr || K->slice_ptr != A->slice_ptr || Ac->slice_ptr != A->slice_ptr)
+    OX_FAIL("ox_scalar_rows_cellvisc: A, M, K and A_c must share one sparsity pattern");
+  if (Ac->vals == A->vals || Ac->vals == M->vals || Ac->vals == K->vals)
+    OX_FAIL("ox_scalar_rows_cellvisc: A_c needs a value array of its own");
+  if (!(dt > 0.0)) OX_FAIL("ox_scalar_rows_cellvisc: dt=%g", dt);
+  if (ncomp < 1 || ncomp > OX_MAXC) OX_FAIL("ox_scalar_rows_cellvisc: ncomp=%d", ncomp);
+  if (A->n_slices <= 0) return 0;
+  const RowLaunch L{cells, space, row_blocks == 1, ox_stream(stream)};
+  const ScalarVisArgs F{M->vals, K->vals, nut, c1, b0, Ac->vals, b, a_c1, s, t, 2.0 / dt,
+                        M->vcode, K->vcode, M->vdict, K->vdict, M->n_dict, K->n_dict};
+  const int g = cells->gdim, degree = space->degree, pw = space->pw;
+  int rc = -1;
+  bool found = false;
+  if (ox_prof_on) ox_prof_start(OX_TAG_SCALAR_ROWS_CELLVISC, L.st, ncomp);
+#define OX_SCV_CASE(GD, DG, P)                                 \
+  if (!found && g == GD && degree == DG && pw == P) {          \
+    found = true;                                              \
+    rc = launch_scalar_cellvisc<GD, DG, P>(L, A, F, ncomp);    \
+  }
+  OX_SCV_CASE(2, 1, 4) OX_SCV_CASE(2, 2, 8) OX_SCV_CASE(3, 1, 4) OX_SCV_CASE(3, 2, 16) OX_SCV_CASE(2, 3, 16) OX_SCV_CASE(3, 3, 32)
+#undef OX_SCV_CASE
+  if (ox_prof_on) ox_prof_stop(L.st);
+  if (!found) OX_FAIL("ox_scalar_rows_cellvisc: unsupported gdim=%d degree=%d (adj_pos stride %d)", g, degree, pw);
+  return rc;
+}
+
+// ---------------------------------------------------------------------------------------
 // Vectors.  lane = row, 4 slices per 256-thread block, no LDS.
 // ---------------------------------------------------------------------------------------
 #define OX_ADJ_WALK_BEGIN                                                       \

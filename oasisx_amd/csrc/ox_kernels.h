@@ -149,7 +149,8 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_OUTLET_UPDATE 181   // ox_outlet_update (key = tags)
 #define OX_TAG_OUTLET_BACKFLOW 182 // ox_outlet_backflow (key = rows)
 #define OX_TAG_BUOYANCY_ROWS 190   // ox_buoyancy_rows (key = 2 x terms + 1 where M is read through its dictionary)
-#define OX_TAG_SCALAR_FLUX 191     // ox_scalar_flux (key = facets)
+#define OX_TAG_SCALAR_FLUX 191     // ox_scalar_flux, ox_scalar_flux_cells (key = facets)
+#define OX_TAG_SCALAR_ROWS_CELLVISC 192 // ox_scalar_rows_cellvisc (key = columns)
 extern bool ox_prof_on;
 void ox_prof_start(int tag, hipStream_t st, long long key = 0);
 void ox_prof_stop(hipStream_t st);

@@ -238,12 +238,15 @@ int launch_buoyancy(const ox_sell *M, int gdim, const ox_buoy_term *terms, doubl
 // weight > 0, the read-modify-write of the accumulator); gathered: the cell's dof list, geometry record and ND values of
 // column col of c.  The facet means of the basis and of its gradient are compile-time constants: identically-zero
 // entries cost nothing; the local facet selects one of GDIM + 1 instantiations of the contraction.
-template <int GDIM, int DEG>
+// CELLS (a solver with a viscosity model): the coefficient is kappa + nut[cell] inv_sct, one more
+// gathered double per facet; the other instantiation reads neither argument and keeps the code it had.
+template <int GDIM, int DEG, bool CELLS = false>
 __global__ __launch_bounds__(256) void k_scalar_flux(ox_cells cells, const int32_t *__restrict__ dofs, int64_t n_facets,
                                                      const int2 *__restrict__ rec, const double *__restrict__ c, int nc,
                                                      int col, double kappa, double weight, double *__restrict__ q,
                                                      double *__restrict__ fq, double *__restrict__ cbar,
-                                                     double *__restrict__ acc_q) {
+                                                     double *__restrict__ acc_q, const double *__restrict__ nut = nullptr,
+                                                     double inv_sct = 0.0) {
   constexpr int ND = ox_nd(GDIM, DEG);
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= n_facets) return;
@@ -284,7 +287,8 @@ __global__ __launch_bounds__(256) void k_scalar_flux(ox_cells cells, const int32
       for (int bb = 0; bb <= GDIM; ++bb) g = fma(tb[bb], G[bb][k], g);
       gn = fma(n[k], g, gn);
     }
-    qv = -kappa * gn;
+    if constexpr (CELLS) qv = -fma(nut[e], inv_sct, kappa) * gn;
+    else qv = -kappa * gn;
     fv = area * qv;
     cb = mean;
   }
@@ -359,4 +363,35 @@ extern "C" int ox_scalar_flux(int degree, const ox_cells *cells, const int32_t *
   OX_FOR_GDIM_DEG(OX_SCALAR_FLUX_CASE)
 #undef OX_SCALAR_FLUX_CASE
   OX_FAIL("ox_scalar_flux: unsupported gdim=%d, P%d", g, degree);
+}
+
+extern "C" int ox_scalar_flux_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, int64_t n_facets,
+                                    const int32_t *facet_rec, const double *c, int nc, int col, double kappa,
+                                    const double *nut, double inv_sct, double weight, double *q, double *fq, double *cbar,
+                                    double *acc_q, void *stream) {
+  if (!cells || !cells->geom || !cell_dofs || !facet_rec || !c || !q || !fq || !cbar || !nut)
+    OX_FAIL("ox_scalar_flux_cells: null argument");
+  if (nc < 1 || col < 0 || col >= nc) OX_FAIL("ox_scalar_flux_cells: column %d of %d", col, nc);
+  if (weight > 0.0 && !acc_q) OX_FAIL("ox_scalar_flux_cells: weight > 0 without an accumulator");
+  if (!(inv_sct >= 0.0) || inv_sct > 1.0e300) OX_FAIL("ox_scalar_flux_cells: inv_sct=%g", inv_sct);
+  if (!(weight >= 0.0)) OX_FAIL("ox_scalar_flux_cells: weight=%g", weight);
+  if (n_facets <= 0) return 0;
+  if (n_facets > (int64_t)0x7fffffff || cells->n_cells > (int64_t)0x7fffffff)
+    OX_FAIL("ox_scalar_flux_cells: %lld facets, %lld cells", (long long)n_facets, (long long)cells->n_cells);
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const unsigned nblk = (unsigned)((n_facets + 255) / 256);
+#define OX_SCALAR_FLUXC_CASE(GD, DG)                                                                                  \
+  if (g == GD && degree == DG) {                                                                                      \
+    if (ox_prof_on) ox_prof_start(OX_TAG_SCALAR_FLUX, st, n_facets);                                                  \
+    hipLaunchKernelGGL((k_scalar_flux<GD, DG, true>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, n_facets,      \
+                       reinterpret_cast<const int2 *>(facet_rec), c, nc, col, kappa, weight, q, fq, cbar, acc_q, nut, \
+                       inv_sct);                                                                                      \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                 \
+    OX_LAUNCH_CHECK();                                                                                                \
+    return 0;                                                                                                         \
+  }
+  OX_FOR_GDIM_DEG(OX_SCALAR_FLUXC_CASE)
+#undef OX_SCALAR_FLUXC_CASE
+  OX_FAIL("ox_scalar_flux_cells: unsupported gdim=%d, P%d", g, degree);
 }

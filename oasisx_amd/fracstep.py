@@ -111,7 +111,9 @@ class FractionalStep_AB_CN:
         viscosity_model: :class:`oasisx_amd.Smagorinsky`, :class:`oasisx_amd.Wale` or :class:`oasisx_amd.CellViscosity`:
             an additional viscosity per cell, ``div(nut grad u)``, evaluated per step from the extrapolated velocity and
             added by the fused assembly kernel (:mod:`oasisx_amd.viscosity`); ``None``: the constant-viscosity step,
-            unchanged.  One GPU only; not with ``rotational=True`` or ``scalars=``.  :class:`oasisx_amd.CarreauYasuda`,
+            unchanged.  One GPU only; not with ``rotational=True``.  With ``scalars=`` every scalar states its
+            ``turbulent_schmidt=``: its diffusivity is ``kappa + nut / Sc_t`` per cell (``scalar_diffusivity``; there is no
+            default, and with a law only ``inf`` is accepted: :mod:`oasisx_amd.scalar`).  :class:`oasisx_amd.CarreauYasuda`,
             :class:`oasisx_amd.Cross` and :class:`oasisx_amd.PowerLaw` are shear-dependent laws ``nu(gd)``: the step is run at
             ``nu = viscosity_model.base_viscosity`` and ``nut = nu(gd) - base_viscosity`` (``effective_viscosity()``)
         stress_form: ``"laplacian"`` (default): ``div(nut grad u)``, today's path; ``"full"``: ``div(nut (grad u + grad u^T))``,
@@ -548,6 +550,23 @@ class FractionalStep_AB_CN:
         out[self._Vi[0][0].local_cells.to(torch.int64)] = self._nut
         return out
 
+    def scalar_diffusivity(self, name: str, nu: float) -> torch.Tensor:
+        """``kappa + nut_c / Sc_t`` per cell of the scalar ``name`` with the ``nut`` of the last ``assemble_first``: a device
+        tensor ``(num_cells,)`` in the MESH's cell order, the scalar's counterpart of ``eddy_viscosity()``.  Evaluated as
+        ``kappa + eddy_viscosity() / Sc_t`` (one division, one addition per cell; ``Sc_t = inf`` and the laws: ``kappa``)."""
+        if self._viscosity_model is None:
+            raise RuntimeError("scalar_diffusivity: the solver was built without a viscosity_model (the scalar's "
+                               "diffusivity is the constant kappa)")
+        if name not in self._scalar_index:
+            raise KeyError(f"no scalar named {name!r} (have: {sorted(self._scalar_index)})")
+        g, j = self._scalar_index[name]
+        m = g.members[j]
+        kappa = m.kappa(nu)
+        nut = self.eddy_viscosity()
+        if not self._viscosity_model.diffuses_scalars:
+            return torch.full_like(nut, kappa)
+        return kappa + nut / m.turbulent_schmidt
+
     def effective_viscosity(self) -> torch.Tensor:
         """``base_viscosity + nut`` per cell of the last ``assemble_first`` -- the law's ``nu(gd)`` -- in the MESH's cell
         order.  Defined for the generalised-Newtonian laws (CarreauYasuda, Cross, PowerLaw)."""
@@ -682,7 +701,8 @@ class FractionalStep_AB_CN:
     @_phase
     def scalar_assemble(self, dt: float, nu: float):
         """Per scalar group: A_c = A + (kappa - nu)/2 K, b_c = (2/dt) M c_1 - A_c c_1 + b0_c and, for a solver with a nonzero
-        initial guess, A_c c_1 -- one pass over the values of the shared pattern (``ox_scalar_rows``); then the group's own
+        initial guess, A_c c_1 -- one pass over the values of the shared pattern (``ox_scalar_rows``; with a
+        ``viscosity_model`` and ``Sc_t != 1``: A_c = A + s K + t K_t, ``ox_scalar_rows_cellvisc``); then the group's own
         Dirichlet rows.  Runs INSIDE ``assemble_first``, between the fused kernel and the velocity's boundary rows:
         afterwards those rows of ``A`` are gone."""
         if not self._A_pre_bc:

@@ -11,7 +11,16 @@ Plain Galerkin.  ``C(u_ab)`` is what the velocity step assembles anyway:
 ``A_c = A + (kappa - nu)/2 K`` with the velocity matrix ``A`` before its boundary rows, one streaming pass over the
 values of the shared SELL-64 pattern (``ox_scalar_rows``, csrc/ox_scalar.hip) instead of a second element loop.
 
-Scalars with the same diffusivity specification and the same set of Dirichlet rows form a GROUP: one matrix, solved in
+On a solver with a ``viscosity_model`` ``A`` also holds ``K_t / 2``, ``K_t = sum_c nut_c K_c``, and a
+scalar with ``turbulent_schmidt=Sc_t`` has the diffusivity ``kappa + nut_c / Sc_t`` per cell::
+
+    A_c = A + s K + t K_t,    s = (kappa - nu)/2,    t = (1/Sc_t - 1)/2        (a law's nut does not diffuse: t = -1/2)
+
+``K_t`` is stored nowhere: ``ox_scalar_rows_cellvisc`` forms its rows once more in LDS (the stiffness contraction of the
+fused kernel without its convection turns and gathers) and streams the slices as ``ox_scalar_rows`` does.  ``Sc_t = 1``
+(``t = 0``) and a solver without a model run ``ox_scalar_rows``.
+
+Scalars with the same diffusivity specification (``turbulent_schmidt`` included) and the same set of Dirichlet rows form a GROUP: one matrix, solved in
 lock-step as the columns of one block solve (at most 3 columns; more open further groups).  One group costs one f64
 value array of the velocity pattern in device memory.
 
@@ -61,10 +70,14 @@ class ScalarTransport:
         extrapolate: ``True`` (default): the force is taken at the step's midpoint, ``c* = c_1 + 0.5 (c_1 - c_2)`` (second
             order; the group keeps a second time level ``c_2``, ``solver.scalar(name, level=2)``); ``False``: ``c* = c_1``,
             first order
+        turbulent_schmidt: ``Sc_t``, for a solver with a ``viscosity_model`` (there it must be given: there is no default):
+            a finite float > 0 -- the scalar's diffusivity is ``kappa + nut_c / Sc_t`` per cell -- or ``float("inf")``: no
+            turbulent diffusivity.  With a generalised-Newtonian law (whose ``nut`` belongs to the momentum alone) only
+            ``inf`` is accepted.  Without a ``viscosity_model`` it has no effect
     """
 
     def __init__(self, name, diffusivity=None, schmidt=None, bcs=(), source=0.0, initial=None, buoyancy=None,
-                 reference=0.0, extrapolate=True):
+                 reference=0.0, extrapolate=True, turbulent_schmidt=None):
         if not isinstance(name, str) or not name:
             raise ValueError("ScalarTransport: name must be a non-empty string")
         if (diffusivity is None) == (schmidt is None):
@@ -98,12 +111,52 @@ class ScalarTransport:
         if not np.isfinite(self.reference):
             raise ValueError(f"ScalarTransport {name!r}: reference = {self.reference}: a finite number is expected")
         self.extrapolate = bool(extrapolate)
+        if turbulent_schmidt is not None:
+            try:
+                turbulent_schmidt = float(turbulent_schmidt)
+            except (TypeError, ValueError):
+                raise ValueError(f"ScalarTransport {name!r}: turbulent_schmidt = {turbulent_schmidt!r}: a float > 0 or "
+                                 "float('inf') is expected") from None
+            if not turbulent_schmidt > 0.0:  # (NaN too)
+                raise ValueError(f"ScalarTransport {name!r}: turbulent_schmidt = {turbulent_schmidt}: a float > 0 or "
+                                 "float('inf') is expected")
+        self.turbulent_schmidt = turbulent_schmidt
+
+    def inverse_turbulent_schmidt(self) -> float:
+        """``1 / Sc_t``; 0 for ``inf`` (and where none was given)."""
+        return 0.0 if self.turbulent_schmidt is None else 1.0 / self.turbulent_schmidt
 
     def kappa(self, nu: float) -> float:
         return self.diffusivity if self.schmidt is None else float(nu) / self.schmidt
 
     def _spec(self):
-        return ("kappa", self.diffusivity) if self.schmidt is None else ("schmidt", self.schmidt)
+        spec = ("kappa", self.diffusivity) if self.schmidt is None else ("schmidt", self.schmidt)
+        return spec + (("turbulent_schmidt", self.turbulent_schmidt),)
+
+
+def check_turbulent_schmidt(model, scalars) -> None:
+    """The scope guard of ``viscosity_model=`` with ``scalars=`` (run by ``viscosity.check_model``, before the library is
+    loaded): every scalar states its turbulent Schmidt number, and with a model whose ``nut`` does not mix scalars
+    (``diffuses_scalars = False``: the generalised-Newtonian laws) that number is ``inf``."""
+    for s in scalars:
+        if not isinstance(s, ScalarTransport):
+            raise TypeError(f"scalars: a list of ScalarTransport (got {type(s).__name__})")
+        if s.turbulent_schmidt is None:
+            raise NotImplementedError(f"viscosity_model with scalars=: ScalarTransport {s.name!r} has no turbulent_schmidt=: "
+                                      "the turbulent diffusivity of a scalar is a modelling decision with no default here "
+                                      "(kappa + nut / Sc_t; float('inf') for none)")
+        if not model.diffuses_scalars and s.turbulent_schmidt != float("inf"):
+            raise ValueError(f"ScalarTransport {s.name!r}: turbulent_schmidt = {s.turbulent_schmidt} with {model!r}: the "
+                             "law's nut = nu(gd) - base_viscosity is a property of the fluid's momentum and does not "
+                             "diffuse scalars; turbulent_schmidt must be float('inf')")
+
+
+def turbulent_factor(solver, member) -> float:
+    """``t`` of ``A_c = A + s K + t K_t``: ``(1/Sc_t - 1)/2`` where the model's ``nut`` diffuses scalars, ``-1/2`` (``K_t``
+    taken out again) where it does not."""
+    if not solver._viscosity_model.diffuses_scalars:
+        return -0.5
+    return 0.5 * (member.inverse_turbulent_schmidt() - 1.0)
 
 
 class ScalarGroup:
@@ -233,9 +286,19 @@ def assemble(solver, group: ScalarGroup, dt: float, nu: float):
     lib, st = solver._lib, _lib.current_stream()
     kappa = group.members[0].kappa(nu)
     au = group.AC1.ptr() if group.wants_ax0() else None
-    _lib.check(lib.ox_scalar_rows(solver._A.ref(), solver._M.ref(), solver._K.ref(), group.Ac.ref(),
-                                  0.5 * (kappa - float(nu)), float(dt), group.nc, group.C1.rptr(), group.B0.rptr(),
-                                  group.B.ptr(), au, st), "ox_scalar_rows")
+    t = 0.0 if solver._viscosity_model is None else turbulent_factor(solver, group.members[0])
+    if t == 0.0:  # no model, or Sc_t = 1: the scalar's operator differs from A by a multiple of K alone
+        _lib.check(lib.ox_scalar_rows(solver._A.ref(), solver._M.ref(), solver._K.ref(), group.Ac.ref(),
+                                      0.5 * (kappa - float(nu)), float(dt), group.nc, group.C1.rptr(), group.B0.rptr(),
+                                      group.B.ptr(), au, st), "ox_scalar_rows")
+    else:  # A_c = A + s K + t K_t: the rows of K_t = sum_c nut_c K_c once more, in LDS
+        Vi = solver._Vi[0][0]
+        _lib.check(lib.ox_scalar_rows_cellvisc(C.byref(solver._cells), C.byref(Vi.assembly_info()), solver._A.ref(),
+                                               solver._M.ref(), solver._K.ref(), group.Ac.ref(), _lib.ptr(solver._nut),
+                                               0.5 * (kappa - float(nu)), t, float(dt), group.nc, group.C1.rptr(),
+                                               group.B0.rptr(), group.B.ptr(), au,
+                                               int(solver._row_blocks and Vi.pattern.n_row_blocks > 0), st),
+                   "ox_scalar_rows_cellvisc")
     group.Ac.version += 1
     if group.rows_dev.shape[0] > 0:  # identity rows; (A_c c_1)[row] = c_1[row] there, in the same launch
         group.Ac.zero_rows(group.rows_dev, 1.0, au, group.C1.rptr() if au is not None else None, group.nc)
@@ -263,7 +326,8 @@ def solve(solver, group: ScalarGroup):
 
 
 class ScalarFlux:
-    """Diffusive flux ``q_f = -kappa n . mean_f(grad c)`` of one scalar of a ``FractionalStep_AB_CN`` solver through
+    """Diffusive flux ``q_f = -kappa n . mean_f(grad c)`` (on a solver with a ``viscosity_model``: ``kappa + nut_c / Sc_t``
+    of the facet's cell, with the ``nut`` of the last ``assemble_first``; ``ox_scalar_flux_cells``) of one scalar of a ``FractionalStep_AB_CN`` solver through
     exterior facets, evaluated on the device beside the time step: the Nusselt / Sherwood number of a wall is
     ``totals()`` over the wall's area and the reference flux.  ``n`` points outward: a positive flux leaves the domain.
 
@@ -342,7 +406,14 @@ class ScalarFlux:
         Vi = S._Vi[0][0]
         lib, st = _lib.load(), _lib.current_stream()
         kappa = g.members[self._col].kappa(nu)
-        if self.n_facets:
+        model = S._viscosity_model
+        if self.n_facets and model is not None:  # kappa + nut_c / Sc_t of the facet's cell, nut of the last assemble_first
+            inv = g.members[self._col].inverse_turbulent_schmidt() if model.diffuses_scalars else 0.0
+            _lib.check(lib.ox_scalar_flux_cells(Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), self.n_facets,
+                                                _lib.ptr(self._rec), g.C.rptr(), g.nc, self._col, float(kappa),
+                                                _lib.ptr(S._nut), inv, dt, _lib.ptr(self._q), _lib.ptr(self._fq),
+                                                _lib.ptr(self._cbar), _lib.ptr(self._acc), st), "ox_scalar_flux_cells")
+        elif self.n_facets:
             _lib.check(lib.ox_scalar_flux(Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), self.n_facets,
                                           _lib.ptr(self._rec), g.C.rptr(), g.nc, self._col, float(kappa), dt, _lib.ptr(self._q),
                                           _lib.ptr(self._fq), _lib.ptr(self._cbar), _lib.ptr(self._acc), st), "ox_scalar_flux")

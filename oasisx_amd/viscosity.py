@@ -50,6 +50,8 @@ class _KernelModel:
     """A model whose ``nut`` is a function of ``grad u_ab`` at the cell centroid: evaluated by ``ox_eddy_viscosity``."""
 
     model_id = None
+    # nut is a turbulent viscosity that mixes scalars too: kappa_eff = kappa + nut / Sc_t (scalar.py, DESIGN.md section 25)
+    diffuses_scalars = True
 
     def check(self, gdim: int):
         pass
@@ -229,6 +231,8 @@ class _LawModel(_KernelModel):
 
     base_viscosity = None
     params = ()
+    # nut = nu(gd) - base_viscosity is a property of the fluid's momentum, not a mixing of scalars
+    diffuses_scalars = False
 
     def evaluate(self, solver, nut: torch.Tensor, nu=None):
         Vi = solver._Vi[0][0]
@@ -304,6 +308,7 @@ class CellViscosity:
     """
 
     model_id = None
+    diffuses_scalars = True
 
     def __init__(self, value):
         if callable(value):
@@ -365,8 +370,9 @@ def check_model(model, mesh, rotational: bool, scalars) -> None:
         raise NotImplementedError("viscosity_model with rotational=True: the xi nu div(u) term of the rotational pressure "
                                   "update is derived for a constant viscosity")
     if scalars:
-        raise NotImplementedError("viscosity_model with scalars=: the turbulent diffusivity of a scalar (a turbulent Schmidt "
-                                  "number) is a modelling decision that has not been made here")
+        from .scalar import check_turbulent_schmidt
+
+        check_turbulent_schmidt(model, scalars)
     comm = getattr(mesh, "comm", None)
     if comm is not None and getattr(comm, "size", 1) > 1:
         raise NotImplementedError("viscosity_model on a mesh partition (comm.size > 1): the per-cell viscosity is built for "
