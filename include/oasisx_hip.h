@@ -512,6 +512,47 @@ typedef struct {
 } ox_vandriest;
 int ox_eddy_viscosity_damped(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
                              double coefficient, const ox_vandriest *vd, double *nut, void *stream);
+/* ---- the dynamic Smagorinsky model: the Germano-Lilly procedure ----
+ * NS = gdim (gdim + 1) / 2.  All arrays are device arrays in kernel cell order / vertex-class order; every launch has one
+ * summation order and no atomics, so equal inputs give equal bits.  Counts must fit int32 (indices are int32).
+ * The test filter of a per-cell q: q_v = sum_{c in patch(v)} |c| q_c / sum |c| (the cells of a vertex in ascending order),
+ * q^_c = the mean of q_v over the cell's gdim + 1 vertices.  ptr [n_vertices + 1], idx [ptr[n_vertices]]: the vertex ->
+ * cell CSR; cell_verts [n_cells][gdim + 1]: the vertex classes of a cell.  An index out of range writes NaN and reads
+ * nothing.
+ *   ox_dynamic_cells:    rec[c][gdim + NS + 2] = {u at the centroid, upper triangle of S = sym(grad uab) row by row,
+ *                        D s, |c|}, D = |c|^(2/gdim), s = sqrt(2 S:S); arguments as ox_eddy_viscosity
+ *   ox_dynamic_vertices: mom[v][gdim + 3 NS] = {u, u u^T, S, D s S} filtered to the vertex (upper triangles)
+ *   ox_dynamic_products: lm[c][2] = {Ld:M, M:M}, L = (u u^T)^ - u^ u^^T, Ld = L - tr L / gdim I,
+ *                        M = filter_ratio^2 D |S^| S^ - (D s S)^, |S^| = sqrt(2 S^:S^); filter_ratio > 1
+ *   ox_dynamic_bin_sums: partials[chunk][2] = sum over the chunk's cells of vol[c vol_stride] {lm[c][0], lm[c][1]}; order,
+ *                        chunks, n_chunks: the plan of ox_profile_cells
+ *   ox_dynamic_bin_coefficients: bins[b][4] = {sum LM, sum MM, -(1/2) LM / MM, that clipped to [0, cs2_max]}; the clipped
+ *                        value is 0 where sum MM is not positive; a NaN stays a NaN.  One wave per bin.
+ *   ox_patch_filter_vertices / ox_patch_filter_cells: the two halves of the filter for q [n_cells][k], k = 1 or 2;
+ *                        n_idx = ptr[n_vertices]
+ *   ox_dynamic_clip:     cs2[i] = the clipped -(1/2) pairs[i][0] / pairs[i][1], as above
+ *   ox_eddy_viscosity_cellcoef: nut[c] = C D s (the Smagorinsky branch of ox_eddy_viscosity), C = cs2[k cs2_stride] with
+ *                        k = cell_bin[c] (cell_bin given; k < 0: C = 0; k >= n_coef: NaN) or k = c (cell_bin NULL,
+ *                        n_coef = n_cells) */
+int ox_dynamic_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab, double *rec,
+                     void *stream);
+int ox_dynamic_vertices(int gdim, int64_t n_vertices, const int32_t *ptr, const int32_t *idx, int64_t n_cells,
+                        const double *rec, double *mom, void *stream);
+int ox_dynamic_products(int gdim, int64_t n_cells, const int32_t *cell_verts, int64_t n_vertices, const double *rec,
+                        const double *mom, double filter_ratio, double *lm, void *stream);
+int ox_dynamic_bin_sums(int64_t n_cells, const double *lm, const double *vol, int64_t vol_stride, const int32_t *order,
+                        const int32_t *chunks, int64_t n_chunks, double *partials, void *stream);
+int ox_dynamic_bin_coefficients(int64_t n_bins, const int32_t *bin_chunk_ptr, const double *partials, double cs2_max,
+                                double *bins, void *stream);
+int ox_patch_filter_vertices(int k, int64_t n_vertices, const int32_t *ptr, const int32_t *idx, int64_t n_cells,
+                             int64_t n_idx, const double *q, const double *vol, int64_t vol_stride, double *qv,
+                             void *stream);
+int ox_patch_filter_cells(int k, int gdim, int64_t n_cells, const int32_t *cell_verts, int64_t n_vertices, const double *qv,
+                          double *qf, void *stream);
+int ox_dynamic_clip(int64_t n, const double *pairs, double cs2_max, double *cs2, void *stream);
+int ox_eddy_viscosity_cellcoef(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
+                               const double *cs2, int64_t cs2_stride, int64_t n_coef, const int32_t *cell_bin, double *nut,
+                               void *stream);
 /* ---- generalised-Newtonian laws and the full stress form ---- */
 /* nut[e] = max(nu(gd_e) - base, 0), gd = sqrt(2 S:S) with S = sym(grad uab) at the cell's centroid (the quantity of
  * ox_eddy_viscosity's Smagorinsky model), arguments as there.  law 2, Carreau-Yasuda, params = {nu0, nu_inf, lam, n, a}:

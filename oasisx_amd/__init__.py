@@ -15,7 +15,8 @@ from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
 from .scalar import ScalarFlux, ScalarTransport
 from .tracers import Tracers
-from .viscosity import CarreauYasuda, CellViscosity, Cross, PowerLaw, Smagorinsky, VanDriest, Wale
+from .viscosity import (CarreauYasuda, CellViscosity, Cross, DynamicSmagorinsky, PatchFilter, PowerLaw, Smagorinsky, VanDriest,
+                        Wale)
 from .wall import WallStress
 
 logging.basicConfig()
@@ -31,6 +32,8 @@ __all__ = [
     "ScalarTransport",
     "ScalarFlux",
     "Smagorinsky",
+    "DynamicSmagorinsky",
+    "PatchFilter",
     "Wale",
     "VanDriest",
     "WallDistance",

@@ -325,6 +325,15 @@ SIGNATURES = {
                                C.POINTER(ox_sell), C.POINTER(ox_first_args), _I, _P]),
     "ox_eddy_viscosity": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, _P, _P]),
     "ox_eddy_viscosity_damped": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, C.POINTER(ox_vandriest), _P, _P]),
+    "ox_dynamic_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _P]),
+    "ox_dynamic_vertices": (_I, [_I, _L, _P, _P, _L, _P, _P, _P]),
+    "ox_dynamic_products": (_I, [_I, _L, _P, _L, _P, _P, _D, _P, _P]),
+    "ox_dynamic_bin_sums": (_I, [_L, _P, _P, _L, _P, _P, _L, _P, _P]),
+    "ox_dynamic_bin_coefficients": (_I, [_L, _P, _P, _D, _P, _P]),
+    "ox_patch_filter_vertices": (_I, [_I, _L, _P, _P, _L, _L, _P, _P, _L, _P, _P]),
+    "ox_patch_filter_cells": (_I, [_I, _I, _L, _P, _L, _P, _P, _P]),
+    "ox_dynamic_clip": (_I, [_L, _P, _D, _P, _P]),
+    "ox_eddy_viscosity_cellcoef": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _L, _L, _P, _P, _P]),
     "ox_viscosity_law": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, C.POINTER(_D), _I, _P, _P]),
     "ox_assemble_stress_transpose": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P, _P, _D, _P, _P]),
     "ox_flow_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _D, _D, _P, _P, _P, _P]),

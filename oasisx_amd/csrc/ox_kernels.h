@@ -151,6 +151,13 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_BUOYANCY_ROWS 190   // ox_buoyancy_rows (key = 2 x terms + 1 where M is read through its dictionary)
 #define OX_TAG_SCALAR_FLUX 191     // ox_scalar_flux, ox_scalar_flux_cells (key = facets)
 #define OX_TAG_SCALAR_ROWS_CELLVISC 192 // ox_scalar_rows_cellvisc (key = columns)
+#define OX_TAG_DYNAMIC_CELLS 200    // ox_dynamic_cells (key = cells)
+#define OX_TAG_DYNAMIC_VERTICES 201 // ox_dynamic_vertices (key = vertices)
+#define OX_TAG_DYNAMIC_PRODUCTS 202 // ox_dynamic_products (key = cells)
+#define OX_TAG_DYNAMIC_BIN_SUMS 203 // ox_dynamic_bin_sums (key = chunks)
+#define OX_TAG_DYNAMIC_BIN_COEF 204 // ox_dynamic_bin_coefficients (key = bins), ox_dynamic_clip (key = entries)
+#define OX_TAG_PATCH_FILTER 205     // ox_patch_filter_vertices (key = vertices), ox_patch_filter_cells (key = cells)
+#define OX_TAG_EDDY_VISCOSITY_CELLCOEF 206 // ox_eddy_viscosity_cellcoef (key = cells)
 extern bool ox_prof_on;
 void ox_prof_start(int tag, hipStream_t st, long long key = 0);
 void ox_prof_stop(hipStream_t st);

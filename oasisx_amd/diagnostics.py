@@ -362,6 +362,40 @@ def slab_bins(mesh, axis: int, edges=None, tol=None):
     return bins.astype(np.int64), edges
 
 
+def bin_chunk_plan(bins_mesh, local_cells, n_cells, n_bins, who):
+    """The atomic-free plan of a sum over the cells of every bin, built on the device (shared by ``ProfileStatistics``
+    and ``DynamicSmagorinsky``): ``order`` (the sampled cells, kernel numbering, stably sorted by bin), the chunk table
+    ``{first entry, cells, bin, consecutive}`` of at most 256 entries each, none crossing a bin, and ``bin_chunk_ptr``.
+    ``bins_mesh``: the bin of every cell in the MESH's cell order (-1: left out), ``local_cells``: the mesh cell of every
+    kernel cell."""
+    dev = bins_mesh.device
+    if int(local_cells.shape[0]) != n_cells or int(local_cells.max()) >= int(bins_mesh.shape[0]):
+        raise RuntimeError(f"{who}: the solver's cell order does not match its mesh")
+    bk = bins_mesh[local_cells]  # bins in the kernel's cell order
+    sel = torch.nonzero(bk >= 0).reshape(-1)
+    order = sel[torch.sort(bk[sel], stable=True).indices]
+    nb = n_bins
+    count = torch.bincount(bk[sel], minlength=nb)
+    nch = (count + 255) // 256
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    ptr = torch.cat([zero, torch.cumsum(nch, 0)])
+    start = torch.cat([zero, torch.cumsum(count, 0)])
+    cbin = torch.repeat_interleave(torch.arange(nb, device=dev), nch)
+    off = start[cbin] + 256 * (torch.arange(int(ptr[-1]), device=dev) - ptr[cbin])
+    length = torch.minimum(start[cbin + 1] - off, torch.full_like(off, 256))
+    # breaks[i]: entries j <= i of order that do not continue their predecessor
+    brk = torch.cat([zero, torch.cumsum((order[1:] - order[:-1] != 1).to(torch.int64), 0)])
+    consecutive = (brk[off + length - 1] - brk[off]) == 0
+    chunks = torch.stack([off, length, cbin, consecutive.to(torch.int64)], dim=1).to(torch.int32).contiguous()
+    n_sampled = int(order.shape[0])
+    lmin, lmax, lsum = torch.stack([length.min(), length.max(), length.sum()]).tolist()
+    if not (1 <= lmin and lmax <= 256 and lsum == n_sampled):  # (the kernel's lanes index order by these)
+        raise RuntimeError(f"{who}: chunks of {lmin} .. {lmax} cells covering {lsum} of {n_sampled}")
+    return {"order": order.to(torch.int32).contiguous(), "chunks": chunks,
+            "bin_chunk_ptr": ptr.to(torch.int32).contiguous(), "n_chunks": int(chunks.shape[0]), "n_sampled": n_sampled,
+            "bins_kernel": bk}
+
+
 def _tri_index(n, i, j):
     """Position of (i, j), i <= j, in the upper triangle of an n x n matrix stored row by row."""
     return i * n - i * (i - 1) // 2 + j - i
@@ -476,35 +510,10 @@ class ProfileStatistics:
 
     # ---- set-up ------------------------------------------------------------------------------------------------------
     def _build_chunks(self, bins_mesh, local_cells, n_cells):
-        """On the device: ``order`` (the sampled cells, kernel numbering, stably sorted by bin), the chunk table
-        ``{first entry, cells, bin, consecutive}`` of at most 256 entries each, none crossing a bin, and
-        ``bin_chunk_ptr``."""
-        dev = bins_mesh.device
-        if int(local_cells.shape[0]) != n_cells or int(local_cells.max()) >= int(bins_mesh.shape[0]):
-            raise RuntimeError("ProfileStatistics: the solver's cell order does not match its mesh")
-        bk = bins_mesh[local_cells]  # bins in the kernel's cell order
-        sel = torch.nonzero(bk >= 0).reshape(-1)
-        order = sel[torch.sort(bk[sel], stable=True).indices]
-        nb = self.n_bins
-        count = torch.bincount(bk[sel], minlength=nb)
-        nch = (count + 255) // 256
-        zero = torch.zeros(1, dtype=torch.int64, device=dev)
-        ptr = torch.cat([zero, torch.cumsum(nch, 0)])
-        start = torch.cat([zero, torch.cumsum(count, 0)])
-        cbin = torch.repeat_interleave(torch.arange(nb, device=dev), nch)
-        off = start[cbin] + 256 * (torch.arange(int(ptr[-1]), device=dev) - ptr[cbin])
-        length = torch.minimum(start[cbin + 1] - off, torch.full_like(off, 256))
-        # breaks[i]: entries j <= i of order that do not continue their predecessor
-        brk = torch.cat([zero, torch.cumsum((order[1:] - order[:-1] != 1).to(torch.int64), 0)])
-        consecutive = (brk[off + length - 1] - brk[off]) == 0
-        self._order = order.to(torch.int32).contiguous()
-        self._chunks = torch.stack([off, length, cbin, consecutive.to(torch.int64)], dim=1).to(torch.int32).contiguous()
-        self._bin_chunk_ptr = ptr.to(torch.int32).contiguous()
-        self.n_chunks = int(self._chunks.shape[0])
-        self.n_sampled = int(order.shape[0])
-        lmin, lmax, lsum = torch.stack([length.min(), length.max(), length.sum()]).tolist()
-        if not (1 <= lmin and lmax <= 256 and lsum == self.n_sampled):  # (the kernel's lanes index order by these)
-            raise RuntimeError(f"ProfileStatistics: chunks of {lmin} .. {lmax} cells covering {lsum} of {self.n_sampled}")
+        """The chunk plan of ``bin_chunk_plan`` as this object's tables."""
+        plan = bin_chunk_plan(bins_mesh, local_cells, n_cells, self.n_bins, "ProfileStatistics")
+        self._order, self._chunks, self._bin_chunk_ptr = plan["order"], plan["chunks"], plan["bin_chunk_ptr"]
+        self.n_chunks, self.n_sampled = plan["n_chunks"], plan["n_sampled"]
 
     def _add_group(self, members, space, sources, dev):
         d = self.gdim

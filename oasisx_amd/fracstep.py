@@ -108,7 +108,8 @@ class FractionalStep_AB_CN:
             scalar extrapolated to the step's midpoint, added to ``b_first`` inside ``assemble_first`` in one pass over the
             mass matrix (``buoyancy_assemble``); the coupling is explicit in ``c`` and conditionally stable.
             :class:`oasisx_amd.ScalarFlux` reads the Nusselt / Sherwood number through tagged walls.  One GPU only
-        viscosity_model: :class:`oasisx_amd.Smagorinsky`, :class:`oasisx_amd.Wale` or :class:`oasisx_amd.CellViscosity`:
+        viscosity_model: :class:`oasisx_amd.Smagorinsky`, :class:`oasisx_amd.DynamicSmagorinsky` (the coefficient found from
+            the resolved field, ``smagorinsky_coefficient()``), :class:`oasisx_amd.Wale` or :class:`oasisx_amd.CellViscosity`:
             an additional viscosity per cell, ``div(nut grad u)``, evaluated per step from the extrapolated velocity and
             added by the fused assembly kernel (:mod:`oasisx_amd.viscosity`); ``None``: the constant-viscosity step,
             unchanged.  One GPU only; not with ``rotational=True``.  With ``scalars=`` every scalar states its
@@ -549,6 +550,14 @@ class FractionalStep_AB_CN:
         out = torch.zeros(int(self._mesh.num_cells), dtype=torch.float64, device=self._nut.device)
         out[self._Vi[0][0].local_cells.to(torch.int64)] = self._nut
         return out
+
+    def smagorinsky_coefficient(self) -> torch.Tensor:
+        """``Cs2`` per cell of a :class:`oasisx_amd.DynamicSmagorinsky` model, as the last ``assemble_first`` used it: a
+        device tensor ``(num_cells,)`` in the MESH's cell order."""
+        fn = getattr(self._viscosity_model, "coefficient_cells", None)
+        if fn is None:
+            raise RuntimeError("smagorinsky_coefficient: the solver's viscosity_model is not a DynamicSmagorinsky")
+        return fn(self)
 
     def scalar_diffusivity(self, name: str, nu: float) -> torch.Tensor:
         """``kappa + nut_c / Sc_t`` per cell of the scalar ``name`` with the ``nut`` of the last ``assemble_first``: a device

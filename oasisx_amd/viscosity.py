@@ -36,7 +36,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["Smagorinsky", "Wale", "CellViscosity", "CarreauYasuda", "Cross", "PowerLaw", "VanDriest"]
+__all__ = ["Smagorinsky", "Wale", "CellViscosity", "CarreauYasuda", "Cross", "PowerLaw", "VanDriest", "DynamicSmagorinsky",
+           "PatchFilter"]
 
 
 def _coefficient(what, v):
@@ -189,6 +190,298 @@ class Smagorinsky(_KernelModel):
         if self.damping is not None:
             return f"Smagorinsky(Cs={self.coefficient}, damping={self.damping!r})"
         return f"Smagorinsky(Cs={self.coefficient})"
+
+
+class _Patches:
+    """The vertex patches of a solver's mesh for the test filter: the vertex -> cell CSR over vertex CLASSES (on a
+    ``make_periodic`` mesh the patches wrap around the seam), cells in the kernels' order and ascending within a vertex,
+    and the cell -> vertex-class table.  Built once with torch, validated on the host before any launch."""
+
+    def __init__(self, solver, who):
+        mesh = solver._mesh
+        Vi = solver._Vi[0][0]
+        dev = solver._geom.device
+        lc = Vi.local_cells.to(torch.int64).to(dev)
+        self.n_cells = nc = int(solver._geom.shape[0])
+        self.gdim = d = int(mesh.gdim)
+        per = getattr(mesh, "periodic", None)
+        self.n_vertices = nv = int(per.n_free_vertices) if per is not None else int(mesh.coords.shape[0])
+        cv = mesh.topological_cells().to(dev).to(torch.int64)[lc]  # (nc, d + 1), kernel cell order
+        if int(lc.shape[0]) != nc or nc * (d + 1) > 0x7FFFFFFF or nv > 0x7FFFFFFF:
+            raise RuntimeError(f"{who}: {nc} cells, {nv} vertices do not fit the filter's int32 tables")
+        flat = cv.reshape(-1)
+        cell = torch.arange(nc, device=dev).repeat_interleave(d + 1)
+        perm = torch.sort(flat, stable=True).indices  # stable: ascending cell id within a vertex
+        count = torch.bincount(flat, minlength=nv)
+        ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(count, 0)])
+        idx = cell[perm]
+        # the host check: monotone pointer, every index below n_cells, every vertex with at least one cell
+        lo, hi, cmin, total = (int(v) for v in torch.stack([idx.min(), idx.max(), count.min(), ptr[-1]]).tolist())
+        if int(flat.min()) < 0 or int(flat.max()) >= nv or int(count.shape[0]) != nv:
+            raise ValueError(f"{who}: a cell names a vertex outside 0 .. {nv - 1}")
+        if cmin < 1:
+            raise ValueError(f"{who}: vertex {int(torch.argmin(count))} belongs to no cell (the test filter has no patch there)")
+        if lo < 0 or hi >= nc or total != nc * (d + 1) or not bool((ptr[1:] > ptr[:-1]).all()):
+            raise RuntimeError(f"{who}: the vertex -> cell table is inconsistent ({total} entries, cells {lo} .. {hi})")
+        self.ptr, self.idx = ptr.to(torch.int32).contiguous(), idx.to(torch.int32).contiguous()
+        self.cell_verts = cv.to(torch.int32).contiguous()
+        self.n_idx = total
+        self.max_patch = int(count.max())
+        self.local_cells = lc
+
+
+class PatchFilter:
+    """The test filter of the dynamic procedure, the vertex-patch top hat, for per-cell data::
+
+        q_v  = sum_{c in patch(v)} |c| q_c / sum_{c in patch(v)} |c|      q^_c = mean of q_v over the cell's vertices
+
+    Vertices are mesh vertices (vertex classes on a periodic mesh), so the filter is the same for P1 / P2 / P3; boundary
+    patches are one-sided; constants are preserved and the weights are positive.  ``apply(q)`` takes a device tensor
+    ``(num_cells,)`` or ``(num_cells, k)`` in the MESH's cell order and returns the filtered tensor of the same shape:
+    two launches (``ox_patch_filter_vertices``, ``ox_patch_filter_cells``), the ones ``average="local"`` runs.
+    ``k = 1`` and ``k = 2`` are instantiated."""
+
+    def __init__(self, solver, _patches=None):
+        comm = getattr(solver._mesh, "comm", None)
+        if comm is not None and getattr(comm, "size", 1) > 1:
+            raise NotImplementedError("PatchFilter on a mesh partition (comm.size > 1): the patches are built for one GPU")
+        self._solver = solver
+        self._p = _patches if _patches is not None else _Patches(solver, "PatchFilter")
+        p = self._p
+        dev = solver._geom.device
+        # |c| in kernel cell order, as the kernels form it from |det J|
+        d = p.gdim
+        adet = solver._geom[:, d * d]
+        self._vol = (0.5 * adet if d == 2 else adet * (1.0 / 6.0)).contiguous()
+        self._qv = torch.zeros((p.n_vertices, 2), dtype=torch.float64, device=dev)
+
+    def _launch(self, k, q, out, vol=None, vol_stride=1):
+        """q, out: (n_cells, k) contiguous, kernel cell order."""
+        p, lib, st = self._p, self._solver._lib, _lib.current_stream()
+        vol = _lib.ptr(self._vol) if vol is None else vol  # (or the address of the |c| column of the cell records)
+        _lib.check(lib.ox_patch_filter_vertices(k, p.n_vertices, _lib.ptr(p.ptr), _lib.ptr(p.idx), p.n_cells, p.n_idx,
+                                                _lib.ptr(q), vol, vol_stride, _lib.ptr(self._qv), st),
+                   "ox_patch_filter_vertices")
+        _lib.check(lib.ox_patch_filter_cells(k, p.gdim, p.n_cells, _lib.ptr(p.cell_verts), p.n_vertices, _lib.ptr(self._qv),
+                                             _lib.ptr(out), st), "ox_patch_filter_cells")
+
+    def apply(self, q: torch.Tensor) -> torch.Tensor:
+        p = self._p
+        nc_mesh = int(self._solver._mesh.num_cells)
+        if not torch.is_tensor(q) or q.dtype != torch.float64 or q.dim() not in (1, 2) or int(q.shape[0]) != nc_mesh:
+            raise ValueError(f"PatchFilter.apply: a float64 tensor ({nc_mesh},) or ({nc_mesh}, k) in the mesh's cell order is "
+                             "expected")
+        k = 1 if q.dim() == 1 else int(q.shape[1])
+        if k not in (1, 2):
+            raise NotImplementedError(f"PatchFilter.apply: k = {k} (k = 1 and k = 2 are instantiated)")
+        qk = q.to(self._vol.device).reshape(nc_mesh, k)[p.local_cells].contiguous()
+        out = torch.empty_like(qk)
+        self._launch(k, qk, out)
+        res = torch.zeros((nc_mesh, k), dtype=torch.float64, device=out.device)
+        res[p.local_cells] = out
+        return res.reshape(q.shape)
+
+
+class DynamicSmagorinsky(_KernelModel):
+    """The dynamic Smagorinsky model (Germano et al. 1991, Lilly 1992): ``nut_c = Cs2_c Delta_c^2 sqrt(2 S:S)`` with
+    ``Cs2 = -(1/2) <Ld:M> / <M:M>`` from the step's ``u_ab``, clipped to ``[0, cs2_max]`` (0 where ``<M:M>`` is not
+    positive); ``L = (u u^T)^ - u^ u^^T``, ``M = filter_ratio^2 Delta^2 |S^| S^ - (Delta^2 |S| S)^`` with the vertex-patch
+    test filter ``^`` of :class:`PatchFilter`.  2-D and 3-D, P1 / P2 / P3.
+
+    Args:
+        average: ``"global"``: ``<.>`` sums ``|c| .`` over all cells, or over the cells of each bin where ``axis=`` /
+            ``cell_bins=`` is given; ``"local"``: ``<.>`` is the test filter applied once more, a coefficient per cell
+        axis, edges, tol: bins as ``slab_bins(mesh, axis, edges, tol)``
+        cell_bins: bins as for ``ProfileStatistics`` (mesh cell order; -1: the cell gets ``Cs2 = 0``)
+        filter_ratio: test-filter width over grid-filter width (> 1)
+        cs2_max: the upper clip of ``Cs2`` (>= 0)
+        update_every: ``Cs2`` is recomputed in the first ``assemble_first`` and every n-th after it; ``nut`` is recomputed
+            from the stored ``Cs2`` in every step
+    """
+
+    model_id = 0
+    damping = None
+
+    def __init__(self, average="global", axis=None, edges=None, cell_bins=None, filter_ratio=2.0, cs2_max=0.09,
+                 update_every=1, tol=None):
+        if average not in ("global", "local"):
+            raise ValueError(f'DynamicSmagorinsky: average is "global" or "local" (got {average!r})')
+        if axis is not None and cell_bins is not None:
+            raise ValueError("DynamicSmagorinsky: give at most one of axis= (with optional edges=) and cell_bins=")
+        if average == "local" and (axis is not None or cell_bins is not None):
+            raise ValueError('DynamicSmagorinsky: average="local" takes no bins (axis= / cell_bins= belong to "global")')
+        if edges is not None and axis is None:
+            raise ValueError("DynamicSmagorinsky: edges= belongs to axis=")
+        self.average = average
+        self.axis = None if axis is None else int(axis)
+        self.edges_arg, self.tol = edges, tol
+        self.cell_bins_arg = cell_bins
+        self.filter_ratio = float(filter_ratio)
+        if not np.isfinite(self.filter_ratio) or self.filter_ratio <= 1.0:
+            raise ValueError(f"DynamicSmagorinsky: filter_ratio must be finite and > 1 (got {filter_ratio})")
+        self.cs2_max = float(cs2_max)
+        if not np.isfinite(self.cs2_max) or self.cs2_max < 0.0:
+            raise ValueError(f"DynamicSmagorinsky: cs2_max must be finite and >= 0 (got {cs2_max})")
+        if int(update_every) != update_every or int(update_every) < 1:
+            raise ValueError(f"DynamicSmagorinsky: update_every must be an integer >= 1 (got {update_every})")
+        self.update_every = int(update_every)
+        self.edges = None
+        self.n_bins = None
+        self.n_evaluations = 0  # assemble_first calls seen
+        self.n_updates = 0      # of which recomputed Cs2
+        self._patches = None
+
+    # ---- what can be refused without the library
+    def _bins_of(self, mesh):
+        """(bins in mesh cell order or None, n_bins)."""
+        nc = int(mesh.num_cells)
+        if self.average == "local":
+            return None, 0
+        if self.axis is not None:
+            from .diagnostics import slab_bins
+
+            bins, self.edges = slab_bins(mesh, self.axis, self.edges_arg, self.tol)
+        elif self.cell_bins_arg is not None:
+            cb = self.cell_bins_arg
+            bins = np.asarray(cb.cpu().numpy() if torch.is_tensor(cb) else cb)
+            if bins.shape != (nc,) or not np.issubdtype(bins.dtype, np.integer):
+                raise ValueError(f"DynamicSmagorinsky: cell_bins must be {nc} integers in the mesh's cell order")
+            bins = bins.astype(np.int64)
+            if bins.min() < -1 or bins.max() < 0:
+                raise ValueError("DynamicSmagorinsky: cell_bins holds values below -1, or no cell is in a bin")
+        else:
+            bins = np.zeros(nc, dtype=np.int64)
+        nb = int(bins.max()) + 1
+        count = np.bincount(bins[bins >= 0], minlength=nb)
+        if (count == 0).any():
+            raise ValueError(f"DynamicSmagorinsky: bin {int(np.argmax(count == 0))} holds no cell")
+        return bins, nb
+
+    def check_mesh(self, mesh):
+        self._bins_of(mesh)
+
+    def bind(self, solver):
+        from .diagnostics import bin_chunk_plan
+
+        mesh = solver._mesh
+        dev = solver._geom.device
+        self._patches = p = _Patches(solver, "DynamicSmagorinsky")
+        d, nc = p.gdim, p.n_cells
+        ns = d * (d + 1) // 2
+        self._nr, self._nm = d + ns + 2, d + 3 * ns
+        f64 = dict(dtype=torch.float64, device=dev)
+        self._rec = torch.zeros((nc, self._nr), **f64)
+        self._mom = torch.zeros((p.n_vertices, self._nm), **f64)
+        self._lm = torch.zeros((nc, 2), **f64)
+        bins, nb = self._bins_of(mesh)
+        self.n_bins = nb
+        if self.average == "local":
+            self._filter = PatchFilter(solver, _patches=p)
+            self._lmf = torch.zeros((nc, 2), **f64)
+            self._cs2 = torch.zeros(nc, **f64)
+        else:
+            plan = bin_chunk_plan(torch.from_numpy(bins).to(dev), p.local_cells, nc, nb, "DynamicSmagorinsky")
+            self._plan = plan
+            self._cell_bin = plan["bins_kernel"].to(torch.int32).contiguous()
+            self._partials = torch.zeros((plan["n_chunks"], 2), **f64)
+            self._bins = torch.zeros((nb, 4), **f64)  # {sum |c| LM, sum |c| MM, Cs2 unclipped, Cs2 clipped}
+        self.n_evaluations = self.n_updates = 0
+
+    # ---- per assemble_first
+    def update_coefficient(self, solver):
+        """The launches that recompute ``Cs2`` from the solver's ``u_ab``."""
+        import ctypes as C
+
+        p, lib, st = self._patches, solver._lib, _lib.current_stream()
+        Vi = solver._Vi[0][0]
+        _lib.check(lib.ox_dynamic_cells(Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs), solver._UAB.rptr(),
+                                        _lib.ptr(self._rec), st), "ox_dynamic_cells")
+        _lib.check(lib.ox_dynamic_vertices(p.gdim, p.n_vertices, _lib.ptr(p.ptr), _lib.ptr(p.idx), p.n_cells,
+                                           _lib.ptr(self._rec), _lib.ptr(self._mom), st), "ox_dynamic_vertices")
+        _lib.check(lib.ox_dynamic_products(p.gdim, p.n_cells, _lib.ptr(p.cell_verts), p.n_vertices, _lib.ptr(self._rec),
+                                           _lib.ptr(self._mom), self.filter_ratio, _lib.ptr(self._lm), st),
+                   "ox_dynamic_products")
+        vol = C.c_void_p(self._rec.data_ptr() + 8 * (self._nr - 1))  # |c|: the last column of the cell records
+        if self.average == "local":
+            self._filter._launch(2, self._lm, self._lmf, vol=vol, vol_stride=self._nr)
+            _lib.check(lib.ox_dynamic_clip(p.n_cells, _lib.ptr(self._lmf), self.cs2_max, _lib.ptr(self._cs2), st),
+                       "ox_dynamic_clip")
+        else:
+            pl = self._plan
+            _lib.check(lib.ox_dynamic_bin_sums(p.n_cells, _lib.ptr(self._lm), vol, self._nr, _lib.ptr(pl["order"]),
+                                               _lib.ptr(pl["chunks"]), pl["n_chunks"], _lib.ptr(self._partials), st),
+                       "ox_dynamic_bin_sums")
+            _lib.check(lib.ox_dynamic_bin_coefficients(self.n_bins, _lib.ptr(pl["bin_chunk_ptr"]), _lib.ptr(self._partials),
+                                                       self.cs2_max, _lib.ptr(self._bins), st),
+                       "ox_dynamic_bin_coefficients")
+        self.n_updates += 1
+
+    def evaluate(self, solver, nut: torch.Tensor, nu=None):
+        import ctypes as C
+
+        if self._patches is None:
+            raise RuntimeError("DynamicSmagorinsky: the model is not bound to a solver")
+        if self.n_evaluations % self.update_every == 0:
+            self.update_coefficient(solver)
+        self.n_evaluations += 1
+        Vi = solver._Vi[0][0]
+        if self.average == "local":
+            cs2, stride, n, cb = _lib.ptr(self._cs2), 1, self._patches.n_cells, None
+        else:
+            cs2, stride, n, cb = C.c_void_p(self._bins.data_ptr() + 8 * 3), 4, self.n_bins, _lib.ptr(self._cell_bin)
+        _lib.check(solver._lib.ox_eddy_viscosity_cellcoef(Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
+                                                          solver._UAB.rptr(), cs2, stride, n, cb, _lib.ptr(nut),
+                                                          _lib.current_stream()), "ox_eddy_viscosity_cellcoef")
+
+    # ---- accessors
+    def _need(self, what):
+        if self._patches is None or self.n_updates == 0:
+            raise RuntimeError(f"DynamicSmagorinsky.{what}: no assemble_first has run with this model")
+
+    def _to_mesh_order(self, t):
+        lc = self._patches.local_cells
+        out = torch.zeros((int(lc.max()) + 1,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+        out[lc] = t
+        return out
+
+    def coefficient_cells(self, solver=None) -> torch.Tensor:
+        """``Cs2`` per cell (clipped), device tensor in the MESH's cell order."""
+        self._need("coefficient_cells")
+        if self.average == "local":
+            ck = self._cs2
+        else:
+            cb = self._cell_bin.to(torch.int64)
+            ck = torch.where(cb >= 0, self._bins[:, 3][cb.clamp_min(0)], torch.zeros_like(self._bins[:1, 3]))
+        nc_mesh = int(solver._mesh.num_cells) if solver is not None else int(self._patches.local_cells.max()) + 1
+        out = torch.zeros(nc_mesh, dtype=torch.float64, device=ck.device)
+        out[self._patches.local_cells] = ck
+        return out
+
+    def bin_coefficients(self, clipped=True) -> torch.Tensor:
+        """``Cs2`` per bin (length 1 for the global average), clipped or as the ratio stands."""
+        self._need("bin_coefficients")
+        if self.average == "local":
+            raise RuntimeError('DynamicSmagorinsky.bin_coefficients: average="local" has a coefficient per cell')
+        return self._bins[:, 3 if clipped else 2].clone()
+
+    def bin_sums(self) -> torch.Tensor:
+        """``(sum |c| LM, sum |c| MM)`` per bin, shape ``(n_bins, 2)``."""
+        self._need("bin_sums")
+        if self.average == "local":
+            raise RuntimeError('DynamicSmagorinsky.bin_sums: average="local" has no bins')
+        return self._bins[:, :2].clone()
+
+    def products(self):
+        """``(LM, MM)`` per cell, ``Ld:M`` and ``M:M``, device tensors in the MESH's cell order."""
+        self._need("products")
+        both = self._to_mesh_order(self._lm)
+        return both[:, 0].contiguous(), both[:, 1].contiguous()
+
+    def __repr__(self):
+        where = self.average if self.axis is None and self.cell_bins_arg is None else (
+            f"axis={self.axis}" if self.axis is not None else "cell_bins")
+        return (f"DynamicSmagorinsky({where}, filter_ratio={self.filter_ratio}, cs2_max={self.cs2_max}, "
+                f"update_every={self.update_every})")
 
 
 class Wale(_KernelModel):
@@ -363,8 +656,8 @@ class CellViscosity:
 def check_model(model, mesh, rotational: bool, scalars) -> None:
     """The scope guards of ``viscosity_model=``; run before anything is built (and before the HIP library is loaded)."""
     if not isinstance(model, (_KernelModel, CellViscosity)):
-        raise TypeError("viscosity_model: a Smagorinsky, Wale, CarreauYasuda, Cross, PowerLaw or CellViscosity object is "
-                        "expected "
+        raise TypeError("viscosity_model: a Smagorinsky, DynamicSmagorinsky, Wale, CarreauYasuda, Cross, PowerLaw or "
+                        "CellViscosity object is expected "
                         f"(got {type(model).__name__})")
     if rotational:
         raise NotImplementedError("viscosity_model with rotational=True: the xi nu div(u) term of the rotational pressure "
@@ -380,5 +673,7 @@ def check_model(model, mesh, rotational: bool, scalars) -> None:
     model.check(mesh.geometry.dim)
     if getattr(model, "damping", None) is not None:
         model.check_mesh(mesh)  # an empty wall selection fails here
+    if isinstance(model, DynamicSmagorinsky):
+        model.check_mesh(mesh)  # bins that do not fit the mesh fail here
     if isinstance(model, CellViscosity):
         model.values(mesh)  # a callable or an array of the wrong length / sign fails here, not in the first step
