@@ -841,6 +841,46 @@ typedef struct ox_tracer_args {
 } ox_tracer_args;
 int ox_tracer_advance(const ox_tracer_args *args, void *stream);
 
+/* Lagrangian averaging of the dynamic Smagorinsky model (Meneveau, Lund & Cabot 1996): one lane per
+ * vertex class, float64, one launch.  With s_LM = -2 src[v][0], s_MM = 4 src[v][1] (src: the k = 2 vertex pass of
+ * ox_patch_filter_vertices on {Ld:M, M:M}):
+ *   first != 0:  F_MM = s_MM, F_LM = max(cs2_initial s_MM, cs2_floor s_MM), status 0, nothing is traced.
+ *   first == 0:  x' = x[v] - h u[v u_stride ..], folded into [lo, hi) on every axis with periodic[k] != 0; its cell is
+ *     hint[v] (a mesh cell id) when all barycentric coordinates there are >= 0, else the LOWEST containing cell of the
+ *     locator (lambda >= -tol): the rule of ox_tracer_advance.  B = the P1 interpolant of f_old at x' through
+ *     cell_verts[cell_inv[cell]], summed in local vertex order.  status 1 (no cell holds x'): B = f_old[v].
+ *     T = time_scale delta[v] (F_LM F_MM)^(-1/8) of f_old[v], eps = (h/T) / (1 + h/T), 0 where the product is not positive
+ *     and finite, NaN where it is NaN.  F_MM = eps s_MM + (1 - eps) B_MM, F_LM = max(eps s_LM + (1 - eps) B_LM,
+ *     cs2_floor F_MM); a NaN passes the max.  status 2 (x' not finite, or hint / cell_inv / cell_verts out of range):
+ *     both fields NaN, nothing read out of range.
+ *   cs2v[v] = F_LM / F_MM clipped to [0, cs2_max], 0 where F_MM is not positive, NaN where either is NaN.
+ * f_old, f_new [n_vertices][2] = {F_LM, F_MM} must differ (lanes read their neighbours' old values); cell_verts
+ * [n_cells][gdim + 1] in kernel cell order, cell_inv [n_mesh_cells] as for ox_tracer_advance; loc: a whole-mesh locator.
+ * Arguments are checked on the host before the first device call; n_vertices == 0 launches nothing. */
+typedef struct ox_lagrangian_args {
+  const ox_locator *loc;
+  int gdim, first;
+  int64_t n_vertices;
+  const double *x;           /* [n_vertices][gdim]                              */
+  const double *u;           /* row v: u + v u_stride, gdim entries             */
+  int64_t u_stride;
+  const int64_t *hint;       /* [n_vertices]                                    */
+  const int64_t *cell_inv;   /* [n_mesh_cells]                                  */
+  int64_t n_mesh_cells;
+  const int32_t *cell_verts; /* [n_cells][gdim + 1]                             */
+  int64_t n_cells;
+  const double *src;         /* [n_vertices][2]                                 */
+  const double *delta;       /* [n_vertices]                                    */
+  const double *f_old;
+  double *f_new;
+  double *cs2v;              /* [n_vertices]                                    */
+  int32_t *status;           /* [n_vertices]                                    */
+  double h, time_scale, cs2_floor, cs2_max, cs2_initial, tol;
+  int periodic[3];
+  double lo[3], hi[3], period[3];
+} ox_lagrangian_args;
+int ox_dynamic_lagrangian(const ox_lagrangian_args *args, void *stream);
+
 /* ---- Distance to the nearest wall facet (ox_probe.hip) ------------------------------------------
  * facet_xyz (device [n_facets][gdim][gdim]): the vertices of the wall facets, segments in 2-D and triangles in 3-D;
  * n_facets >= 1.  The object copies them, lays the locator's uniform grid over their bounding box (an axis without

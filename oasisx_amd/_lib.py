@@ -259,6 +259,39 @@ class ox_tracer_args(C.Structure):
     ]
 
 
+class ox_lagrangian_args(C.Structure):
+    _fields_ = [
+        ("loc", C.c_void_p),
+        ("gdim", C.c_int),
+        ("first", C.c_int),
+        ("n_vertices", C.c_int64),
+        ("x", C.c_void_p),
+        ("u", C.c_void_p),
+        ("u_stride", C.c_int64),
+        ("hint", C.c_void_p),
+        ("cell_inv", C.c_void_p),
+        ("n_mesh_cells", C.c_int64),
+        ("cell_verts", C.c_void_p),
+        ("n_cells", C.c_int64),
+        ("src", C.c_void_p),
+        ("delta", C.c_void_p),
+        ("f_old", C.c_void_p),
+        ("f_new", C.c_void_p),
+        ("cs2v", C.c_void_p),
+        ("status", C.c_void_p),
+        ("h", C.c_double),
+        ("time_scale", C.c_double),
+        ("cs2_floor", C.c_double),
+        ("cs2_max", C.c_double),
+        ("cs2_initial", C.c_double),
+        ("tol", C.c_double),
+        ("periodic", C.c_int * 3),
+        ("lo", C.c_double * 3),
+        ("hi", C.c_double * 3),
+        ("period", C.c_double * 3),
+    ]
+
+
 class ox_buoy_term(C.Structure):
     _fields_ = [
         ("c1", C.c_void_p),
@@ -376,6 +409,7 @@ SIGNATURES = {
     "ox_eval_points": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P]),
     "ox_probe_sample": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _L, _L, _P]),
     "ox_tracer_advance": (_I, [C.POINTER(ox_tracer_args), _P]),
+    "ox_dynamic_lagrangian": (_I, [C.POINTER(ox_lagrangian_args), _P]),
     "ox_walldist_create": (_I, [_I, _P, _L, C.POINTER(_I), _P, C.POINTER(_P)]),
     "ox_walldist_destroy": (_I, [_P]),
     "ox_walldist_info": (_I, [_P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)]),

@@ -158,6 +158,7 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_DYNAMIC_BIN_COEF 204 // ox_dynamic_bin_coefficients (key = bins), ox_dynamic_clip (key = entries)
 #define OX_TAG_PATCH_FILTER 205     // ox_patch_filter_vertices (key = vertices), ox_patch_filter_cells (key = cells)
 #define OX_TAG_EDDY_VISCOSITY_CELLCOEF 206 // ox_eddy_viscosity_cellcoef (key = cells)
+#define OX_TAG_DYNAMIC_LAGRANGIAN 207 // ox_dynamic_lagrangian (key = vertices)
 extern bool ox_prof_on;
 void ox_prof_start(int tag, hipStream_t st, long long key = 0);
 void ox_prof_stop(hipStream_t st);

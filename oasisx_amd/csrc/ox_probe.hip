@@ -627,6 +627,106 @@ __global__ __launch_bounds__(256) void k_tracer_advance(TracerParams P) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Lagrangian averaging of the dynamic Smagorinsky model: one lane per vertex class traces its path
+// line back over h with the patch-mean velocity, x' = x_v - h u_v (folded into the box on periodic axes), finds the cell
+// of x' by the tracers' rule (tracer_locate with the patch's first cell as the hint), interpolates the OLD pair
+// {F_LM, F_MM} there (P1, local vertex order) and relaxes it towards the sources.  The new pair goes to a second buffer:
+// lanes read their neighbours' old values.  No LDS, no atomics, no cross-lane traffic; the only loop is the clamped list
+// walk of tracer_locate.
+struct LagParams {
+  int64_t n;                 // vertex classes
+  const double *x;           // [n][D] the master vertex of every class
+  const double *u;           // patch-mean velocity: the first D entries of row v
+  int64_t u_stride;
+  const int64_t *hint;       // [n] mesh cell id of the first cell of the vertex's patch
+  const int64_t *cell_inv;   // [n_loc] mesh cell id -> kernel cell position
+  int64_t n_cells;
+  const int32_t *cell_verts; // [n_cells][D + 1] vertex classes, kernel cell order
+  const double *src;         // [n][2] {(LM)_v, (MM)_v}
+  const double *delta;       // [n]
+  const double *f_old;       // [n][2] {F_LM, F_MM}
+  double *f_new;
+  double *cs2v;              // [n]
+  int32_t *status;           // [n]
+  double h, time_scale, cs2_floor, cs2_max, cs2_initial;
+  int first;
+  int periodic[3];
+  double lo[3], hi[3], period[3];
+};
+
+// max(a, b) that lets a NaN of either side through
+__device__ __forceinline__ double lag_max(double a, double b) { return a >= b ? a : (a != a ? a : b); }
+
+// lm / mm clipped to [0, cmax]; 0 where mm is not positive; a NaN stays a NaN (the comparison forms of dyn_clip)
+__device__ __forceinline__ double lag_clip(double lm, double mm, double cmax) {
+  if (mm > 0.0) {
+    const double c = lm / mm;
+    return c < 0.0 ? 0.0 : (c > cmax ? cmax : c);  // (NaN fails both comparisons)
+  }
+  return (mm != mm || lm != lm) ? (double)NAN : 0.0;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_dyn_lagrangian(TracerParams L, LagParams A) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= A.n) return;
+  const double s_lm = -2.0 * A.src[2 * v], s_mm = 4.0 * A.src[2 * v + 1];
+  double f_lm, f_mm;
+  int status = 0;
+  if (A.first) {
+    f_mm = s_mm;
+    f_lm = lag_max(A.cs2_initial * s_mm, A.cs2_floor * s_mm);
+  } else {
+    const double o_lm = A.f_old[2 * v], o_mm = A.f_old[2 * v + 1];
+    double xd[D], b_lm = o_lm, b_mm = o_mm;
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      double xk = fma(-A.h, A.u[v * A.u_stride + k], A.x[v * D + k]);
+      finite = finite && isfinite(xk);
+      if (A.periodic[k]) {
+        xk -= A.period[k] * floor((xk - A.lo[k]) / A.period[k]);
+        if (xk >= A.hi[k]) xk -= A.period[k];
+      }
+      xd[k] = xk;
+    }
+    int64_t cell = A.hint[v];
+    double lam[D + 1];
+    if (!finite || cell < 0 || cell >= L.n_loc) status = 2;
+    else if (!tracer_locate<D>(L, xd, cell, lam)) status = 1;
+    else {
+      const int64_t kp = A.cell_inv[cell];  // (cell is in [0, n_loc): tracer_locate's answer)
+      if (kp < 0 || kp >= A.n_cells) status = 2;
+      else {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int j = 0; j <= D; ++j) {
+          const int64_t w = A.cell_verts[kp * (D + 1) + j];
+          if (w < 0 || w >= A.n) status = 2;
+          else a = fma(lam[j], A.f_old[2 * w], a), b = fma(lam[j], A.f_old[2 * w + 1], b);
+        }
+        b_lm = a, b_mm = b;
+      }
+    }
+    const double p = o_lm * o_mm;
+    double eps = 0.0;
+    if (p != p) eps = p;
+    else if (p > 0.0 && p < INFINITY) {
+      const double T = A.time_scale * A.delta[v] * (1.0 / sqrt(sqrt(sqrt(p))));  // p^(-1/8)
+      const double r = A.h / T;
+      eps = r / (1.0 + r);
+    }
+    f_mm = fma(eps, s_mm, (1.0 - eps) * b_mm);
+    f_lm = lag_max(fma(eps, s_lm, (1.0 - eps) * b_lm), A.cs2_floor * f_mm);
+    if (status == 2) f_lm = f_mm = NAN;
+  }
+  A.f_new[2 * v] = f_lm;
+  A.f_new[2 * v + 1] = f_mm;
+  A.cs2v[v] = lag_clip(f_lm, f_mm, A.cs2_max);
+  A.status[v] = status;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host side
 static void loc_free(ox_locator *L) {
   if (!L) return;
@@ -902,6 +1002,62 @@ extern "C" int ox_tracer_advance(const ox_tracer_args *a, void *stream) {
     case 32: hipLaunchKernelGGL((k_tracer_advance<3, 2>), grid, blk, 0, st, P); break;
     default: hipLaunchKernelGGL((k_tracer_advance<3, 3>), grid, blk, 0, st, P); break;
   }
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ox_dynamic_lagrangian(const ox_lagrangian_args *a, void *stream) {
+  if (!a) OX_FAIL("ox_dynamic_lagrangian: null argument (args)");
+  if (!a->loc) OX_FAIL("ox_dynamic_lagrangian: null argument (loc)");
+  if (a->gdim != 2 && a->gdim != 3) OX_FAIL("ox_dynamic_lagrangian: gdim=%d", a->gdim);
+  const ox_locator *L = a->loc;
+  if (L->ids) OX_FAIL("ox_dynamic_lagrangian: a locator over a selection of cells; the back-trace takes the whole-mesh locator");
+  if (L->gdim != a->gdim) OX_FAIL("ox_dynamic_lagrangian: loc->gdim=%d, gdim=%d", L->gdim, a->gdim);
+  if (a->n_mesh_cells != L->n_cells)
+    OX_FAIL("ox_dynamic_lagrangian: n_mesh_cells=%lld, the locator holds %lld", (long long)a->n_mesh_cells,
+            (long long)L->n_cells);
+  if (!(a->tol >= 0.0) || a->tol > L->tol)
+    OX_FAIL("ox_dynamic_lagrangian: tol=%g, the grid was built for tol <= %g", a->tol, L->tol);
+  if (a->n_vertices < 0 || a->n_vertices > (int64_t)0x7fffffff)
+    OX_FAIL("ox_dynamic_lagrangian: n_vertices=%lld", (long long)a->n_vertices);
+  if (!std::isfinite(a->h) || a->h < 0.0) OX_FAIL("ox_dynamic_lagrangian: h=%g (finite, >= 0)", a->h);
+  if (!std::isfinite(a->time_scale) || !(a->time_scale > 0.0)) OX_FAIL("ox_dynamic_lagrangian: time_scale=%g", a->time_scale);
+  if (!std::isfinite(a->cs2_max) || a->cs2_max < 0.0) OX_FAIL("ox_dynamic_lagrangian: cs2_max=%g", a->cs2_max);
+  if (!(a->cs2_floor >= 0.0) || a->cs2_floor > a->cs2_max)
+    OX_FAIL("ox_dynamic_lagrangian: cs2_floor=%g (0..cs2_max=%g)", a->cs2_floor, a->cs2_max);
+  if (!std::isfinite(a->cs2_initial) || a->cs2_initial < 0.0) OX_FAIL("ox_dynamic_lagrangian: cs2_initial=%g", a->cs2_initial);
+  if (a->u_stride < a->gdim) OX_FAIL("ox_dynamic_lagrangian: u_stride=%lld", (long long)a->u_stride);
+  for (int k = 0; k < a->gdim; ++k)
+    if (a->periodic[k] && (!std::isfinite(a->lo[k]) || !std::isfinite(a->hi[k]) || !(a->period[k] > 0.0) ||
+                           !std::isfinite(a->period[k]) || !(a->hi[k] > a->lo[k])))
+      OX_FAIL("ox_dynamic_lagrangian: periodic axis %d with box %g .. %g, period %g", k, a->lo[k], a->hi[k], a->period[k]);
+  if (a->n_vertices == 0) return 0;
+  if (a->n_cells < 1 || a->n_cells > (int64_t)0x7fffffff) OX_FAIL("ox_dynamic_lagrangian: n_cells=%lld", (long long)a->n_cells);
+  if (!a->x || !a->u || !a->hint || !a->cell_inv || !a->cell_verts || !a->src || !a->delta)
+    OX_FAIL("ox_dynamic_lagrangian: null argument (x, u, hint, cell_inv, cell_verts, src, delta)");
+  if (!a->f_old || !a->f_new || !a->cs2v || !a->status) OX_FAIL("ox_dynamic_lagrangian: null argument (f_old, f_new, cs2v, status)");
+  if (a->f_old == a->f_new) OX_FAIL("ox_dynamic_lagrangian: f_new is f_old; lanes read their neighbours' old values");
+  TracerParams P;
+  memset(&P, 0, sizeof(P));
+  P.G = L->grid;
+  P.n_loc = L->n_cells, P.n_bins = L->n_bins, P.n_list = L->n_list;
+  P.bin_ptr = L->bin_ptr, P.list = L->list, P.x0 = L->x0, P.grad = L->grad;
+  P.tol = a->tol, P.use_hint = 1;
+  LagParams A;
+  memset(&A, 0, sizeof(A));
+  A.n = a->n_vertices, A.x = a->x, A.u = a->u, A.u_stride = a->u_stride, A.hint = a->hint;
+  A.cell_inv = a->cell_inv, A.n_cells = a->n_cells, A.cell_verts = a->cell_verts;
+  A.src = a->src, A.delta = a->delta, A.f_old = a->f_old, A.f_new = a->f_new, A.cs2v = a->cs2v, A.status = a->status;
+  A.h = a->h, A.time_scale = a->time_scale, A.cs2_floor = a->cs2_floor, A.cs2_max = a->cs2_max;
+  A.cs2_initial = a->cs2_initial, A.first = a->first ? 1 : 0;
+  for (int k = 0; k < a->gdim; ++k)
+    A.periodic[k] = a->periodic[k] ? 1 : 0, A.lo[k] = a->lo[k], A.hi[k] = a->hi[k], A.period[k] = a->period[k];
+  hipStream_t st = ox_stream(stream);
+  const dim3 grid((unsigned)((a->n_vertices + 255) / 256)), blk(256);
+  if (ox_prof_on) ox_prof_start(OX_TAG_DYNAMIC_LAGRANGIAN, st, a->n_vertices);
+  if (a->gdim == 2) hipLaunchKernelGGL((k_dyn_lagrangian<2>), grid, blk, 0, st, P, A);
+  else hipLaunchKernelGGL((k_dyn_lagrangian<3>), grid, blk, 0, st, P, A);
+  if (ox_prof_on) ox_prof_stop(st);
   OX_LAUNCH_CHECK();
   return 0;
 }

@@ -452,7 +452,7 @@ class FractionalStep_AB_CN:
                 raise ValueError(f"assemble_first: nu = {nu} with {self._viscosity_model!r}: the law's nut is nu(gd) - "
                                  f"base_viscosity, so the step runs at nu = base_viscosity = {base}")
             # nut per cell from u_ab, then the fused kernel with nut K_c added to the convection rows of every cell
-            self.viscosity_assemble(nu)
+            self.viscosity_assemble(nu, dt)
         self._assemble_first_rows(dt, nu, want_au)
         if self._viscosity_model is not None and self._stress_form == "full":
             self.stress_transpose_assemble()
@@ -502,13 +502,17 @@ class FractionalStep_AB_CN:
         self._outlet_backflow.add()
 
     @_phase
-    def viscosity_assemble(self, nu=None):
+    def viscosity_assemble(self, nu=None, dt=None):
         """``nut`` per cell (kernel cell order) of the model, from the ``u_ab`` block ``assemble_first`` has just formed
         (``ox_eddy_viscosity``; a :class:`CellViscosity` copies its fixed values).  ``nu``: the molecular viscosity of the
-        step, read only by a model with wall damping (``y+ = d u_tau / nu``)."""
+        step, read only by a model with wall damping (``y+ = d u_tau / nu``).  ``dt``: the step, handed only to a model
+        that declares ``needs_dt`` (the Lagrangian average of :class:`oasisx_amd.DynamicSmagorinsky`, which has a memory)."""
         if self._viscosity_model is None:
             raise RuntimeError("viscosity_assemble: the solver was built without a viscosity_model")
-        self._viscosity_model.evaluate(self, self._nut, nu)
+        if getattr(self._viscosity_model, "needs_dt", False):
+            self._viscosity_model.evaluate(self, self._nut, nu, dt=dt)
+        else:
+            self._viscosity_model.evaluate(self, self._nut, nu)
 
     def wall_units(self):
         """``(y_plus, damping)`` per cell of the last ``assemble_first`` of a model with wall damping

@@ -297,19 +297,33 @@ class DynamicSmagorinsky(_KernelModel):
         cs2_max: the upper clip of ``Cs2`` (>= 0)
         update_every: ``Cs2`` is recomputed in the first ``assemble_first`` and every n-th after it; ``nut`` is recomputed
             from the stored ``Cs2`` in every step
+
+    ``average="lagrangian"`` (Meneveau, Lund & Cabot 1996): ``Cs2 = F_LM / F_MM`` of two fields kept per
+    vertex class, the averages of ``-2 (Ld:M)_v`` and ``4 (M:M)_v`` along the path lines with an exponentially fading
+    memory: every update traces ``x_v - h u_v`` back (``h = update_every dt``, ``u_v`` the patch-mean ``u_ab``),
+    interpolates the old fields there and relaxes them towards the sources with ``eps = (h/T) / (1 + h/T)``,
+    ``T = time_scale Delta_v (F_LM F_MM)^(-1/8)`` (``ox_dynamic_lagrangian``).  Needs no homogeneous direction and has a
+    memory: the model must be given ``dt`` (``assemble_first`` hands it on), and ``save`` / ``load`` carry the fields over
+    a restart.
+
+        cs2_initial: ``F_LM = cs2_initial F_MM`` in the first update (finite, >= 0)
+        time_scale: the constant of the relaxation time ``T`` (1.5 in the paper; finite, > 0)
+        cs2_floor: ``F_LM >= cs2_floor F_MM`` after every update, so that ``T`` stays finite (in ``[0, cs2_max]``)
     """
 
     model_id = 0
     damping = None
+    AVERAGES = ("global", "local", "lagrangian")
 
     def __init__(self, average="global", axis=None, edges=None, cell_bins=None, filter_ratio=2.0, cs2_max=0.09,
-                 update_every=1, tol=None):
-        if average not in ("global", "local"):
-            raise ValueError(f'DynamicSmagorinsky: average is "global" or "local" (got {average!r})')
+                 update_every=1, tol=None, cs2_initial=0.0256, time_scale=1.5, cs2_floor=1e-24):
+        if average not in self.AVERAGES:
+            raise ValueError(f'DynamicSmagorinsky: average is "global", "local" or "lagrangian" (got {average!r})')
         if axis is not None and cell_bins is not None:
             raise ValueError("DynamicSmagorinsky: give at most one of axis= (with optional edges=) and cell_bins=")
-        if average == "local" and (axis is not None or cell_bins is not None):
-            raise ValueError('DynamicSmagorinsky: average="local" takes no bins (axis= / cell_bins= belong to "global")')
+        if average != "global" and (axis is not None or edges is not None or cell_bins is not None):
+            raise ValueError(f'DynamicSmagorinsky: average="{average}" takes no bins (axis= / edges= / cell_bins= belong to '
+                             '"global")')
         if edges is not None and axis is None:
             raise ValueError("DynamicSmagorinsky: edges= belongs to axis=")
         self.average = average
@@ -325,6 +339,13 @@ class DynamicSmagorinsky(_KernelModel):
         if int(update_every) != update_every or int(update_every) < 1:
             raise ValueError(f"DynamicSmagorinsky: update_every must be an integer >= 1 (got {update_every})")
         self.update_every = int(update_every)
+        self.cs2_initial, self.time_scale, self.cs2_floor = float(cs2_initial), float(time_scale), float(cs2_floor)
+        if not np.isfinite(self.cs2_initial) or self.cs2_initial < 0.0:
+            raise ValueError(f"DynamicSmagorinsky: cs2_initial must be finite and >= 0 (got {cs2_initial})")
+        if not np.isfinite(self.time_scale) or self.time_scale <= 0.0:
+            raise ValueError(f"DynamicSmagorinsky: time_scale must be finite and > 0 (got {time_scale})")
+        if not 0.0 <= self.cs2_floor <= self.cs2_max:
+            raise ValueError(f"DynamicSmagorinsky: cs2_floor must lie in [0, cs2_max = {self.cs2_max}] (got {cs2_floor})")
         self.edges = None
         self.n_bins = None
         self.n_evaluations = 0  # assemble_first calls seen
@@ -335,7 +356,7 @@ class DynamicSmagorinsky(_KernelModel):
     def _bins_of(self, mesh):
         """(bins in mesh cell order or None, n_bins)."""
         nc = int(mesh.num_cells)
-        if self.average == "local":
+        if self.average != "global":
             return None, 0
         if self.axis is not None:
             from .diagnostics import slab_bins
@@ -379,6 +400,8 @@ class DynamicSmagorinsky(_KernelModel):
             self._filter = PatchFilter(solver, _patches=p)
             self._lmf = torch.zeros((nc, 2), **f64)
             self._cs2 = torch.zeros(nc, **f64)
+        elif self.average == "lagrangian":
+            self._bind_lagrangian(solver)
         else:
             plan = bin_chunk_plan(torch.from_numpy(bins).to(dev), p.local_cells, nc, nb, "DynamicSmagorinsky")
             self._plan = plan
@@ -387,8 +410,84 @@ class DynamicSmagorinsky(_KernelModel):
             self._bins = torch.zeros((nb, 4), **f64)  # {sum |c| LM, sum |c| MM, Cs2 unclipped, Cs2 clipped}
         self.n_evaluations = self.n_updates = 0
 
+    @property
+    def needs_dt(self) -> bool:
+        """``viscosity_assemble`` hands ``dt`` to a model that says so: the Lagrangian average traces back over it."""
+        return self.average == "lagrangian"
+
+    def _bind_lagrangian(self, solver):
+        """The whole-mesh locator of the tracers, the master vertex of every class, ``Delta_v`` and the two field pairs."""
+        from . import geometry as G
+
+        mesh, p = solver._mesh, self._patches
+        Vi = solver._Vi[0][0]
+        dev = solver._geom.device
+        d, nv, nc = p.gdim, p.n_vertices, p.n_cells
+        f64 = dict(dtype=torch.float64, device=dev)
+        self._loc_tol = G.DEFAULT_TOL
+        self._tree = G.space_tree(Vi, self._loc_tol)
+        self._cell_inv = G.kernel_position_table(Vi)
+        per = getattr(mesh, "periodic", None)
+        coords = mesh.coords.to(dev)
+        self._periodic = [0, 0, 0]
+        self._lo, self._hi, self._period = [0.0] * 3, [0.0] * 3, [0.0] * 3
+        if per is None:
+            self._xv = coords.contiguous()
+        else:
+            vm = np.asarray(per.vertex_master)
+            free = np.nonzero(vm == np.arange(vm.shape[0]))[0]  # ascending master id: the order of the classes
+            self._xv = coords[torch.from_numpy(free).to(dev)].contiguous()
+            for k in per.axes:
+                self._periodic[k] = 1
+                self._lo[k], self._hi[k], self._period[k] = float(per.lo[k]), float(per.hi[k]), float(per.period[k])
+        if tuple(self._xv.shape) != (nv, d):
+            raise RuntimeError(f"DynamicSmagorinsky: {tuple(self._xv.shape)} master-vertex coordinates for {nv} vertex classes")
+        # the hint: the first cell of every patch, as a mesh cell id (the locator's numbering)
+        first = p.idx.to(torch.int64)[p.ptr[:-1].to(torch.int64)]
+        self._hint = p.local_cells[first].contiguous()
+        lib, st = solver._lib, _lib.current_stream()
+        adet = solver._geom[:, d * d]
+        vol = (0.5 * adet if d == 2 else adet * (1.0 / 6.0)).contiguous()  # |c| as the kernels form it from |det J|
+        vv = torch.zeros(nv, **f64)
+        _lib.check(lib.ox_patch_filter_vertices(1, nv, _lib.ptr(p.ptr), _lib.ptr(p.idx), nc, p.n_idx, _lib.ptr(vol),
+                                                _lib.ptr(vol), 1, _lib.ptr(vv), st), "ox_patch_filter_vertices")
+        self._delta_v = torch.pow(vv, 1.0 / d).contiguous()
+        self._src = torch.zeros((nv, 2), **f64)               # {(LM)_v, (MM)_v}
+        self._f = [torch.zeros((nv, 2), **f64) for _ in range(2)]  # {F_LM, F_MM}: the current pair is _f[_cur]
+        self._cur = 0
+        self._cs2v = torch.zeros(nv, **f64)
+        self._status = torch.zeros(nv, dtype=torch.int32, device=dev)
+        self._cs2 = torch.zeros(nc, **f64)
+
+    def _update_lagrangian(self, solver, vol, dt):
+        """Launches 4 to 6 of the Lagrangian update: the sources per vertex, the back-trace and relaxation, ``Cs2`` per cell."""
+        import ctypes as C
+
+        p, lib, st = self._patches, solver._lib, _lib.current_stream()
+        h = self.update_every * float(dt)
+        _lib.check(lib.ox_patch_filter_vertices(2, p.n_vertices, _lib.ptr(p.ptr), _lib.ptr(p.idx), p.n_cells, p.n_idx,
+                                                _lib.ptr(self._lm), vol, self._nr, _lib.ptr(self._src), st),
+                   "ox_patch_filter_vertices")
+        old, new = self._f[self._cur], self._f[1 - self._cur]
+        args = self.lagrangian_args(h, self.n_updates == 0, self._mom, self._nm, self._src, old, new, self._cs2v, self._status)
+        _lib.check(lib.ox_dynamic_lagrangian(C.byref(args), st), "ox_dynamic_lagrangian")
+        self._cur = 1 - self._cur
+        _lib.check(lib.ox_patch_filter_cells(1, p.gdim, p.n_cells, _lib.ptr(p.cell_verts), p.n_vertices,
+                                             _lib.ptr(self._cs2v), _lib.ptr(self._cs2), st), "ox_patch_filter_cells")
+
+    def lagrangian_args(self, h, first, u, u_stride, src, f_old, f_new, cs2v, status):
+        """The argument block of ``ox_dynamic_lagrangian`` on this model's tables, for the given device tensors."""
+        p = self._patches
+        A3, I3 = _lib.C.c_double * 3, _lib.C.c_int * 3
+        return _lib.ox_lagrangian_args(
+            self._tree._h, p.gdim, int(bool(first)), p.n_vertices, _lib.ptr(self._xv), _lib.ptr(u), int(u_stride),
+            _lib.ptr(self._hint), _lib.ptr(self._cell_inv), int(self._cell_inv.shape[0]), _lib.ptr(p.cell_verts), p.n_cells,
+            _lib.ptr(src), _lib.ptr(self._delta_v), _lib.ptr(f_old), _lib.ptr(f_new), _lib.ptr(cs2v), _lib.ptr(status),
+            float(h), self.time_scale, self.cs2_floor, self.cs2_max, self.cs2_initial, self._loc_tol,
+            I3(*self._periodic), A3(*self._lo), A3(*self._hi), A3(*self._period))
+
     # ---- per assemble_first
-    def update_coefficient(self, solver):
+    def update_coefficient(self, solver, dt=None):
         """The launches that recompute ``Cs2`` from the solver's ``u_ab``."""
         import ctypes as C
 
@@ -406,6 +505,8 @@ class DynamicSmagorinsky(_KernelModel):
             self._filter._launch(2, self._lm, self._lmf, vol=vol, vol_stride=self._nr)
             _lib.check(lib.ox_dynamic_clip(p.n_cells, _lib.ptr(self._lmf), self.cs2_max, _lib.ptr(self._cs2), st),
                        "ox_dynamic_clip")
+        elif self.average == "lagrangian":
+            self._update_lagrangian(solver, vol, dt)
         else:
             pl = self._plan
             _lib.check(lib.ox_dynamic_bin_sums(p.n_cells, _lib.ptr(self._lm), vol, self._nr, _lib.ptr(pl["order"]),
@@ -416,16 +517,20 @@ class DynamicSmagorinsky(_KernelModel):
                        "ox_dynamic_bin_coefficients")
         self.n_updates += 1
 
-    def evaluate(self, solver, nut: torch.Tensor, nu=None):
+    def evaluate(self, solver, nut: torch.Tensor, nu=None, dt=None):
         import ctypes as C
 
         if self._patches is None:
             raise RuntimeError("DynamicSmagorinsky: the model is not bound to a solver")
+        if self.average == "lagrangian":
+            if dt is None or not np.isfinite(float(dt)) or float(dt) < 0.0:
+                raise ValueError('DynamicSmagorinsky: average="lagrangian" traces the path lines back over the step: '
+                                 f"viscosity_assemble(nu, dt) with a finite dt >= 0 (got dt = {dt})")
         if self.n_evaluations % self.update_every == 0:
-            self.update_coefficient(solver)
+            self.update_coefficient(solver, dt)
         self.n_evaluations += 1
         Vi = solver._Vi[0][0]
-        if self.average == "local":
+        if self.average != "global":
             cs2, stride, n, cb = _lib.ptr(self._cs2), 1, self._patches.n_cells, None
         else:
             cs2, stride, n, cb = C.c_void_p(self._bins.data_ptr() + 8 * 3), 4, self.n_bins, _lib.ptr(self._cell_bin)
@@ -447,7 +552,7 @@ class DynamicSmagorinsky(_KernelModel):
     def coefficient_cells(self, solver=None) -> torch.Tensor:
         """``Cs2`` per cell (clipped), device tensor in the MESH's cell order."""
         self._need("coefficient_cells")
-        if self.average == "local":
+        if self.average != "global":
             ck = self._cs2
         else:
             cb = self._cell_bin.to(torch.int64)
@@ -460,15 +565,15 @@ class DynamicSmagorinsky(_KernelModel):
     def bin_coefficients(self, clipped=True) -> torch.Tensor:
         """``Cs2`` per bin (length 1 for the global average), clipped or as the ratio stands."""
         self._need("bin_coefficients")
-        if self.average == "local":
-            raise RuntimeError('DynamicSmagorinsky.bin_coefficients: average="local" has a coefficient per cell')
+        if self.average != "global":
+            raise RuntimeError(f'DynamicSmagorinsky.bin_coefficients: average="{self.average}" has a coefficient per cell')
         return self._bins[:, 3 if clipped else 2].clone()
 
     def bin_sums(self) -> torch.Tensor:
         """``(sum |c| LM, sum |c| MM)`` per bin, shape ``(n_bins, 2)``."""
         self._need("bin_sums")
-        if self.average == "local":
-            raise RuntimeError('DynamicSmagorinsky.bin_sums: average="local" has no bins')
+        if self.average != "global":
+            raise RuntimeError(f'DynamicSmagorinsky.bin_sums: average="{self.average}" has no bins')
         return self._bins[:, :2].clone()
 
     def products(self):
@@ -477,7 +582,62 @@ class DynamicSmagorinsky(_KernelModel):
         both = self._to_mesh_order(self._lm)
         return both[:, 0].contiguous(), both[:, 1].contiguous()
 
+    # ---- the Lagrangian average: its fields, and their way over a restart
+    def _need_lagrangian(self, what, updated=True):
+        if self.average != "lagrangian":
+            raise RuntimeError(f'DynamicSmagorinsky.{what}: average="{self.average}" keeps no fields along path lines')
+        if self._patches is None or (updated and self.n_updates == 0):
+            raise RuntimeError(f"DynamicSmagorinsky.{what}: no assemble_first has run with this model")
+
+    def lagrangian_fields(self):
+        """``(F_LM, F_MM)`` per vertex class (on a periodic mesh: per class of identified vertices), device tensors."""
+        self._need_lagrangian("lagrangian_fields")
+        f = self._f[self._cur]
+        return f[:, 0].contiguous(), f[:, 1].contiguous()
+
+    def vertex_coefficients(self) -> torch.Tensor:
+        """``Cs2_v = F_LM / F_MM`` per vertex class, clipped to ``[0, cs2_max]``."""
+        self._need_lagrangian("vertex_coefficients")
+        return self._cs2v.clone()
+
+    def backtrace_status(self) -> torch.Tensor:
+        """int32 per vertex class of the last update: 0 a cell was found, 1 the path line left the mesh (the vertex kept
+        its own old value), 2 a non-finite departure point or an index out of range (NaN)."""
+        self._need_lagrangian("backtrace_status")
+        return self._status.clone()
+
+    def save(self, path) -> None:
+        """The two fields, the coefficients and the counters as an ``.npz``: what a restarted run needs to go on bit for bit."""
+        self._need_lagrangian("save", updated=False)
+        f = self._f[self._cur]
+        np.savez(path, fields=f.cpu().numpy(), cs2_vertices=self._cs2v.cpu().numpy(), cs2_cells=self._cs2.cpu().numpy(),
+                 status=self._status.cpu().numpy(), n_evaluations=np.int64(self.n_evaluations),
+                 n_updates=np.int64(self.n_updates), update_every=np.int64(self.update_every))
+
+    def load(self, path) -> None:
+        """What ``save`` wrote, into this model (bound to a solver on the same mesh, with the same ``update_every``)."""
+        self._need_lagrangian("load", updated=False)
+        with np.load(path) as z:
+            f, cv, cc, st = z["fields"], z["cs2_vertices"], z["cs2_cells"], z["status"]
+            nv, nc = self._patches.n_vertices, self._patches.n_cells
+            if f.shape != (nv, 2) or cv.shape != (nv,) or cc.shape != (nc,) or st.shape != (nv,):
+                raise ValueError(f"DynamicSmagorinsky.load: saved for {f.shape[0]} vertex classes and {cc.shape[0]} cells; the "
+                                 f"solver has {nv} and {nc}")
+            if int(z["update_every"]) != self.update_every:
+                raise ValueError(f"DynamicSmagorinsky.load: saved with update_every = {int(z['update_every'])}, the model "
+                                 f"has {self.update_every}")
+            dev = self._cs2.device
+            self._f[self._cur].copy_(torch.from_numpy(np.ascontiguousarray(f)).to(dev))
+            self._cs2v.copy_(torch.from_numpy(np.ascontiguousarray(cv)).to(dev))
+            self._cs2.copy_(torch.from_numpy(np.ascontiguousarray(cc)).to(dev))
+            self._status.copy_(torch.from_numpy(np.ascontiguousarray(st)).to(dev))
+            self.n_evaluations, self.n_updates = int(z["n_evaluations"]), int(z["n_updates"])
+
     def __repr__(self):
+        if self.average == "lagrangian":
+            return (f"DynamicSmagorinsky(lagrangian, filter_ratio={self.filter_ratio}, cs2_max={self.cs2_max}, "
+                    f"update_every={self.update_every}, cs2_initial={self.cs2_initial}, time_scale={self.time_scale}, "
+                    f"cs2_floor={self.cs2_floor})")
         where = self.average if self.axis is None and self.cell_bins_arg is None else (
             f"axis={self.axis}" if self.axis is not None else "cell_bins")
         return (f"DynamicSmagorinsky({where}, filter_ratio={self.filter_ratio}, cs2_max={self.cs2_max}, "
