@@ -3,7 +3,7 @@
 
 The z-extruded Taylor-Green vortex on [-1, 1]^3 (exact Dirichlet velocity, no pressure condition) is marched twice from
 the same initial data: with the constant viscosity alone, and with ``viscosity_model=oasisx_amd.Smagorinsky(Cs)``, whose
-``nut`` per cell is evaluated from the extrapolated velocity of every step (``ox_eddy_viscosity``) and added by the fused
+``nut`` per cell is evaluated from the extrapolated velocity of every step (``ox_cell_viscosity``) and added by the fused
 assembly kernel.  Per step the kinetic energy (1/2) u^T M u and the minimum / mean / maximum of ``nut`` are printed: the
 model takes energy out of the resolved field, so its run ends below the other.
 

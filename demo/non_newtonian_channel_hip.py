@@ -3,7 +3,7 @@
 
 The channel [0, 4] x [-1, 1], P2-P1, driven by a constant body force (G, 0) between no-slip walls.  The viscosity is
 ``oasisx_amd.PowerLaw(k, n, nu_min, nu_max)``: nu(gd) = k gd^(n - 1) of the shear rate gd = sqrt(2 S:S), evaluated per cell
-from the extrapolated velocity of every step (``ox_viscosity_law``) and added by the fused assembly kernel; the solver
+from the extrapolated velocity of every step (``ox_cell_viscosity``) and added by the fused assembly kernel; the solver
 runs at nu = ``base_viscosity`` = nu_min.  With p = 0 the steady solution is
 
     u(y) = n / (n + 1) (G / k)^(1 / n) (1 - |y|^((n + 1) / n)),        v = 0

@@ -473,7 +473,7 @@ int ox_assemble_load_vector(const ox_cells *cells, const ox_adj *adj, int64_t n_
  * where u1 is also the initial guess of the tentative-velocity solve (fracstep.py:521 with
  * -ksp_initial_guess_nonzero) it is that solve's first mat-vec (ox_ksp_options.ax0), once the rows ox_zero_rows_au
  * turns into identity rows have been set to u1.
- * nut (device [n_cells], kernel cell order: ox_eddy_viscosity / ox_viscosity_law): C is replaced by
+ * nut (device [n_cells], kernel cell order: ox_cell_viscosity): C is replaced by
  * C + sum_e nut[e] K_e (K_e: the stiffness matrix of cell e), i.e. A = M/dt + C/2 + (nu K + K_nut)/2 and b_first to
  * match: the Laplacian form div(nut grad u) of a viscosity that varies per cell.  Same launch forms, same epilogue;
  * nut = 0 everywhere gives the bits of nut == NULL. */
@@ -488,20 +488,30 @@ typedef struct {
 int ox_assemble_first(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
                       const ox_sell *K, const ox_first_args *args, int row_blocks, void *stream);
 
-/* ---- eddy-viscosity models: a viscosity per cell for ox_first_args.nut ---- */
-/* nut[e], e in kernel cell order (the order of cells->geom and cell_dofs), from grad uab at the cell's centroid:
- * model 0, Smagorinsky: (coefficient Delta)^2 sqrt(2 S:S); model 1, WALE (gdim = 3 only):
- * (coefficient Delta)^2 (Sd:Sd)^(3/2) / ((S:S)^(5/2) + (Sd:Sd)^(5/4)), 0 where the denominator is 0; S = sym(grad uab),
- * Sd = sym(g g) - tr(g g)/3 I with g = grad uab, Delta = |cell|^(1/gdim).  uab interleaved [n_u][gdim], cell_dofs
- * [n_cells][nd] of the velocity component space of `degree` (1, 2, 3).  One lane per cell. */
-int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
-                      double coefficient, double *nut, void *stream);
-/* The Smagorinsky model with van Driest wall damping, arguments as ox_eddy_viscosity (model 0 only):
- *   nut[e] = (coefficient Delta D)^2 sqrt(2 S:S),  D = 1 - exp(-y+ / a_plus),  y+ = dist[e] u_tau / nu
- * dist[e], nearest[e] (device, kernel cell order): the wall distance of the cell's centroid and the position of its
- * nearest wall facet (ox_walldist_query); u_tau = sqrt(|wss[nearest[e]]|) with wss (device [n_facets][gdim]) the kinematic
- * wall shear of those facets (ox_wall_stress), or the constant u_tau where wss is NULL.  nearest[e] outside
- * [0, n_facets) writes NaN and reads nothing; wss = 0 gives D = 0 and nut = 0. */
+/* ---- a viscosity per cell for ox_first_args.nut: eddy-viscosity models and generalised-Newtonian laws ---- */
+/* nut[e], e in kernel cell order (the order of cells->geom and cell_dofs), from g = grad uab at the cell's centroid:
+ * S = sym(g), gd = sqrt(2 S:S), Delta = |cell|^(1/gdim).  uab interleaved [n_u][gdim], cell_dofs [n_cells][nd] of the
+ * velocity component space of `degree` (1, 2, 3).  One launch, one lane per cell.
+ *   model 0, Smagorinsky: nut = C Delta^2 gd with
+ *     C = coefficient^2, or
+ *     C = (coefficient D)^2 with `damping` (van Driest): D = 1 - exp(-y+ / a_plus),
+ *       y+ = dist[e] u_tau / nu.  dist[e], nearest[e] (device, kernel cell order): the wall distance of the cell's centroid
+ *       and the position of its nearest wall facet (ox_walldist_query); u_tau = sqrt(|wss[nearest[e]]|) with wss (device
+ *       [n_facets][gdim]) the kinematic wall shear of those facets (ox_wall_stress), or the constant u_tau where wss is
+ *       NULL.  nearest[e] outside [0, n_facets) writes NaN and reads nothing; wss = 0 gives D = 0 and nut = 0.  Or
+ *     C = cs2[k cs2_stride] with `cs2` (device; the dynamic model): k = cell_bin[e] (cell_bin given;
+ *       k < 0: C = 0; k >= n_coef: NaN) or k = e (cell_bin NULL, n_coef = n_cells).
+ *   model 1, WALE (gdim = 3 only): (coefficient Delta)^2 (Sd:Sd)^(3/2) / ((S:S)^(5/2) + (Sd:Sd)^(5/4)), 0 where the
+ *     denominator is 0; Sd = sym(g g) - tr(g g)/3 I.
+ *   models 2-4, the generalised-Newtonian laws: nut = max(nu(gd) - base, 0); the caller runs the
+ *     step at nu = base.  params: HOST array of n_params doubles (5, 4, 4), finite.
+ *     2, Carreau-Yasuda, params = {nu0, nu_inf, lam, n, a}: nu = nu_inf + (nu0 - nu_inf) (1 + (lam gd)^a)^((n - 1)/a),
+ *        base = min(nu0, nu_inf);  3, Cross, params = {nu0, nu_inf, lam, m}: nu = nu_inf + (nu0 - nu_inf) / (1 + (lam gd)^m),
+ *        same base;  4, power law, params = {k, n, nu_min, nu_max}: nu = min(max(k gd^(n - 1), nu_min), nu_max),
+ *        base = nu_min; at gd == 0: nu_max for n < 1, nu_min for n > 1, the clipped k for n == 1.
+ * A field the chosen form does not read must be NULL or 0, or the call is refused (on the host, nothing is written):
+ * coefficient with cs2 or a law, params with models 0 and 1, damping or cs2 with models 1-4, damping together with cs2 (not
+ * instantiated), cs2_stride / n_coef / cell_bin without cs2. */
 typedef struct {
   const double *dist;      /* [n_cells]                                       */
   const int32_t *nearest;  /* [n_cells]                                       */
@@ -510,8 +520,19 @@ typedef struct {
   double nu, a_plus;       /* > 0                                             */
   int64_t n_facets;
 } ox_vandriest;
-int ox_eddy_viscosity_damped(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
-                             double coefficient, const ox_vandriest *vd, double *nut, void *stream);
+typedef struct {
+  int model, degree;            /* 0 Smagorinsky, 1 WALE, 2 Carreau-Yasuda, 3 Cross, 4 power law                    */
+  const int32_t *cell_dofs;     /* device [n_cells][nd]                                                            */
+  const double *uab;            /* device, interleaved [n_u][gdim]                                                 */
+  double *nut;                  /* device [n_cells]                                                                */
+  double coefficient;           /* models 0, 1 (Cs, Cw) where cs2 is NULL; >= 0, squared on the host               */
+  const double *params; int n_params;  /* models 2-4: HOST array                                                   */
+  const ox_vandriest *damping;  /* model 0, optional (host struct of device tables)                                */
+  const double *cs2;            /* model 0, optional: device table of coefficients                                 */
+  int64_t cs2_stride, n_coef;   /* >= 1; 1 .. INT32_MAX                                                            */
+  const int32_t *cell_bin;      /* device [n_cells] or NULL                                                        */
+} ox_viscosity_args;
+int ox_cell_viscosity(const ox_cells *cells, const ox_viscosity_args *args, void *stream);
 /* ---- the dynamic Smagorinsky model: the Germano-Lilly procedure ----
  * NS = gdim (gdim + 1) / 2.  All arrays are device arrays in kernel cell order / vertex-class order; every launch has one
  * summation order and no atomics, so equal inputs give equal bits.  Counts must fit int32 (indices are int32).
@@ -520,7 +541,7 @@ int ox_eddy_viscosity_damped(int model, int degree, const ox_cells *cells, const
  * cell CSR; cell_verts [n_cells][gdim + 1]: the vertex classes of a cell.  An index out of range writes NaN and reads
  * nothing.
  *   ox_dynamic_cells:    rec[c][gdim + NS + 2] = {u at the centroid, upper triangle of S = sym(grad uab) row by row,
- *                        D s, |c|}, D = |c|^(2/gdim), s = sqrt(2 S:S); arguments as ox_eddy_viscosity
+ *                        D s, |c|}, D = |c|^(2/gdim), s = sqrt(2 S:S); cell_dofs, uab as for ox_cell_viscosity
  *   ox_dynamic_vertices: mom[v][gdim + 3 NS] = {u, u u^T, S, D s S} filtered to the vertex (upper triangles)
  *   ox_dynamic_products: lm[c][2] = {Ld:M, M:M}, L = (u u^T)^ - u^ u^^T, Ld = L - tr L / gdim I,
  *                        M = filter_ratio^2 D |S^| S^ - (D s S)^, |S^| = sqrt(2 S^:S^); filter_ratio > 1
@@ -531,9 +552,7 @@ int ox_eddy_viscosity_damped(int model, int degree, const ox_cells *cells, const
  *   ox_patch_filter_vertices / ox_patch_filter_cells: the two halves of the filter for q [n_cells][k], k = 1 or 2;
  *                        n_idx = ptr[n_vertices]
  *   ox_dynamic_clip:     cs2[i] = the clipped -(1/2) pairs[i][0] / pairs[i][1], as above
- *   ox_eddy_viscosity_cellcoef: nut[c] = C D s (the Smagorinsky branch of ox_eddy_viscosity), C = cs2[k cs2_stride] with
- *                        k = cell_bin[c] (cell_bin given; k < 0: C = 0; k >= n_coef: NaN) or k = c (cell_bin NULL,
- *                        n_coef = n_cells) */
+ * nut then comes from ox_cell_viscosity with cs2 = the clipped coefficients, per cell or per bin. */
 int ox_dynamic_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab, double *rec,
                      void *stream);
 int ox_dynamic_vertices(int gdim, int64_t n_vertices, const int32_t *ptr, const int32_t *idx, int64_t n_cells,
@@ -550,18 +569,7 @@ int ox_patch_filter_vertices(int k, int64_t n_vertices, const int32_t *ptr, cons
 int ox_patch_filter_cells(int k, int gdim, int64_t n_cells, const int32_t *cell_verts, int64_t n_vertices, const double *qv,
                           double *qf, void *stream);
 int ox_dynamic_clip(int64_t n, const double *pairs, double cs2_max, double *cs2, void *stream);
-int ox_eddy_viscosity_cellcoef(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
-                               const double *cs2, int64_t cs2_stride, int64_t n_coef, const int32_t *cell_bin, double *nut,
-                               void *stream);
-/* ---- generalised-Newtonian laws and the full stress form ---- */
-/* nut[e] = max(nu(gd_e) - base, 0), gd = sqrt(2 S:S) with S = sym(grad uab) at the cell's centroid (the quantity of
- * ox_eddy_viscosity's Smagorinsky model), arguments as there.  law 2, Carreau-Yasuda, params = {nu0, nu_inf, lam, n, a}:
- * nu = nu_inf + (nu0 - nu_inf) (1 + (lam gd)^a)^((n - 1)/a), base = min(nu0, nu_inf);  law 3, Cross, params = {nu0, nu_inf,
- * lam, m}: nu = nu_inf + (nu0 - nu_inf) / (1 + (lam gd)^m), same base;  law 4, power law, params = {k, n, nu_min, nu_max}:
- * nu = min(max(k gd^(n - 1), nu_min), nu_max), base = nu_min; at gd == 0: nu_max for n < 1, nu_min for n > 1, the clipped
- * k for n == 1.  params: HOST array of n_params doubles (5, 4, 4); the caller runs the step at nu = base. */
-int ox_viscosity_law(int law, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
-                     const double *params, int n_params, double *nut, void *stream);
+/* ---- the full stress form of a per-cell viscosity ---- */
 /* The transposed term of div(nut (grad u + grad u^T)), explicit in uab, added to b in place:
  * b[r][i] += scale * sum_e nut[e] int_e sum_j d(uab)_j/dx_i d(phi_r)/dx_j, rows r < n_rows of the velocity component space
  * of `degree` (1, 2, 3; adj and cell_dofs of that space), b and uab interleaved [n][gdim], nut [n_cells] in kernel cell

@@ -183,6 +183,24 @@ class ox_vandriest(C.Structure):
     ]
 
 
+class ox_viscosity_args(C.Structure):
+    _fields_ = [
+        ("model", C.c_int),
+        ("degree", C.c_int),
+        ("cell_dofs", C.c_void_p),
+        ("uab", C.c_void_p),
+        ("nut", C.c_void_p),
+        ("coefficient", C.c_double),
+        ("params", C.POINTER(C.c_double)),
+        ("n_params", C.c_int),
+        ("damping", C.POINTER(ox_vandriest)),
+        ("cs2", C.c_void_p),
+        ("cs2_stride", C.c_int64),
+        ("n_coef", C.c_int64),
+        ("cell_bin", C.c_void_p),
+    ]
+
+
 class ox_mg_level(C.Structure):
     _fields_ = [
         ("A", ox_sell),
@@ -356,8 +374,7 @@ SIGNATURES = {
     "ox_assemble_load_vector": (_I, [C.POINTER(ox_cells), C.POINTER(ox_adj), _L, _I, _I, _P, _P, _P, _P]),
     "ox_assemble_first": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), C.POINTER(ox_sell),
                                C.POINTER(ox_sell), C.POINTER(ox_first_args), _I, _P]),
-    "ox_eddy_viscosity": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, _P, _P]),
-    "ox_eddy_viscosity_damped": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _D, C.POINTER(ox_vandriest), _P, _P]),
+    "ox_cell_viscosity": (_I, [C.POINTER(ox_cells), C.POINTER(ox_viscosity_args), _P]),
     "ox_dynamic_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _P]),
     "ox_dynamic_vertices": (_I, [_I, _L, _P, _P, _L, _P, _P, _P]),
     "ox_dynamic_products": (_I, [_I, _L, _P, _L, _P, _P, _D, _P, _P]),
@@ -366,8 +383,6 @@ SIGNATURES = {
     "ox_patch_filter_vertices": (_I, [_I, _L, _P, _P, _L, _L, _P, _P, _L, _P, _P]),
     "ox_patch_filter_cells": (_I, [_I, _I, _L, _P, _L, _P, _P, _P]),
     "ox_dynamic_clip": (_I, [_L, _P, _D, _P, _P]),
-    "ox_eddy_viscosity_cellcoef": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _L, _L, _P, _P, _P]),
-    "ox_viscosity_law": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, C.POINTER(_D), _I, _P, _P]),
     "ox_assemble_stress_transpose": (_I, [_I, C.POINTER(ox_cells), _P, C.POINTER(ox_adj), _L, _P, _P, _D, _P, _P]),
     "ox_flow_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _D, _D, _P, _P, _P, _P]),
     "ox_flow_reduce": (_I, [_L, _P, _P, _L, _L, _P]),

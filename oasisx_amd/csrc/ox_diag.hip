@@ -1,12 +1,12 @@
 // Flow diagnostics and running statistics.  Nothing here writes a solver field or touches a matrix.
 //
-// ox_flow_cells: one lane per cell, in kernel cell order -- the streams of k_eddy_viscosity (the cell's dof list, its
+// ox_flow_cells: one lane per cell, in kernel cell order -- the streams of k_cell_viscosity (the cell's dof list, its
 // geometry record, the gathered ND x GDIM coefficients) plus a quadrature loop.  With g = grad u (g[d][k] = du_d/dx_k),
 // S = sym g, W = skew g, omega = curl u:
 //
 //   cell integrals (exact for the element)                       centroid quantities (fields, optional)
 //     vol     = |cell| = |det J| / gdim!                           cfl   = dt max_a |u(x_c) . grad lambda_a|
-//     ke      = 1/2 int |u|^2      (mass table, degree 2 DEG)      shear = sqrt(2 S:S)       (gd of ox_viscosity_law)
+//     ke      = 1/2 int |u|^2      (mass table, degree 2 DEG)      shear = sqrt(2 S:S)       (gd of the viscosity laws)
 //     strain2 = int 2 S:S          (rule of degree 2 (DEG - 1))    divc  = tr g
 //     diss    = (nu + nut_c) strain2                               q     = 1/2 (W:W - S:S)
 //     ens     = 1/2 int |omega|^2                                  omega: g[1][0] - g[0][1]  |  the three of curl u
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
     ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
     double uc[ND][GDIM];
     ox_gather<ND, GDIM>(dd, u, uc);
-    const double vol = GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0);
+    const double vol = ox_cell_volume<GDIM>(adet);
 
     // ---- ke = 1/2 |cell| sum_d u_d^T M u_d, M the mean mass matrix
     double k2 = 0.0;
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void k_flow_cells(ox_cells cells, const int32_
       for (int i = 0; i < 7; ++i) cint[(size_t)e * 7 + i] = v[i];
     }
 
-    // ---- the centroid: grad u as k_eddy_viscosity forms it, u(x_c) for the CFL number
+    // ---- the centroid: grad u as k_cell_viscosity forms it, u(x_c) for the CFL number
     double t[GDIM][GDIM + 1] = {}, ucen[GDIM] = {};
     ox_contract<GDIM, ND>(uc, ox_dphic<GDIM, DEG>(), t);
 #pragma unroll
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(256) void k_profile_cells(ox_cells cells, const int
 #pragma unroll
       for (int i = 0; i < ND; ++i) q[i][k] -= sh;
     }
-    const double vol = GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0);
+    const double vol = ox_cell_volume<GDIM>(adet);
     v[0] = vol;
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {

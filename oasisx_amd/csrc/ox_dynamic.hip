@@ -1,8 +1,8 @@
 // The dynamic Smagorinsky model: the Germano-Lilly procedure on a simplicial mesh.
 //
-// Per cell c (kernel cell order), from u_ab as k_eddy_viscosity reads it: u_c, g_c at the centroid, S_c = sym g_c,
-// s_c = sqrt(2 S_c:S_c), D_c = |c|^(2/gdim), |c| = |det J| / gdim!.  The test filter of a per-cell quantity q is the
-// vertex-patch top hat
+// Per cell c (kernel cell order), from u_ab as the nut kernel (ox_viscosity.hip) reads it: u_c, g_c at the centroid,
+// S_c = sym g_c, s_c = sqrt(2 S_c:S_c), D_c = |c|^(2/gdim), |c| = |det J| / gdim!.  The test filter of a per-cell
+// quantity q is the vertex-patch top hat
 //   q_v  = sum_{c in patch(v)} |c| q_c / sum_{c in patch(v)} |c|       (cells in ascending kernel cell id)
 //   q^_c = (1/(gdim+1)) sum_a q_{v_a(c)}                               (local vertex order)
 // over vertex CLASSES (a periodic mesh's patches wrap around the seam).  With r = filter_ratio
@@ -20,7 +20,8 @@
 //                         then one wave per bin: bins[b] = {sum |c| LM, sum |c| MM, Cs2 unclipped, Cs2 clipped}
 //   ox_patch_filter_vertices / ox_patch_filter_cells    the test filter of K = 1, 2 fields (the local average; PatchFilter)
 //   ox_dynamic_clip       cs2[c]  = clip(-(1/2) a_c / b_c) of a pair field
-//   ox_eddy_viscosity_cellcoef   nut_c = Cs2 D_c s_c with Cs2 read per cell or through the cell's bin
+// and then ox_cell_viscosity with the table of Cs2 (ox_viscosity.hip): nut_c = Cs2 D_c s_c, Cs2 read per cell or through
+// the cell's bin.
 // The vertex pass is lane-per-vertex: a patch holds at most a few tens of cells (24 on the Kuhn lattice), every lane keeps
 // its NM running sums in registers and adds its cells in ascending order; a sub-wave per vertex would need a cross-lane
 // sum of NM values per vertex and another summation order.
@@ -41,16 +42,6 @@ __host__ __device__ constexpr const auto &ox_phic() {
 }
 
 __device__ __forceinline__ double dyn_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// Delta^2 = |c|^(2/gdim) from |c|
-template <int GDIM>
-__device__ __forceinline__ double dyn_delta2(double vol) {
-  if constexpr (GDIM == 2) return vol;
-  else {
-    const double h = cbrt(vol);
-    return h * h;
-  }
-}
 
 // -(1/2) lm / mm clipped to [0, cmax]; 0 where mm is not positive; a NaN in either stays a NaN
 __device__ __forceinline__ double dyn_ratio(double lm, double mm) { return -0.5 * lm / mm; }
@@ -74,24 +65,17 @@ __device__ __forceinline__ double dyn_sym_dot(const double (&a)[dyn_ns(GDIM)], c
   return s;
 }
 
-// ---- 1. the cell pass: k_eddy_viscosity's prologue, plus u at the centroid
+// ---- 1. the cell pass: the centroid prologue of the nut kernel (ox_element.h), plus u at the centroid
 template <int GDIM, int DEG>
 __global__ __launch_bounds__(256) void k_dyn_cells(ox_cells cells, const int32_t *__restrict__ cell_dofs,
                                                    const double *__restrict__ uab, double *__restrict__ rec) {
   constexpr int ND = ox_nd(GDIM, DEG), NS = dyn_ns(GDIM), NR = dyn_nr(GDIM);
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= cells.n_cells) return;
-  int32_t dd[ND];
-  ox_load_dofs<ND>(cell_dofs, e, dd);
-  double G[GDIM + 1][GDIM], adet;
-  ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
-  double uc[ND][GDIM];
-  ox_gather<ND, GDIM>(dd, uab, uc);
-  double t[GDIM][GDIM + 1] = {}, g[GDIM][GDIM];
-  ox_contract<GDIM, ND>(uc, ox_dphic<GDIM, DEG>(), t);
-  ox_grad_from_t<GDIM>(t, G, g);
+  double uc[ND][GDIM], g[GDIM][GDIM], adet;
+  ox_centroid_grad<GDIM, DEG>(cells, cell_dofs, uab, e, g, uc, adet);
   const double ss = ox_sym_sq<GDIM>(g);
-  const double vol = GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0);
+  const double vol = ox_cell_volume<GDIM>(adet);
   double *__restrict__ r = rec + (size_t)e * NR;
 #pragma unroll
   for (int d = 0; d < GDIM; ++d) {
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(256) void k_dyn_cells(ox_cells cells, const int32_t
   for (int i = 0; i < GDIM; ++i)
 #pragma unroll
     for (int j = i; j < GDIM; ++j, ++m) r[GDIM + m] = 0.5 * (g[i][j] + g[j][i]);
-  r[GDIM + NS] = dyn_delta2<GDIM>(vol) * sqrt(2.0 * ss);
+  r[GDIM + NS] = ox_delta2_of_volume<GDIM>(vol) * sqrt(2.0 * ss);
   r[GDIM + NS + 1] = vol;
 }
 
@@ -192,7 +176,7 @@ __global__ __launch_bounds__(256) void k_dyn_products(int64_t n_cells, const int
     lm[2 * e] = lm[2 * e + 1] = dyn_nan();
     return;
   }
-  const double d2 = dyn_delta2<GDIM>(rec[(size_t)e * NR + NR - 1]);
+  const double d2 = ox_delta2_of_volume<GDIM>(rec[(size_t)e * NR + NR - 1]);
   double L[NS], S[NS], M[NS];
   int m = 0;
   double tr = 0.0;
@@ -309,35 +293,6 @@ __global__ __launch_bounds__(256) void k_dyn_clip(int64_t n, const double *__res
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
   cs2[e] = dyn_clip(pairs[2 * e], pairs[2 * e + 1], cmax);
-}
-
-// ---- 5. nut = Cs2 D s: the Smagorinsky branch of k_eddy_viscosity with the coefficient read per cell or per bin
-template <int GDIM, int DEG>
-__global__ __launch_bounds__(256) void k_eddy_viscosity_cellcoef(ox_cells cells, const int32_t *__restrict__ cell_dofs,
-                                                                 const double *__restrict__ uab,
-                                                                 const double *__restrict__ cs2, int64_t cs2_stride,
-                                                                 int64_t n_coef, const int32_t *__restrict__ cell_bin,
-                                                                 double *__restrict__ nut) {
-  constexpr int ND = ox_nd(GDIM, DEG);
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= cells.n_cells) return;
-  int32_t dd[ND];
-  ox_load_dofs<ND>(cell_dofs, e, dd);
-  double G[GDIM + 1][GDIM], adet;
-  ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
-  double uc[ND][GDIM];
-  ox_gather<ND, GDIM>(dd, uab, uc);
-  double t[GDIM][GDIM + 1] = {}, g[GDIM][GDIM];
-  ox_contract<GDIM, ND>(uc, ox_dphic<GDIM, DEG>(), t);
-  ox_grad_from_t<GDIM>(t, G, g);
-  const double ss = ox_sym_sq<GDIM>(g);
-  const double vol = GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0);
-  const int64_t k = cell_bin ? (int64_t)cell_bin[e] : e;
-  double c;
-  if (k < 0) c = 0.0;  // a cell outside every bin
-  else if (k >= n_coef) c = dyn_nan();
-  else c = cs2[(size_t)k * cs2_stride];
-  nut[e] = c * dyn_delta2<GDIM>(vol) * sqrt(2.0 * ss);
 }
 
 static inline int64_t dyn_blocks(int64_t n) { return (n + 255) / 256; }
@@ -489,30 +444,4 @@ extern "C" int ox_dynamic_clip(int64_t n, const double *pairs, double cs2_max, d
   if (ox_prof_on) ox_prof_stop(st);
   OX_LAUNCH_CHECK();
   return 0;
-}
-
-extern "C" int ox_eddy_viscosity_cellcoef(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
-                                          const double *cs2, int64_t cs2_stride, int64_t n_coef, const int32_t *cell_bin,
-                                          double *nut, void *stream) {
-  if (!cells || !cell_dofs || !uab || !cs2 || !nut || !cells->geom) OX_FAIL("ox_eddy_viscosity_cellcoef: null argument");
-  if (cs2_stride < 1) OX_FAIL("ox_eddy_viscosity_cellcoef: cs2_stride=%lld", (long long)cs2_stride);
-  OX_DYN_COUNT("ox_eddy_viscosity_cellcoef", "n_coef", n_coef);
-  if (!cell_bin && n_coef != cells->n_cells)
-    OX_FAIL("ox_eddy_viscosity_cellcoef: %lld coefficients for %lld cells", (long long)n_coef, (long long)cells->n_cells);
-  const int64_t nblk = ox_cell_blocks("ox_eddy_viscosity_cellcoef", cells);
-  if (nblk <= 0) return (int)nblk;
-  hipStream_t st = ox_stream(stream);
-  const int g = cells->gdim;
-#define OX_CC_CASE(GD, DG)                                                                                              \
-  if (g == GD && degree == DG) {                                                                                        \
-    if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY_CELLCOEF, st, cells->n_cells);                                  \
-    hipLaunchKernelGGL((k_eddy_viscosity_cellcoef<GD, DG>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, cs2, \
-                       cs2_stride, n_coef, cell_bin, nut);                                                              \
-    if (ox_prof_on) ox_prof_stop(st);                                                                                   \
-    OX_LAUNCH_CHECK();                                                                                                  \
-    return 0;                                                                                                           \
-  }
-  OX_FOR_GDIM_DEG(OX_CC_CASE)
-#undef OX_CC_CASE
-  OX_FAIL("ox_eddy_viscosity_cellcoef: unsupported gdim=%d degree=%d", g, degree);
 }

@@ -6,6 +6,7 @@
 #include "fe_tables_f.h"
 #include "fe_tables_o.h"
 #include "ox_kernels.h"
+#include <cmath>
 #include <type_traits>
 
 // dofs of the Lagrange element of degree 1, 2, 3 on a simplex, and doubles of a cell's geometry record
@@ -120,6 +121,35 @@ __device__ __forceinline__ double ox_sym_sq(const double (&g)[GDIM][GDIM]) {
     }
   return ss;
 }
+
+// The centroid prologue of the nut kernel and ox_dynamic_cells: round 1 the cell's dofs and geometry (both indexed by e),
+// round 2 the coefficient gathers; uc[i][d] = u_ab at the cell's dofs, g[d][k] = d(u_ab)_d / dx_k, adet = |det J|
+template <int GDIM, int DEG>
+__device__ __forceinline__ void ox_centroid_grad(const ox_cells &cells, const int32_t *__restrict__ cell_dofs,
+                                                 const double *__restrict__ uab, int64_t e, double (&g)[GDIM][GDIM],
+                                                 double (&uc)[ox_nd(GDIM, DEG)][GDIM], double &adet) {
+  constexpr int ND = ox_nd(GDIM, DEG);
+  int32_t dd[ND];
+  ox_load_dofs<ND>(cell_dofs, e, dd);
+  double G[GDIM + 1][GDIM];
+  ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
+  ox_gather<ND, GDIM>(dd, uab, uc);
+  double t[GDIM][GDIM + 1] = {};
+  ox_contract<GDIM, ND>(uc, ox_dphic<GDIM, DEG>(), t);
+  ox_grad_from_t<GDIM>(t, G, g);
+}
+
+// |cell| = |det J| / gdim! and Delta^2 = |cell|^(2/gdim), from the volume or from |det J|
+template <int GDIM>
+__device__ __forceinline__ double ox_cell_volume(double adet) { return GDIM == 2 ? 0.5 * adet : adet * (1.0 / 6.0); }
+template <int GDIM>
+__device__ __forceinline__ double ox_delta2_of_volume(double vol) {
+  if constexpr (GDIM == 2) return vol;
+  const double h = cbrt(vol);
+  return h * h;
+}
+template <int GDIM>
+__device__ __forceinline__ double ox_delta2(double adet) { return ox_delta2_of_volume<GDIM>(ox_cell_volume<GDIM>(adet)); }
 
 // The facet opposite local vertex a, Ga = grad lambda_a: outward unit normal n = -Ga / |Ga| and measure
 // |det J| |Ga| / (GDIM - 1)!

@@ -136,7 +136,7 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_RECT_V2S 141
 #define OX_TAG_HALO 150       // one halo exchange (key = components); includes waiting for the peers
 #define OX_TAG_SYNC_POINT 151 // one distributed Krylov synchronisation point (reduce + all-reduce + logic)
-#define OX_TAG_EDDY_VISCOSITY 160  // ox_eddy_viscosity (key = cells)
+#define OX_TAG_EDDY_VISCOSITY 160  // ox_cell_viscosity but for its table form (key = cells)
 #define OX_TAG_STRESS_TRANSPOSE 161 // ox_assemble_stress_transpose
 #define OX_TAG_FLOW_CELLS 162       // ox_flow_cells (key = cells)
 #define OX_TAG_FLOW_REDUCE 163      // ox_flow_reduce (key = partial rows)
@@ -157,7 +157,7 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_DYNAMIC_BIN_SUMS 203 // ox_dynamic_bin_sums (key = chunks)
 #define OX_TAG_DYNAMIC_BIN_COEF 204 // ox_dynamic_bin_coefficients (key = bins), ox_dynamic_clip (key = entries)
 #define OX_TAG_PATCH_FILTER 205     // ox_patch_filter_vertices (key = vertices), ox_patch_filter_cells (key = cells)
-#define OX_TAG_EDDY_VISCOSITY_CELLCOEF 206 // ox_eddy_viscosity_cellcoef (key = cells)
+#define OX_TAG_EDDY_VISCOSITY_CELLCOEF 206 // ox_cell_viscosity with a table of Cs2 (key = cells)
 #define OX_TAG_DYNAMIC_LAGRANGIAN 207 // ox_dynamic_lagrangian (key = vertices)
 extern bool ox_prof_on;
 void ox_prof_start(int tag, hipStream_t st, long long key = 0);

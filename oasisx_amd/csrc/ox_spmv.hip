@@ -8,7 +8,7 @@
 
 thread_local char ox_err_buf[512] = "";
 
-extern "C" int ox_version(void) { return 101; }
+extern "C" int ox_version(void) { return 102; }
 extern "C" const char *ox_last_error(void) { return ox_err_buf; }
 extern "C" int ox_sell_kv(void) { return OX_KV; }
 

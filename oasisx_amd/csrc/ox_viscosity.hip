@@ -1,21 +1,22 @@
-// Eddy viscosity per cell: nut[e] from grad u_ab at the cell's centroid, for the fused
-// assemble_first with a per-cell viscosity (ox_assemble_first with ox_first_args.nut).
+// Viscosity per cell (DESIGN.md sections 14, 16, 24, 26, 28): nut[e] from grad u_ab at the cell's centroid for
+// ox_assemble_first with ox_first_args.nut.  ONE kernel template, ONE entry point; the forms differ in one factor.
 //
 //   g[d][k] = d(u_ab)_d / dx_k = sum_i u_ab[dof_i][d] sum_b dphi_i/dlambda_b (centroid) G[b][k]
 //   S       = (g + g^T)/2,   Delta^2 = |cell|^(2/gdim),  |cell| = |det J| / gdim!
-//   Smagorinsky:  nut = Cs^2 Delta^2 sqrt(2 S:S)
+//   Smagorinsky:  nut = C Delta^2 sqrt(2 S:S),  C = Cs^2 | Cs^2 D^2 (van Driest) | cs2[k] (a table, per cell or per bin)
 //   WALE (3-D):   Sd  = sym(g g) - tr(g g)/3 I,  x = Sd:Sd,  y = S:S
 //                 nut = Cw^2 Delta^2 x sqrt(x) / (y^2 sqrt(y) + x sqrt(sqrt(x))),  0 where the denominator is 0
 //
-// Generalised-Newtonian laws (DESIGN.md section 16), gd = sqrt(2 S:S), nut = max(nu(gd) - base, 0):
+// Generalised-Newtonian laws, gd = sqrt(2 S:S), nut = max(nu(gd) - base, 0):
 //   Carreau-Yasuda:  nu = nu_inf + (nu0 - nu_inf) (1 + (lam gd)^a)^((n - 1)/a),  base = min(nu0, nu_inf)
 //   Cross:           nu = nu_inf + (nu0 - nu_inf) / (1 + (lam gd)^m),            base = min(nu0, nu_inf)
 //   power law:       nu = min(max(k gd^(n - 1), nu_min), nu_max),                base = nu_min
 //                    (gd == 0: nu_max for n < 1, nu_min for n > 1, the clipped k for n == 1 -- no 0^negative)
 //
 // One lane per cell, in kernel cell order: the cell's dof list (ND x 4 B) and geometry record (GS x 8 B) are streamed,
-// the ND x GDIM coefficients are gathered, 8 B are written.  The centroid derivatives are compile-time constants
-// (fe_tables_c.h): identically-zero entries cost nothing.  No atomics, no LDS; every sum has a fixed order.
+// the ND x GDIM coefficients are gathered, 8 B are written (damped: 12 B more streamed, dist and nearest, and gdim doubles
+// of wss gathered; table: 8 or 12 B more).  The centroid derivatives are compile-time constants (fe_tables_c.h):
+// identically-zero entries cost nothing.  No atomics, no LDS; every sum has a fixed order.
 #include "ox_element.h"
 #include <cmath>
 
@@ -27,51 +28,51 @@ namespace {
 #define OX_NUT_CROSS 3
 #define OX_NUT_POWER_LAW 4
 
-// The parameters of a generalised-Newtonian law, by value in the kernel arguments (the eddy-viscosity models keep their
-// one double).  Carreau-Yasuda: c0 = nu_inf, c1 = nu0 - nu_inf, c2 = lam, c3 = a, c4 = (n - 1)/a;  Cross: c0 = nu_inf,
-// c1 = nu0 - nu_inf, c2 = lam, c3 = m;  power law: c0 = k, c1 = n - 1, c2 = nu_min, c3 = nu_max.
+// FORM, where the Smagorinsky factor comes from: Cs^2 alone, Cs^2 with van Driest damping, a table of Cs2
+#define OX_NUT_PLAIN 0
+#define OX_NUT_DAMPED 1
+#define OX_NUT_TABLE 2
+
+// A law's parameters, by value in the kernel arguments.  Carreau-Yasuda: c0 = nu_inf, c1 = nu0 - nu_inf, c2 = lam, c3 = a,
+// c4 = (n - 1)/a;  Cross: the same c0, c1, c2 and c3 = m;  power law: c0 = k, c1 = n - 1, c2 = nu_min, c3 = nu_max.
 struct LawParams {
   double c0, c1, c2, c3, c4, base;
 };
-template <int MODEL>
-using NutArg = std::conditional_t<(MODEL >= OX_NUT_CARREAU_YASUDA), LawParams, double>;
+// Cs2 per cell (cell_bin NULL) or per bin: C = cs2[k stride], k = cell_bin[e] or e
+struct CoefTable {
+  const double *cs2;
+  int64_t stride, n_coef;
+  const int32_t *cell_bin;
+};
+// the model's factor by value: the laws' parameters, the table, or one double (the squared constant)
+template <int MODEL, int FORM>
+using NutArg = std::conditional_t<(MODEL >= OX_NUT_CARREAU_YASUDA), LawParams,
+                                  std::conditional_t<FORM == OX_NUT_TABLE, CoefTable, double>>;
 
-// van Driest damping: the tables of ox_vandriest by value; nothing where the flag is off
+// van Driest damping: the tables of ox_vandriest by value; nothing in the other forms
 struct NoDamping {};
-template <int VD>
-using DampArg = std::conditional_t<(VD != 0), ox_vandriest, NoDamping>;
+template <int FORM>
+using DampArg = std::conditional_t<FORM == OX_NUT_DAMPED, ox_vandriest, NoDamping>;
 
-template <int GDIM, int DEG, int MODEL, int VD = 0>
-__global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const int32_t *__restrict__ cell_dofs,
-                                                        const double *__restrict__ uab, NutArg<MODEL> coef2,
-                                                        double *__restrict__ nut, DampArg<VD> vd) {
-  constexpr int ND = ox_nd(GDIM, DEG);
+__device__ __forceinline__ double nut_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+
+template <int GDIM, int DEG, int MODEL, int FORM>
+__global__ __launch_bounds__(256) void k_cell_viscosity(ox_cells cells, const int32_t *__restrict__ cell_dofs,
+                                                        const double *__restrict__ uab, NutArg<MODEL, FORM> coef2,
+                                                        double *__restrict__ nut, DampArg<FORM> vd) {
+  static_assert(FORM == OX_NUT_PLAIN || MODEL == OX_NUT_SMAGORINSKY, "damping and the table belong to Smagorinsky");
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= cells.n_cells) return;
-  // round 1: the cell's dofs and geometry (both indexed by e); round 2: the coefficient gathers
-  int32_t dd[ND];
-  ox_load_dofs<ND>(cell_dofs, e, dd);
-  double G[GDIM + 1][GDIM], adet;
-  ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
-  double uc[ND][GDIM];
-  ox_gather<ND, GDIM>(dd, uab, uc);
-  double t[GDIM][GDIM + 1] = {}, g[GDIM][GDIM];
-  ox_contract<GDIM, ND>(uc, ox_dphic<GDIM, DEG>(), t);
-  ox_grad_from_t<GDIM>(t, G, g);
+  double uc[ox_nd(GDIM, DEG)][GDIM], g[GDIM][GDIM], adet;
+  ox_centroid_grad<GDIM, DEG>(cells, cell_dofs, uab, e, g, uc, adet);
   const double ss = ox_sym_sq<GDIM>(g);
-  // Delta^2 = |cell|^(2/gdim)
-  double delta2;
-  if constexpr (GDIM == 2) delta2 = 0.5 * adet;
-  else {
-    const double h = cbrt(adet * (1.0 / 6.0));
-    delta2 = h * h;
-  }
+  const double delta2 = ox_delta2<GDIM>(adet);
   double out;
-  if constexpr (MODEL == OX_NUT_SMAGORINSKY && VD != 0) {
+  if constexpr (FORM == OX_NUT_DAMPED) {
     // D = 1 - exp(-y+ / A+), y+ = d u_tau / nu, u_tau = sqrt(|wss|) of the centroid's nearest wall facet
     const int32_t f = vd.nearest[e];
     if (f < 0 || (int64_t)f >= vd.n_facets) {
-      out = __longlong_as_double(0x7ff8000000000000LL);
+      out = nut_nan();
     } else {
       double ut = vd.u_tau;
       if (vd.wss) {
@@ -87,6 +88,13 @@ __global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const in
       const double dmp = -expm1(-yp / vd.a_plus);
       out = coef2 * delta2 * (dmp * dmp) * sqrt(2.0 * ss);
     }
+  } else if constexpr (FORM == OX_NUT_TABLE) {
+    const int64_t k = coef2.cell_bin ? (int64_t)coef2.cell_bin[e] : e;
+    double c;
+    if (k < 0) c = 0.0;  // a cell outside every bin
+    else if (k >= coef2.n_coef) c = nut_nan();
+    else c = coef2.cs2[(size_t)k * coef2.stride];
+    out = c * delta2 * sqrt(2.0 * ss);
   } else if constexpr (MODEL == OX_NUT_SMAGORINSKY) {
     out = coef2 * delta2 * sqrt(2.0 * ss);
   } else if constexpr (MODEL == OX_NUT_CARREAU_YASUDA) {
@@ -132,112 +140,122 @@ __global__ __launch_bounds__(256) void k_eddy_viscosity(ox_cells cells, const in
   nut[e] = out;
 }
 
+// the table form keeps its own profiling tag: recorded profiles stay comparable
+template <int GD, int DG, int MODEL, int FORM>
+int nut_launch(const ox_cells *cells, const ox_viscosity_args *a, NutArg<MODEL, FORM> coef2, DampArg<FORM> vd, int64_t nblk,
+               hipStream_t st) {
+  if (ox_prof_on)
+    ox_prof_start(FORM == OX_NUT_TABLE ? OX_TAG_EDDY_VISCOSITY_CELLCOEF : OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);
+  hipLaunchKernelGGL((k_cell_viscosity<GD, DG, MODEL, FORM>), dim3(nblk), dim3(256), 0, st, *cells, a->cell_dofs, a->uab,
+                     coef2, a->nut, vd);
+  if (ox_prof_on) ox_prof_stop(st);
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+// the 39 instantiations: per element Smagorinsky plain, damped and from a table, the three laws, and WALE in 3-D
+template <int GD, int DG>
+int nut_model(const ox_cells *cells, const ox_viscosity_args *a, double c2, const LawParams &P, int64_t nblk,
+              hipStream_t st) {
+  switch (a->model) {
+  case OX_NUT_SMAGORINSKY:
+    if (a->cs2)
+      return nut_launch<GD, DG, OX_NUT_SMAGORINSKY, OX_NUT_TABLE>(
+          cells, a, CoefTable{a->cs2, a->cs2_stride, a->n_coef, a->cell_bin}, {}, nblk, st);
+    if (a->damping) return nut_launch<GD, DG, OX_NUT_SMAGORINSKY, OX_NUT_DAMPED>(cells, a, c2, *a->damping, nblk, st);
+    return nut_launch<GD, DG, OX_NUT_SMAGORINSKY, OX_NUT_PLAIN>(cells, a, c2, {}, nblk, st);
+  case OX_NUT_WALE:
+    if constexpr (GD == 3) return nut_launch<GD, DG, OX_NUT_WALE, OX_NUT_PLAIN>(cells, a, c2, {}, nblk, st);
+    else OX_FAIL("ox_cell_viscosity: model 1, WALE, is built for gdim = 3 (got %d)", GD);
+  case OX_NUT_CARREAU_YASUDA:
+    return nut_launch<GD, DG, OX_NUT_CARREAU_YASUDA, OX_NUT_PLAIN>(cells, a, P, {}, nblk, st);
+  case OX_NUT_CROSS:
+    return nut_launch<GD, DG, OX_NUT_CROSS, OX_NUT_PLAIN>(cells, a, P, {}, nblk, st);
+  default:
+    return nut_launch<GD, DG, OX_NUT_POWER_LAW, OX_NUT_PLAIN>(cells, a, P, {}, nblk, st);
+  }
+}
+
+// Every check on the argument block, on the host and before any device call; the laws' parameters end up in P.  A field
+// the chosen form does not read must be NULL or 0: a block filled for another form is refused, not half-used.
+int nut_check(const ox_cells *cells, const ox_viscosity_args *a, LawParams &P) {
+  if (!cells || !a) OX_FAIL("ox_cell_viscosity: null argument (cells, args)");
+  if (!cells->geom || !a->cell_dofs || !a->uab || !a->nut) OX_FAIL("ox_cell_viscosity: null geom, cell_dofs, uab or nut");
+  const int model = a->model;
+  if (model < OX_NUT_SMAGORINSKY || model > OX_NUT_POWER_LAW)
+    OX_FAIL("ox_cell_viscosity: model=%d (0: Smagorinsky, 1: WALE, 2: Carreau-Yasuda, 3: Cross, 4: power law)", model);
+  if (a->degree < 1 || a->degree > 3) OX_FAIL("ox_cell_viscosity: degree=%d (1, 2, 3)", a->degree);
+  const bool law = model >= OX_NUT_CARREAU_YASUDA, table = a->cs2 != nullptr;
+  if (!law && (a->params || a->n_params))
+    OX_FAIL("ox_cell_viscosity: params, n_params=%d belong to the laws (models 2-4), model=%d", a->n_params, model);
+  if ((law || table) && a->coefficient != 0.0)
+    OX_FAIL("ox_cell_viscosity: coefficient=%g belongs to models 0 and 1 without cs2 (model=%d)", a->coefficient, model);
+  if (model != OX_NUT_SMAGORINSKY && (a->damping || table))
+    OX_FAIL("ox_cell_viscosity: damping and cs2 belong to model 0 (model=%d)", model);
+  if (table && a->damping) OX_FAIL("ox_cell_viscosity: damping together with cs2 is not instantiated");
+  if (!table && (a->cs2_stride || a->n_coef || a->cell_bin))
+    OX_FAIL("ox_cell_viscosity: cs2_stride=%lld, n_coef=%lld, cell_bin without cs2", (long long)a->cs2_stride,
+            (long long)a->n_coef);
+  if (law) {
+    const double *params = a->params;
+    if (!params) OX_FAIL("ox_cell_viscosity: null argument (params)");
+    const int want = model == OX_NUT_CARREAU_YASUDA ? 5 : 4;
+    if (a->n_params != want)
+      OX_FAIL("ox_cell_viscosity: model %d takes n_params=%d parameters (got %d)", model, want, a->n_params);
+    for (int k = 0; k < want; ++k)
+      if (!std::isfinite(params[k])) OX_FAIL("ox_cell_viscosity: params[%d] is not finite", k);
+    if (model == OX_NUT_POWER_LAW) {
+      const double k = params[0], n = params[1], nu_min = params[2], nu_max = params[3];
+      if (k < 0.0 || n <= 0.0 || nu_min <= 0.0 || nu_min > nu_max)
+        OX_FAIL("ox_cell_viscosity: params of the power law k=%g n=%g nu_min=%g nu_max=%g", k, n, nu_min, nu_max);
+      P.c0 = k, P.c1 = n - 1.0, P.c2 = nu_min, P.c3 = nu_max, P.base = nu_min;
+    } else {
+      const double nu0 = params[0], nu_inf = params[1], lam = params[2], e = params[3];
+      if (nu0 < 0.0 || nu_inf < 0.0 || lam < 0.0 || e <= 0.0)
+        OX_FAIL("ox_cell_viscosity: params of model %d nu0=%g nu_inf=%g lam=%g exponent=%g", model, nu0, nu_inf, lam, e);
+      P.c0 = nu_inf, P.c1 = nu0 - nu_inf, P.c2 = lam, P.base = nu0 < nu_inf ? nu0 : nu_inf;
+      if (model == OX_NUT_CARREAU_YASUDA) {
+        const double y = params[4];
+        if (y <= 0.0) OX_FAIL("ox_cell_viscosity: params of Carreau-Yasuda a=%g", y);
+        P.c3 = y, P.c4 = (e - 1.0) / y;
+      } else {
+        P.c3 = e;
+      }
+    }
+  } else if (table) {
+    if (a->cs2_stride < 1) OX_FAIL("ox_cell_viscosity: cs2_stride=%lld", (long long)a->cs2_stride);
+    if (a->n_coef <= 0 || a->n_coef > (int64_t)0x7fffffff) OX_FAIL("ox_cell_viscosity: n_coef=%lld", (long long)a->n_coef);
+    if (!a->cell_bin && a->n_coef != cells->n_cells)
+      OX_FAIL("ox_cell_viscosity: n_coef=%lld coefficients for %lld cells and no cell_bin", (long long)a->n_coef,
+              (long long)cells->n_cells);
+  } else if (!(a->coefficient >= 0.0)) {
+    OX_FAIL("ox_cell_viscosity: coefficient=%g", a->coefficient);
+  }
+  if (const ox_vandriest *vd = a->damping) {
+    if (!vd->dist || !vd->nearest) OX_FAIL("ox_cell_viscosity: null argument (damping->dist, damping->nearest)");
+    if (!(vd->nu > 0.0) || !std::isfinite(vd->nu)) OX_FAIL("ox_cell_viscosity: damping->nu=%g", vd->nu);
+    if (!(vd->a_plus > 0.0) || !std::isfinite(vd->a_plus)) OX_FAIL("ox_cell_viscosity: damping->a_plus=%g", vd->a_plus);
+    if (!vd->wss && (!(vd->u_tau >= 0.0) || !std::isfinite(vd->u_tau)))
+      OX_FAIL("ox_cell_viscosity: damping->u_tau=%g", vd->u_tau);
+    if (vd->n_facets < 1 || vd->n_facets > (int64_t)0x7fffffff)
+      OX_FAIL("ox_cell_viscosity: damping->n_facets=%lld", (long long)vd->n_facets);
+  }
+  return 0;
+}
+
 }  // namespace
 
-extern "C" int ox_eddy_viscosity(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
-                                 double coefficient, double *nut, void *stream) {
-  if (!cells || !cell_dofs || !uab || !nut || !cells->geom) OX_FAIL("ox_eddy_viscosity: null argument");
-  if (!(coefficient >= 0.0)) OX_FAIL("ox_eddy_viscosity: coefficient=%g", coefficient);
-  const int64_t nblk = ox_cell_blocks("ox_eddy_viscosity", cells);
-  if (nblk <= 0) return (int)nblk;
-  hipStream_t st = ox_stream(stream);
-  const int g = cells->gdim;
-  const double c2 = coefficient * coefficient;
-  if (model == OX_NUT_WALE && g != 3) OX_FAIL("ox_eddy_viscosity: WALE is built for gdim = 3 (got %d)", g);
-  if (model != OX_NUT_SMAGORINSKY && model != OX_NUT_WALE) OX_FAIL("ox_eddy_viscosity: model=%d", model);
-#define OX_NUT_CASE(GD, DG, MD)                                                                                        \
-  if (g == GD && degree == DG && model == MD) {                                                                        \
-    if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                          \
-    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, c2, nut, \
-                       NoDamping{});                                                                                   \
-    if (ox_prof_on) ox_prof_stop(st);                                                                                  \
-    OX_LAUNCH_CHECK();                                                                                                 \
-    return 0;                                                                                                          \
-  }
-  OX_FOR_GDIM_DEG(OX_NUT_CASE, OX_NUT_SMAGORINSKY)
-  OX_NUT_CASE(3, 1, OX_NUT_WALE) OX_NUT_CASE(3, 2, OX_NUT_WALE) OX_NUT_CASE(3, 3, OX_NUT_WALE)
-#undef OX_NUT_CASE
-  OX_FAIL("ox_eddy_viscosity: unsupported gdim=%d degree=%d", g, degree);
-}
-
-// Smagorinsky with van Driest damping: k_eddy_viscosity with the damping flag; 12 B more per cell are streamed (dist,
-// nearest) and gdim doubles of wss gathered.
-extern "C" int ox_eddy_viscosity_damped(int model, int degree, const ox_cells *cells, const int32_t *cell_dofs,
-                                        const double *uab, double coefficient, const ox_vandriest *vd, double *nut,
-                                        void *stream) {
-  if (!cells || !cell_dofs || !uab || !nut || !cells->geom || !vd) OX_FAIL("ox_eddy_viscosity_damped: null argument");
-  if (!vd->dist || !vd->nearest) OX_FAIL("ox_eddy_viscosity_damped: null argument (dist, nearest)");
-  if (!(coefficient >= 0.0)) OX_FAIL("ox_eddy_viscosity_damped: coefficient=%g", coefficient);
-  if (model != OX_NUT_SMAGORINSKY) OX_FAIL("ox_eddy_viscosity_damped: model=%d (0: Smagorinsky)", model);
-  if (!(vd->nu > 0.0) || !std::isfinite(vd->nu)) OX_FAIL("ox_eddy_viscosity_damped: nu=%g", vd->nu);
-  if (!(vd->a_plus > 0.0) || !std::isfinite(vd->a_plus)) OX_FAIL("ox_eddy_viscosity_damped: a_plus=%g", vd->a_plus);
-  if (!vd->wss && (!(vd->u_tau >= 0.0) || !std::isfinite(vd->u_tau))) OX_FAIL("ox_eddy_viscosity_damped: u_tau=%g", vd->u_tau);
-  if (vd->n_facets < 1 || vd->n_facets > (int64_t)0x7fffffff)
-    OX_FAIL("ox_eddy_viscosity_damped: n_facets=%lld", (long long)vd->n_facets);
-  const int64_t nblk = ox_cell_blocks("ox_eddy_viscosity_damped", cells);
-  if (nblk <= 0) return (int)nblk;
-  hipStream_t st = ox_stream(stream);
-  const int g = cells->gdim;
-  const double c2 = coefficient * coefficient;
-#define OX_NUT_VD_CASE(GD, DG)                                                                                        \
-  if (g == GD && degree == DG) {                                                                                      \
-    if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                         \
-    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, OX_NUT_SMAGORINSKY, 1>), dim3(nblk), dim3(256), 0, st, *cells,       \
-                       cell_dofs, uab, c2, nut, *vd);                                                                 \
-    if (ox_prof_on) ox_prof_stop(st);                                                                                 \
-    OX_LAUNCH_CHECK();                                                                                                \
-    return 0;                                                                                                         \
-  }
-  OX_FOR_GDIM_DEG(OX_NUT_VD_CASE)
-#undef OX_NUT_VD_CASE
-  OX_FAIL("ox_eddy_viscosity_damped: unsupported gdim=%d degree=%d", g, degree);
-}
-
-// nut[e] = max(nu(gd_e) - base, 0) of a generalised-Newtonian law (include/oasisx_hip.h): the centroid gradient of
-// k_eddy_viscosity, the law as one more branch of it.
-extern "C" int ox_viscosity_law(int law, int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
-                                const double *params, int n_params, double *nut, void *stream) {
-  if (!cells || !cell_dofs || !uab || !params || !nut || !cells->geom) OX_FAIL("ox_viscosity_law: null argument");
-  const int want = law == OX_NUT_CARREAU_YASUDA ? 5 : ((law == OX_NUT_CROSS || law == OX_NUT_POWER_LAW) ? 4 : -1);
-  if (want < 0) OX_FAIL("ox_viscosity_law: law=%d (2: Carreau-Yasuda, 3: Cross, 4: power law)", law);
-  if (n_params != want) OX_FAIL("ox_viscosity_law: law %d takes %d parameters (got %d)", law, want, n_params);
-  for (int k = 0; k < n_params; ++k)
-    if (!std::isfinite(params[k])) OX_FAIL("ox_viscosity_law: parameter %d is not finite", k);
+extern "C" int ox_cell_viscosity(const ox_cells *cells, const ox_viscosity_args *args, void *stream) {
   LawParams P{};
-  if (law == OX_NUT_POWER_LAW) {
-    const double k = params[0], n = params[1], nu_min = params[2], nu_max = params[3];
-    if (k < 0.0 || n <= 0.0 || nu_min <= 0.0 || nu_min > nu_max)
-      OX_FAIL("ox_viscosity_law: power law k=%g n=%g nu_min=%g nu_max=%g", k, n, nu_min, nu_max);
-    P.c0 = k, P.c1 = n - 1.0, P.c2 = nu_min, P.c3 = nu_max, P.base = nu_min;
-  } else {
-    const double nu0 = params[0], nu_inf = params[1], lam = params[2], e = params[3];
-    if (nu0 < 0.0 || nu_inf < 0.0 || lam < 0.0 || e <= 0.0)
-      OX_FAIL("ox_viscosity_law: law %d nu0=%g nu_inf=%g lam=%g exponent=%g", law, nu0, nu_inf, lam, e);
-    P.c0 = nu_inf, P.c1 = nu0 - nu_inf, P.c2 = lam, P.base = nu0 < nu_inf ? nu0 : nu_inf;
-    if (law == OX_NUT_CARREAU_YASUDA) {
-      const double a = params[4];
-      if (a <= 0.0) OX_FAIL("ox_viscosity_law: Carreau-Yasuda a=%g", a);
-      P.c3 = a, P.c4 = (e - 1.0) / a;
-    } else {
-      P.c3 = e;
-    }
-  }
-  const int64_t nblk = ox_cell_blocks("ox_viscosity_law", cells);
+  if (nut_check(cells, args, P)) return -1;
+  const int64_t nblk = ox_cell_blocks("ox_cell_viscosity", cells);
   if (nblk <= 0) return (int)nblk;
   hipStream_t st = ox_stream(stream);
   const int g = cells->gdim;
-#define OX_LAW_CASE(GD, DG, MD)                                                                                       \
-  if (g == GD && degree == DG && law == MD) {                                                                         \
-    if (ox_prof_on) ox_prof_start(OX_TAG_EDDY_VISCOSITY, st, cells->n_cells);                                         \
-    hipLaunchKernelGGL((k_eddy_viscosity<GD, DG, MD>), dim3(nblk), dim3(256), 0, st, *cells, cell_dofs, uab, P, nut, \
-                       NoDamping{});                                                                                  \
-    if (ox_prof_on) ox_prof_stop(st);                                                                                 \
-    OX_LAUNCH_CHECK();                                                                                                \
-    return 0;                                                                                                         \
-  }
-  OX_FOR_GDIM_DEG(OX_LAW_CASE, OX_NUT_CARREAU_YASUDA)
-  OX_FOR_GDIM_DEG(OX_LAW_CASE, OX_NUT_CROSS)
-  OX_FOR_GDIM_DEG(OX_LAW_CASE, OX_NUT_POWER_LAW)
-#undef OX_LAW_CASE
-  OX_FAIL("ox_viscosity_law: unsupported gdim=%d degree=%d", g, degree);
+  const double c2 = args->coefficient * args->coefficient;
+#define OX_NUT_CASE(GD, DG) \
+  if (g == GD && args->degree == DG) return nut_model<GD, DG>(cells, args, c2, P, nblk, st);
+  OX_FOR_GDIM_DEG(OX_NUT_CASE)
+#undef OX_NUT_CASE
+  OX_FAIL("ox_cell_viscosity: unsupported gdim=%d (degree=%d)", g, args->degree);
 }

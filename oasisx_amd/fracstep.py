@@ -504,7 +504,7 @@ class FractionalStep_AB_CN:
     @_phase
     def viscosity_assemble(self, nu=None, dt=None):
         """``nut`` per cell (kernel cell order) of the model, from the ``u_ab`` block ``assemble_first`` has just formed
-        (``ox_eddy_viscosity``; a :class:`CellViscosity` copies its fixed values).  ``nu``: the molecular viscosity of the
+        (``ox_cell_viscosity``; a :class:`CellViscosity` copies its fixed values).  ``nu``: the molecular viscosity of the
         step, read only by a model with wall damping (``y+ = d u_tau / nu``).  ``dt``: the step, handed only to a model
         that declares ``needs_dt`` (the Lagrangian average of :class:`oasisx_amd.DynamicSmagorinsky`, which has a memory)."""
         if self._viscosity_model is None:

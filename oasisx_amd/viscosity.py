@@ -18,7 +18,7 @@ The generalised-Newtonian laws (:class:`CarreauYasuda`, :class:`Cross`, :class:`
 kernel writes ``nut_c = nu(gd_c) - base_viscosity >= 0`` and the caller runs the step at ``nu = base_viscosity``, so
 everything downstream of ``nut`` -- the fused kernel, ``eddy_viscosity()``, :class:`oasisx_amd.WallStress` -- is unchanged.
 
-Per ``assemble_first``: one kernel writes ``nut_c`` from ``grad u_ab`` at the cell centroids (``ox_eddy_viscosity``,
+Per ``assemble_first``: one kernel writes ``nut_c`` from ``grad u_ab`` at the cell centroids (``ox_cell_viscosity``,
 csrc/ox_viscosity.hip; :class:`CellViscosity` has nothing to evaluate), then the fused assembly kernel adds
 ``nut_c K_c`` to the convection rows it forms anyway (``ox_assemble_first`` with ``ox_first_args.nut``): no second pass over the pattern, no
 second matrix.  ``Delta_c = |cell|^(1/gdim)``.
@@ -47,8 +47,24 @@ def _coefficient(what, v):
     return v
 
 
+def _cell_viscosity(solver, nut: torch.Tensor, *, model=0, coefficient=0.0, params=(), damping=None, cs2=None,
+                    cs2_stride=0, n_coef=0, cell_bin=None, stream=None):
+    """One ``ox_cell_viscosity`` launch: ``nut`` (kernel cell order) from the solver's ``u_ab`` on ``stream`` (``None``:
+    torch's current stream).  The other keywords are the per-model fields of ``ox_viscosity_args`` (include/oasisx_hip.h):
+    what a model does not read stays NULL / 0.  ``damping``: an ``ox_vandriest``; ``cs2``, ``cell_bin``: device addresses."""
+    import ctypes as C
+
+    Vi = solver._Vi[0][0]
+    par = (C.c_double * len(params))(*params) if len(params) else None
+    args = _lib.ox_viscosity_args(model, Vi.degree, _lib.ptr(Vi.cell_dofs), solver._UAB.rptr(), _lib.ptr(nut), coefficient,
+                                  par, len(params), None if damping is None else C.pointer(damping), cs2, cs2_stride,
+                                  n_coef, cell_bin)
+    _lib.check(solver._lib.ox_cell_viscosity(C.byref(solver._cells), C.byref(args),
+                                             _lib.current_stream() if stream is None else stream), "ox_cell_viscosity")
+
+
 class _KernelModel:
-    """A model whose ``nut`` is a function of ``grad u_ab`` at the cell centroid: evaluated by ``ox_eddy_viscosity``."""
+    """A model whose ``nut`` is a function of ``grad u_ab`` at the cell centroid: evaluated by ``ox_cell_viscosity``."""
 
     model_id = None
     # nut is a turbulent viscosity that mixes scalars too: kappa_eff = kappa + nut / Sc_t (scalar.py, DESIGN.md section 25)
@@ -61,12 +77,7 @@ class _KernelModel:
         pass
 
     def evaluate(self, solver, nut: torch.Tensor, nu=None):
-        Vi = solver._Vi[0][0]
-        import ctypes as C
-
-        _lib.check(solver._lib.ox_eddy_viscosity(self.model_id, Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
-                                                 solver._UAB.rptr(), self.coefficient, _lib.ptr(nut),
-                                                 _lib.current_stream()), "ox_eddy_viscosity")
+        _cell_viscosity(solver, nut, model=self.model_id, coefficient=self.coefficient)
 
 
 class VanDriest:
@@ -135,9 +146,7 @@ class VanDriest:
         vd = _lib.ox_vandriest(self._dist.data_ptr(), self._nearest.data_ptr(),
                                self._wss.data_ptr() if self.u_tau is None else None,
                                0.0 if self.u_tau is None else self.u_tau, nu, self.A_plus, self.n_facets)
-        _lib.check(lib.ox_eddy_viscosity_damped(0, Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
-                                                solver._UAB.rptr(), coefficient, C.byref(vd), _lib.ptr(nut), st),
-                   "ox_eddy_viscosity_damped")
+        _cell_viscosity(solver, nut, model=0, coefficient=coefficient, damping=vd, stream=st)
         self._nu = nu
 
     def friction_velocity(self) -> torch.Tensor:
@@ -162,7 +171,7 @@ class VanDriest:
 
 class Smagorinsky(_KernelModel):
     """``nut_c = (Cs Delta_c)^2 sqrt(2 S:S)``, ``S = sym(grad u_ab)`` at the cell centroid.  2-D and 3-D, P1 / P2 / P3.
-    ``damping``: a :class:`VanDriest` object: ``nut_c = (Cs Delta_c D_c)^2 sqrt(2 S:S)`` (``ox_eddy_viscosity_damped``);
+    ``damping``: a :class:`VanDriest` object: ``nut_c = (Cs Delta_c D_c)^2 sqrt(2 S:S)`` (the ``damping`` field);
     ``None``: the calls of the undamped model, nothing else."""
 
     model_id = 0
@@ -529,14 +538,11 @@ class DynamicSmagorinsky(_KernelModel):
         if self.n_evaluations % self.update_every == 0:
             self.update_coefficient(solver, dt)
         self.n_evaluations += 1
-        Vi = solver._Vi[0][0]
         if self.average != "global":
             cs2, stride, n, cb = _lib.ptr(self._cs2), 1, self._patches.n_cells, None
         else:
             cs2, stride, n, cb = C.c_void_p(self._bins.data_ptr() + 8 * 3), 4, self.n_bins, _lib.ptr(self._cell_bin)
-        _lib.check(solver._lib.ox_eddy_viscosity_cellcoef(Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
-                                                          solver._UAB.rptr(), cs2, stride, n, cb, _lib.ptr(nut),
-                                                          _lib.current_stream()), "ox_eddy_viscosity_cellcoef")
+        _cell_viscosity(solver, nut, model=0, cs2=cs2, cs2_stride=stride, n_coef=n, cell_bin=cb)
 
     # ---- accessors
     def _need(self, what):
@@ -680,7 +686,7 @@ def _law_parameter(what, name, v, positive=False):
 
 class _LawModel(_KernelModel):
     """A generalised-Newtonian law ``nu(gd)``, ``gd = sqrt(2 S:S)`` at the cell centroid: ``nut_c = nu(gd_c) -
-    base_viscosity`` (``ox_viscosity_law``).  ``params``: the law's parameters in the order of include/oasisx_hip.h."""
+    base_viscosity`` (models 2-4).  ``params``: the law's parameters in the order of include/oasisx_hip.h."""
 
     base_viscosity = None
     params = ()
@@ -688,13 +694,7 @@ class _LawModel(_KernelModel):
     diffuses_scalars = False
 
     def evaluate(self, solver, nut: torch.Tensor, nu=None):
-        Vi = solver._Vi[0][0]
-        import ctypes as C
-
-        par = (C.c_double * len(self.params))(*self.params)
-        _lib.check(solver._lib.ox_viscosity_law(self.model_id, Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs),
-                                                solver._UAB.rptr(), par, len(self.params), _lib.ptr(nut),
-                                                _lib.current_stream()), "ox_viscosity_law")
+        _cell_viscosity(solver, nut, model=self.model_id, params=self.params)
 
 
 class CarreauYasuda(_LawModel):

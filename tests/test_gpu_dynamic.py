@@ -456,9 +456,8 @@ def test_scalars_full_stress_and_storage_modes(hip):
     # the default path
     lib = _lib.load()
     new = ["ox_dynamic_cells", "ox_dynamic_vertices", "ox_dynamic_products", "ox_dynamic_bin_sums",
-           "ox_dynamic_bin_coefficients", "ox_patch_filter_vertices", "ox_patch_filter_cells", "ox_dynamic_clip",
-           "ox_eddy_viscosity_cellcoef"]
-    calls = []
+           "ox_dynamic_bin_coefficients", "ox_patch_filter_vertices", "ox_patch_filter_cells", "ox_dynamic_clip"]
+    calls, tables = [], []  # tables: per ox_cell_viscosity call, whether the block carries a table of Cs2
 
     class Spy:
         def __init__(self, lib):
@@ -467,24 +466,32 @@ def test_scalars_full_stress_and_storage_modes(hip):
         def __getattr__(self, name):
             if name in new:
                 calls.append(name)
-            return getattr(self._lib, name)
+            fn = getattr(self._lib, name)
+            if name != "ox_cell_viscosity":
+                return fn
+
+            def cell_viscosity(cells, args, stream):
+                tables.append(args._obj.cs2 is not None)
+                return fn(cells, args, stream)
+
+            return cell_viscosity
 
     S, clock, _ = _problem(2, 5, 2, None)
     assert S._nut is None
     S._lib = Spy(lib)
     clock["t"] = dt
     S.solve(dt, nu, max_iter=1)
-    assert calls == []
+    assert calls == [] and tables == []
     S, clock, _ = _problem(2, 5, 2, ox.Smagorinsky())
     S._lib = Spy(lib)
     clock["t"] = dt
     S.solve(dt, nu, max_iter=1)
-    assert calls == []
+    assert calls == [] and tables != [] and not any(tables)  # (the constant form: never a table)
     S, clock, _ = _problem(2, 5, 2, ox.DynamicSmagorinsky())
     S._lib = Spy(lib)
     clock["t"] = dt
     S.solve(dt, nu, max_iter=1)
-    assert "ox_dynamic_cells" in calls and "ox_eddy_viscosity_cellcoef" in calls  # (the spy sees the new calls)
+    assert "ox_dynamic_cells" in calls and any(tables)  # (the spy sees the new calls)
 
 
 def test_guards(hip):
@@ -533,10 +540,11 @@ def test_guards(hip):
     q = torch.zeros((p.n_cells, 3), dtype=torch.float64, device=m._rec.device)
     assert lib.ox_patch_filter_cells(3, 2, p.n_cells, _lib.ptr(p.cell_verts), p.n_vertices, _lib.ptr(q), _lib.ptr(q),
                                      None) != 0
-    assert lib.ox_eddy_viscosity_cellcoef(Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), S._UAB.rptr(),
-                                          _lib.ptr(m._bins), 0, 1, None, _lib.ptr(S._nut), None) != 0
-    assert lib.ox_eddy_viscosity_cellcoef(Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), S._UAB.rptr(),
-                                          _lib.ptr(m._bins), 4, 1, None, _lib.ptr(S._nut), None) != 0  # per cell: n_coef
+    for stride in (0, 4):  # cs2_stride < 1; per cell (no cell_bin): n_coef = 1 is not n_cells
+        args = _lib.ox_viscosity_args(0, Vi.degree, _lib.ptr(Vi.cell_dofs), S._UAB.rptr(), _lib.ptr(S._nut), 0.0, None, 0,
+                                      None, _lib.ptr(m._bins), stride, 1, None)
+        assert lib.ox_cell_viscosity(C.byref(S._cells), C.byref(args), None) != 0
+        assert (b"cs2_stride" if stride == 0 else b"n_coef") in lib.ox_last_error()
     torch.cuda.synchronize()
 
 

@@ -299,15 +299,11 @@ def test_surface_and_guards(hip):
     # the C entry points check their own arguments
     Vi = S._Vi[0][0]
     par = (C.c_double * 4)(0.05, 0.6, 0.5, 0.005)  # nu_min > nu_max
-    rc = S._lib.ox_viscosity_law(4, Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), S._UAB.rptr(), par, 4, _lib.ptr(S._nut),
-                                 _lib.current_stream())
-    assert rc != 0
-    rc = S._lib.ox_viscosity_law(2, Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), S._UAB.rptr(), par, 4, _lib.ptr(S._nut),
-                                 _lib.current_stream())
-    assert rc != 0  # Carreau-Yasuda takes five parameters
-    rc = S._lib.ox_viscosity_law(0, Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), S._UAB.rptr(), par, 4, _lib.ptr(S._nut),
-                                 _lib.current_stream())
-    assert rc != 0  # the eddy-viscosity models stay with ox_eddy_viscosity
+    for model in (4, 2, 0):  # the power law's own check; Carreau-Yasuda takes five parameters; model 0 reads no params
+        args = _lib.ox_viscosity_args(model, Vi.degree, _lib.ptr(Vi.cell_dofs), S._UAB.rptr(), _lib.ptr(S._nut), 0.0, par, 4,
+                                      None, None, 0, 0, None)
+        rc = S._lib.ox_cell_viscosity(C.byref(S._cells), C.byref(args), _lib.current_stream())
+        assert rc != 0 and b"ox_cell_viscosity" in S._lib.ox_last_error() and b"param" in S._lib.ox_last_error()
 
 
 # ---- 7. the demo ---------------------------------------------------------------------------------------------------------

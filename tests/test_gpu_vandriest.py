@@ -1,4 +1,4 @@
-"""GPU: Smagorinsky with van Driest wall damping (oasisx_amd.VanDriest, ox_eddy_viscosity_damped of
+"""GPU: Smagorinsky with van Driest wall damping (oasisx_amd.VanDriest, the damping of ox_cell_viscosity,
 csrc/ox_viscosity.hip) against the numpy models of tests/walldist_model.py, tests/wall_stress_model.py and
 tests/viscosity_model.py, on the cases and the perturbed Taylor-Green levels of tests/test_gpu_viscosity.py.
 

@@ -1,6 +1,6 @@
 """numpy model of the wall-distance query (oasisx_amd.geometry.WallDistance, ox_walldist_* of csrc/ox_probe.hip) and of
-the van Driest damping of the Smagorinsky model (oasisx_amd.VanDriest, ox_eddy_viscosity_damped).  No GPU, no grid: every
-point is tested against every facet.
+the van Driest damping of the Smagorinsky model (oasisx_amd.VanDriest, the damping of ox_cell_viscosity).  No GPU, no
+grid: every point is tested against every facet.
 
     2-D   closest point of the segment (a, b): the projection t = (x - a).(b - a) / |b - a|^2 clamped to [0, 1]
     3-D   closest point of the triangle (a, b, c) by its seven regions: three vertices, three edges, the face

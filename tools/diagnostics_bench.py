@@ -6,7 +6,7 @@ tools/viscosity_bench.py.
                                       [--bench-trees this=DIR parent=DIR] [--bench-runs 2]
 
 Part 1, the kernels, launch after launch, alternating:
-  * ``ox_flow_cells`` with and without ``fields`` beside ``ox_eddy_viscosity`` (the same streams -- dof list, geometry
+  * ``ox_flow_cells`` with and without ``fields`` beside ``ox_cell_viscosity`` (the same streams -- dof list, geometry
     record, u once per dof -- plus the quadrature loop; bytes from the stored sizes) and ``ox_flow_reduce``;
   * ``ox_stats_accumulate`` for ``u`` with the bytes it moves, ``(gdim + 2 (gdim + gdim (gdim + 1) / 2)) 8 B`` per dof, and
     for ``p``, beside ``ox_axpby`` (two reads, one write) on blocks of the same total bytes.
@@ -44,6 +44,7 @@ def main():
 
     import oasisx_amd as ox
     from oasisx_amd import _lib
+    from oasisx_amd.viscosity import _cell_viscosity
 
     # part 3 first: the children have the device to themselves (this process has not touched it yet)
     bench = bench_trees(a.bench_trees, a.bench_runs) if a.bench_trees else None
@@ -69,8 +70,7 @@ def main():
                                      _lib.ptr(D._fields), None, _lib.ptr(D._partials), st), "ox_flow_cells")
 
     def eddy():
-        _lib.check(lib.ox_eddy_viscosity(0, Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), S._UAB.rptr(), 0.1677,
-                                         _lib.ptr(nut_scratch), st), "ox_eddy_viscosity")
+        _cell_viscosity(S, nut_scratch, model=0, coefficient=0.1677)
 
     def reduce_():
         _lib.check(lib.ox_flow_reduce(Dsum.n_blocks, _lib.ptr(Dsum._partials), _lib.ptr(Dsum._ring), Dsum.capacity, 0, st),

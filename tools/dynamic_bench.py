@@ -6,7 +6,7 @@ medians, the variants alternating inside the timed loops.
     python tools/dynamic_bench.py [-N 128] [--steps 8] [--warmup 3] [--reps 20] [--out FILE]
                                   [--bench-trees this=DIR parent=DIR] [--bench-runs 2]
 
-Part 1, every new launch, alternating, beside ``ox_eddy_viscosity`` (Smagorinsky) and ``ox_profile_cells`` (the velocity
+Part 1, every new launch, alternating, beside ``ox_cell_viscosity`` (Smagorinsky) and ``ox_profile_cells`` (the velocity
 group of ``ProfileStatistics(axis=1)``).  Bytes per launch from the stored sizes: what is streamed (dof lists, geometry,
 records written) counts once; a gathered table counts twice -- ``gather_bytes`` (what the lanes request) and
 ``unique_bytes`` (every table entry once: what has to come from HBM if the caches serve the re-reads).
@@ -44,6 +44,7 @@ def main():
 
     import oasisx_amd as ox
     from oasisx_amd import _lib
+    from oasisx_amd.viscosity import _cell_viscosity
 
     bench = bench_trees(a.bench_trees, a.bench_runs) if a.bench_trees else None
     smag = ox.Smagorinsky()
@@ -82,16 +83,14 @@ def main():
 
     def cellcoef(m):
         if m.average == "local":
-            args = (_lib.ptr(m._cs2), 1, nc, None)
+            _cell_viscosity(S, S._nut, cs2=_lib.ptr(m._cs2), cs2_stride=1, n_coef=nc)
         else:
-            args = (C.c_void_p(m._bins.data_ptr() + 24), 4, m.n_bins, _lib.ptr(m._cell_bin))
-        _lib.check(lib.ox_eddy_viscosity_cellcoef(Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs), S._UAB.rptr(), *args,
-                                                  _lib.ptr(S._nut), st), "ox_eddy_viscosity_cellcoef")
+            _cell_viscosity(S, S._nut, cs2=C.c_void_p(m._bins.data_ptr() + 24), cs2_stride=4, n_coef=m.n_bins,
+                            cell_bin=_lib.ptr(m._cell_bin))
 
     F = lo._filter
     variants = {
-        "eddy_viscosity": lambda: _lib.check(lib.ox_eddy_viscosity(0, Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs),
-                                                                   S._UAB.rptr(), 0.1677, _lib.ptr(S._nut), st), "nut"),
+        "eddy_viscosity": lambda: _cell_viscosity(S, S._nut, model=0, coefficient=0.1677),
         "profile_cells": lambda: ps._cells(pg, pg.sources, pg.mean),
         "dynamic_cells": lambda: _lib.check(lib.ox_dynamic_cells(Vi.degree, C.byref(S._cells), _lib.ptr(Vi.cell_dofs),
                                                                  S._UAB.rptr(), _lib.ptr(g._rec), st), "cells"),
@@ -150,8 +149,8 @@ def main():
     phase = []
     inner = S.viscosity_assemble
 
-    def wrapped(nu_=None):
-        phase.append(timed(torch, lambda: inner(nu_)))
+    def wrapped(*args):
+        phase.append(timed(torch, lambda: inner(*args)))
 
     S.viscosity_assemble = wrapped
     rec = {k: {"step": [], "nut": []} for k, _, _ in runs}

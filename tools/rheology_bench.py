@@ -6,7 +6,7 @@ alternating inside the timed loops.  The set-up is that of tools/viscosity_bench
                                    [--bench-trees this=DIR parent=DIR] [--bench-runs 2]
 
 Part 1, the kernels, launch after launch, alternating:
-  * ``ox_viscosity_law`` for the three laws beside ``ox_eddy_viscosity`` (Smagorinsky): the same streams, so the same
+  * ``ox_cell_viscosity`` for the three laws beside its Smagorinsky model: the same streams, so the same
     bytes per launch from the stored sizes (dof list, geometry record, nut written, u_ab once per dof);
   * ``ox_assemble_stress_transpose`` beside one ``ox_assemble_grad_vector`` kind-0 launch (the same walk over the rows'
     cells) and one ``ox_assemble_matrix(STIFF)`` pass.  Bytes from the stored sizes: the adjacency table (cell and local
@@ -48,6 +48,7 @@ def main():
     import oasisx_amd as ox
     from bench import make_workload
     from oasisx_amd import _lib
+    from oasisx_amd.viscosity import _cell_viscosity
     from oasisx_amd.la import SellMatrix
 
     # part 3 first: the children have the device to themselves (this process has not touched it yet)
@@ -72,13 +73,10 @@ def main():
     gs = int(S2._geom.shape[1])
 
     def law_kernel(model):
-        par = (C.c_double * len(model.params))(*model.params)
-        _lib.check(lib.ox_viscosity_law(model.model_id, Vi.degree, C.byref(S2._cells), _lib.ptr(Vi.cell_dofs), S2._UAB.rptr(),
-                                        par, len(model.params), _lib.ptr(nut_scratch), st), "ox_viscosity_law")
+        _cell_viscosity(S2, nut_scratch, model=model.model_id, params=model.params)
 
     def smagorinsky_kernel():
-        _lib.check(lib.ox_eddy_viscosity(0, Vi.degree, C.byref(S2._cells), _lib.ptr(Vi.cell_dofs), S2._UAB.rptr(), 0.1677,
-                                         _lib.ptr(nut_scratch), st), "ox_eddy_viscosity")
+        _cell_viscosity(S2, nut_scratch, model=0, coefficient=0.1677)
 
     def transpose_kernel():
         _lib.check(lib.ox_assemble_stress_transpose(Vi.degree, C.byref(S2._cells), _lib.ptr(Vi.cell_dofs), C.byref(S2._adj_u),

@@ -6,7 +6,7 @@ timed loops.
                                     [--bench-trees this=DIR parent=DIR] [--bench-runs 2]
 
 Part 1, the kernels, launch after launch, alternating:
-  * ``ox_eddy_viscosity`` (Smagorinsky, WALE).  Bytes moved per launch from the stored sizes: per cell the dof list
+  * ``ox_cell_viscosity`` (Smagorinsky, WALE).  Bytes moved per launch from the stored sizes: per cell the dof list
     (nd x 4 B), the geometry record (10 x 8 B in 3-D) and 8 B of nut written; the u_ab gathers are served by the caches
     and count once per dof (gdim x 8 B);
   * ``assemble_first`` of the solver without a model (the constant-viscosity instantiation: the code of the parent
@@ -107,13 +107,11 @@ def main():
                     help="source trees to run bench.py's default line in, e.g. this=. parent=../parent")
     ap.add_argument("--bench-runs", type=int, default=2)
     a = ap.parse_args()
-    import ctypes as C
-
     import torch
 
     import oasisx_amd as ox
-    from oasisx_amd import _lib
     from oasisx_amd.la import SellMatrix
+    from oasisx_amd.viscosity import _cell_viscosity
 
     # part 3 first: the children have the device to themselves (this process has not touched it yet)
     bench = bench_trees(a.bench_trees, a.bench_runs) if a.bench_trees else None
@@ -127,15 +125,13 @@ def main():
     torch.cuda.synchronize()
 
     # ---- part 1: the kernels ------------------------------------------------------------------------------------------
-    lib, st = _lib.load(), _lib.current_stream()
     Vi = S1._Vi[0][0]
     P = S1._A.pattern
     ncells, nd = int(S1._geom.shape[0]), int(Vi.cell_dofs.shape[1])
     want_au = True
 
     def nut_kernel(model_id, coef):
-        _lib.check(lib.ox_eddy_viscosity(model_id, Vi.degree, C.byref(S1._cells), _lib.ptr(Vi.cell_dofs), S1._UAB.rptr(), coef,
-                                         _lib.ptr(S1._nut), st), "ox_eddy_viscosity")
+        _cell_viscosity(S1, S1._nut, model=model_id, coefficient=coef)
 
     scratch = SellMatrix(Vi.pattern, symmetric=True, name="K_bench")
     variants = {
@@ -166,8 +162,8 @@ def main():
     phase = []
     inner = S1.viscosity_assemble
 
-    def wrapped():
-        phase.append(timed(torch, inner))
+    def wrapped(*args):
+        phase.append(timed(torch, lambda: inner(*args)))
 
     S1.viscosity_assemble = wrapped
     rec = {"constant_nu": {"step": []}, "smagorinsky": {"step": [], "nut": []}}

@@ -9,7 +9,7 @@ Per wall set (``two``: the faces y = lo and y = hi; ``six``: all exterior facets
     mean number of rings a centroid visits, estimated from its distance and the bin widths (``ceil(d / min h) + 1``, capped
     by the grid);
   * kernels, alternating: the damped nut kernel plus its ``ox_wall_stress`` launch beside the undamped
-    ``ox_eddy_viscosity``; the bytes model is +12 B per cell (dist, nearest) on the undamped kernel's stream;
+    ``ox_cell_viscosity``; the bytes model is +12 B per cell (dist, nearest) on the undamped kernel's stream;
   * whole steps without a model, with Smagorinsky and with Smagorinsky + VanDriest, alternating.
 ``--bench-trees``: ``bench.py``'s default line as child processes in the given source trees, alternating (the default
 path makes no new call)."""
@@ -50,14 +50,12 @@ def main():
     ap.add_argument("--bench-trees", nargs="*", default=[], metavar="LABEL=DIR")
     ap.add_argument("--bench-runs", type=int, default=2)
     a = ap.parse_args()
-    import ctypes as C
-
     import numpy as np
     import torch
     from viscosity_bench import bench_trees, build, timed
 
     import oasisx_amd as ox
-    from oasisx_amd import _lib
+    from oasisx_amd.viscosity import _cell_viscosity
 
     bench = bench_trees(a.bench_trees, a.bench_runs) if a.bench_trees else None
     S0, W, clk0 = build(a.N, None)
@@ -95,12 +93,10 @@ def main():
                 clk["t"] += dt
                 S.solve(dt, nu, max_iter=1)
         torch.cuda.synchronize()
-        lib, st = _lib.load(), _lib.current_stream()
         Vi = S1._Vi[0][0]
 
         def plain():
-            _lib.check(lib.ox_eddy_viscosity(0, Vi.degree, C.byref(S1._cells), _lib.ptr(Vi.cell_dofs), S1._UAB.rptr(), 0.1677,
-                                             _lib.ptr(S1._nut), st), "ox_eddy_viscosity")
+            _cell_viscosity(S1, S1._nut, model=0, coefficient=0.1677)
 
         variants = {"nut_smagorinsky": plain, "nut_damped_with_wall_stress": lambda: S2.viscosity_assemble(nu)}
         ev = {k: [] for k in variants}
