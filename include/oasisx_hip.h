@@ -1016,6 +1016,37 @@ int ox_outlet_backflow(int u_degree, const ox_cells *cells, const int32_t *cell_
                        int64_t n_facets, const int32_t *facet_rec, const double *beta, const double *uab, const double *u1,
                        double *a_vals, int64_t a_size, double *b_first, void *stream);
 
+/* ---- Drag zones: -sigma(x, |u|) (u - u_t) in the momentum equation (ox_drag.hip) ---------------
+ * Porous media (Darcy-Forchheimer), sponge layers that relax to a target field, solids by Brinkman penalisation.  With
+ * M_e the mass matrix of cell e on the velocity component space (|e| times the compile-time table of means of
+ * phi_i phi_j):   D = sum_e sigma_e M_e,   A += theta D,   b_first += D u_t - (1 - theta) D u_1.
+ *
+ * ox_drag_sigma: for list entry k, cell e = zone_cells[k] (kernel cell positions; an entry outside the table is skipped):
+ *   sigma[e] = alpha[k] + beta[k] |w(x_e)|,   w = uab - ut (ut == NULL: uab) at the centroid x_e;
+ * a w that is not finite gives NaN.  No other entry of sigma (device [n_cells], kernel cell order, zero outside the
+ * zones) is written.  uab, ut interleaved [n_u][gdim].  One lane per list entry. */
+int ox_drag_sigma(int u_degree, const ox_cells *cells, const int32_t *cell_vdofs, int64_t n_zone, const int32_t *zone_cells,
+                  const double *alpha, const double *beta, const double *uab, const double *ut, double *sigma, void *stream);
+/* For every row r of the listed slices (slice_list: device [n_list], slices with a row adjacent to a zone cell and at
+ * most lds_width entries per row -- an even number; a wider slice is skipped: the caller launches per width bin of the
+ * pattern), over its (cell e, local index i) pairs in the order of space->adj, cells with sigma[e] == 0 skipped, and the
+ * cell's dofs j:   m = sigma[e] |e| MASSD[i][j];   acc[adj_pos[pair][j]] += theta m (from 0, in that order);
+ *   rb[:] += m w[dof_j][:]   (w: device [n_u][gdim], the caller's u_t - (1 - theta) u_1, or NULL: no right-hand side);
+ * then A->vals[slot k of row r] += acc[k] and b_first[r][:] += rb[:].  A row no such cell touches is not written.  A
+ * carries the pattern of the space (M, K and A share it); theta in [0.5, 1].  One lane per row, which owns that row of the
+ * matrix and of b_first; the accumulator is wave-private LDS (lds_width x 512 B per wave): no atomics, a fixed order of
+ * sums, equal bits for equal inputs.  No table beyond sigma and the slice list is read. */
+int ox_drag_rows(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, int64_t n_list,
+                 const int32_t *slice_list, int lds_width, const double *sigma, double theta, const double *w,
+                 double *b_first, void *stream);
+/* ft[k][:] = sigma[e] int_e (u - ut) dx for e = zone_cells[k] (exact: the means of the basis are the column sums of the
+ * mass table; an entry outside the table leaves NaN); device [n_zone][gdim].  The sums per zone and the ring are
+ * ox_wall_forces' (cells sorted by zone, tag_ptr the zones' segments): with rho < 0 there, the force the fluid exerts on
+ * the medium, +|rho| sum ft. */
+int ox_drag_force_cells(int u_degree, const ox_cells *cells, const int32_t *cell_vdofs, int64_t n_zone,
+                        const int32_t *zone_cells, const double *sigma, const double *u, const double *ut, double *ft,
+                        void *stream);
+
 /* ---- H1 + collectives: mesh-partitioned runs (one process per GPU, RCCL) -------------- */
 int ox_comm_unique_id(char *id128);   /* ncclGetUniqueId on rank 0 (broadcast it out of band) */
 int ox_comm_create(const char *id128, int rank, int nranks, void **comm_out); /* ncclCommInitRank */

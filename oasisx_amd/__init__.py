@@ -8,6 +8,7 @@ import logging
 from . import fem, geometry, io, mesh  # noqa: F401
 from .bcs import DirichletBC, LocatorMethod, PressureBC
 from .diagnostics import FlowDiagnostics, FlowStatistics, ProfileStatistics, slab_bins
+from .drag import DragZone
 from .fracstep import FractionalStep_AB_CN
 from .function import Projector
 from .geometry import Probes, WallDistance  # noqa: F401
@@ -38,6 +39,7 @@ __all__ = [
     "VanDriest",
     "WallDistance",
     "CellViscosity",
+    "DragZone",
     "CarreauYasuda",
     "Cross",
     "PowerLaw",

@@ -441,6 +441,9 @@ SIGNATURES = {
     "ox_outlet_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P]),
     "ox_outlet_update": (_I, [_I, _P, _P, _P, _L, _L, _P, _D, _P, _P, _P, _P, _P, _L, _P]),
     "ox_outlet_backflow": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P]),
+    "ox_drag_sigma": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "ox_drag_rows": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), _L, _P, _I, _P, _D, _P, _P, _P]),
+    "ox_drag_force_cells": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P, _P, _P]),
     "ox_profile_begin": (_I, [_I, _I]),
     "ox_profile_end": (_I, []),
     "ox_profile_get": (_I, [_I, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_D)]),

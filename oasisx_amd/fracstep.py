@@ -120,12 +120,17 @@ class FractionalStep_AB_CN:
         stress_form: ``"laplacian"`` (default): ``div(nut grad u)``, today's path; ``"full"``: ``div(nut (grad u + grad u^T))``,
             the transposed term explicit in ``u_ab`` on the right-hand side (``ox_assemble_stress_transpose``); needs a
             ``viscosity_model``
+        drag: a :class:`oasisx_amd.DragZone` or a list of them: cells with the volume term ``-sigma (u - u_t)``,
+            ``sigma = darcy + forchheimer |u_ab - u_t|`` per cell (porous media, sponge layers, penalised solids), added to
+            ``A`` and ``b_first`` inside ``assemble_first`` (``drag_assemble``, :mod:`oasisx_amd.drag`); ``None``: no drag
+            call is made.  One GPU only; not with ``rotational=True``
+        drag_theta: implicitness of the drag term in [0.5, 1]: 1 (default) backward Euler, 0.5 Crank-Nicolson
     """
 
     def __init__(self, mesh, u_element, p_element, bcs_u, bcs_p, rotational: bool = False,
                  solver_options: dict | None = None, jit_options: dict | None = None,
                  body_force=None, options: dict | None = None, scalars=None, viscosity_model=None,
-                 stress_form: str = "laplacian"):
+                 stress_form: str = "laplacian", drag=None, drag_theta: float = 1.0):
         if stress_form not in ("laplacian", "full"):
             raise ValueError(f'stress_form: "laplacian" or "full" is expected (got {stress_form!r})')
         if stress_form == "full" and viscosity_model is None:
@@ -143,6 +148,11 @@ class FractionalStep_AB_CN:
 
             check_model(viscosity_model, mesh, rotational, scalars)
         self._viscosity_model = viscosity_model
+        drag_selections = None
+        if drag is not None and not (isinstance(drag, (list, tuple)) and len(drag) == 0):
+            from .drag import check_zones
+
+            drag_selections = check_zones(drag, mesh, rotational, drag_theta)
         self._lib = _lib.load()  # fails loudly when the HIP library is missing
         self._mesh = mesh
         gdim = mesh.geometry.dim
@@ -285,6 +295,11 @@ class FractionalStep_AB_CN:
                 self._outlet_models = OutletGroup(self, with_model)
             if with_backflow:
                 self._outlet_backflow = Backflow(self, with_backflow)
+        self._drag = None
+        if drag_selections:  # drag zones (drag.py): sigma per cell, the touched slices, the target block
+            from .drag import DragGroup
+
+            self._drag = DragGroup(self, drag, drag_theta, drag_selections)
         self._nut = None
         if viscosity_model is not None:  # nut per cell, in the kernels' cell order
             self._nut = torch.zeros(int(self._geom.shape[0]), dtype=torch.float64, device=dev)
@@ -444,8 +459,8 @@ class FractionalStep_AB_CN:
         self._AU1_valid = False
         want_au = bool(self._solver_u._options.get("ksp_initial_guess_nonzero", False)) and \
             str(self._solver_u._options.get("ksp_type", "")).lower() != "preonly"
-        if self._outlet_backflow is not None:  # A changes after the fused kernel: its A u1 by-product is not asked for
-            want_au = False
+        if self._outlet_backflow is not None or self._drag is not None:
+            want_au = False  # A changes after the fused kernel: its A u1 by-product is not asked for
         if self._viscosity_model is not None:
             base = getattr(self._viscosity_model, "base_viscosity", None)
             if base is not None and float(nu) != base:
@@ -477,6 +492,8 @@ class FractionalStep_AB_CN:
             bcp.add_surface_terms(self._BFIRST)
         if self._outlet_backflow is not None:  # before the identity rows: Dirichlet rows win on rim dofs
             self.backflow_assemble()
+        if self._drag is not None:  # after the scalars (their A_c comes from A without drag), before the identity rows
+            self.drag_assemble()
         # NOTE (reference :470): rows of the FIRST component's BCs only
         for bcu in self._bcs_u[0]:  # identity rows; (A @ u1)[row] = u1[row] there, in the same launch
             self._A.zero_rows(bcu._rows_dev, 1.0, self._B3.ptr() if want_au else None,
@@ -500,6 +517,23 @@ class FractionalStep_AB_CN:
         if self._outlet_backflow is None:
             raise RuntimeError("backflow_assemble: no PressureBC of the solver has backflow > 0")
         self._outlet_backflow.add()
+
+    @_phase
+    def drag_assemble(self):
+        """``A += theta D``, ``b_first += D u_t - (1 - theta) D u_1`` with ``D = sum_c sigma_c M_c`` over the cells of the
+        drag zones (``ox_drag_sigma`` from the ``u_ab`` block ``assemble_first`` has just formed, where a zone has a
+        ``forchheimer`` part; ``ox_drag_rows``); runs inside ``assemble_first``, after the scalars' operators were taken from
+        ``A`` and before the velocity's identity rows."""
+        if self._drag is None:
+            raise RuntimeError("drag_assemble: the solver was built without drag zones (drag=)")
+        self._drag.add()
+
+    def drag_coefficient(self) -> torch.Tensor:
+        """``sigma`` per cell of the last ``assemble_first`` (zero outside the zones): a device tensor ``(num_cells,)`` in
+        the MESH's cell order."""
+        if self._drag is None:
+            raise RuntimeError("drag_coefficient: the solver was built without drag zones (drag=)")
+        return self._drag.coefficient()
 
     @_phase
     def viscosity_assemble(self, nu=None, dt=None):
