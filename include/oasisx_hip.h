@@ -909,6 +909,58 @@ int ox_walldist_info(const ox_walldist *wd, int64_t *n_facets, int64_t *n_bins, 
 int ox_walldist_query(const ox_walldist *wd, int64_t n_points, const double *x, const double *shift, int merge,
                       double *dist, int32_t *nearest, void *stream);
 
+/* ---- Inertial particles (ox_probe.hip) ----------------------------------------------------------
+ * Point particles, one-way coupled: dx/dt = v, dv/dt = (f / tau_p)(u(x, t) - v) + beta g, with the tracers' field
+ * u(x, theta) = fma(theta, u_b - u_a, u_a), beta = 1 - rho_f / rho_p, f = 1 (OX_PARTICLE_STOKES) or 1 + 0.15 Re_p^0.687,
+ * Re_p = diam |u - v| / nu (OX_PARTICLE_SCHILLER_NAUMANN).  One lane per live particle (status 0), all substeps in
+ * registers.  A substep of h = dt / substeps from (x, v) at theta_s = s / substeps: u0 = the field at x (in cell[i]); f of
+ * (u0, v), frozen; tau_e = tau_p / f; w = u0 + tau_e beta g; tau_e == 0: E = phi = 0, else E = exp(-h / tau_e),
+ * phi = tau_e (-expm1(-h / tau_e));  x_new = x + h w + phi (v - w), v_new = w + E (v - w)  (OX_PARTICLE_EXP1).
+ * OX_PARTICLE_EXP2: the position of the same formulas with h / 2 is folded and located, u_m = the field there at
+ * theta = (s + 1/2) / substeps, and the update uses w_m = u_m + tau_e beta g (f, tau_e of the start).
+ * Every predictor and end point is folded into [lo, hi) on the axes with periodic[k] != 0 before it is located (the rule of
+ * ox_tracer_advance); wraps[i][gdim] counts the images, so that x + wraps * period is the unfolded position; path adds
+ * the unfolded step.  A point in no cell leaves the particle at the substep's start with status 1, t_exit = t + theta_s dt,
+ * cell -1; a non-finite position or velocity or an index out of range does the same with status 2.  A second launch on the
+ * same stream takes the particles that left in THIS call (every other lane returns at once): the nearest facet of
+ * `walls` to the folded point that lay in no cell, by the ring walk of ox_walldist_query (ties: the lower position), goes
+ * to facet[i]; where facet_action[facet] == 1 the status becomes 3 (deposited) and v = 0.
+ *   loc, cell_dofs, cell_inv, u_a, u_b, x, cell, status, age, path, t_exit: as ox_tracer_args.  walls: a structure over the
+ *   exterior facets, n_facets == its facet count == the length of facet_action.  v [n][gdim], wraps [n][gdim], facet [n]
+ *   (-1: none), tau_p, diam, beta [n]: the particles; xq [n][gdim]: work space (the points that left).  nu >= 0 (> 0 for
+ *   Schiller-Naumann).  Arguments are checked on the host before the first device call; n == 0 launches nothing. */
+#define OX_PARTICLE_EXP1 0
+#define OX_PARTICLE_EXP2 1
+#define OX_PARTICLE_STOKES 0
+#define OX_PARTICLE_SCHILLER_NAUMANN 1
+typedef struct ox_particle_args {
+  const ox_locator *loc;
+  const ox_walldist *walls;
+  int degree, gdim, nc;
+  const int32_t *cell_dofs;
+  int64_t n_cells, n_rows;
+  const int64_t *cell_inv;
+  int64_t n_mesh_cells;
+  const double *u_a, *u_b;
+  double t, dt;
+  int substeps, scheme, drag, use_hint;
+  double tol, nu;
+  double g[3];
+  int periodic[3];
+  double lo[3], hi[3], period[3];
+  const int32_t *facet_action; /* [n_facets] 1: deposit */
+  int64_t n_facets;
+  int64_t n;
+  double *x, *v;
+  int64_t *cell;
+  int32_t *status;
+  double *age, *path, *t_exit;
+  int32_t *wraps, *facet;
+  double *xq;
+  const double *tau_p, *diam, *beta;
+} ox_particle_args;
+int ox_particle_advance(const ox_particle_args *args, void *stream);
+
 /* ---- Passive scalar transport (ox_scalar.hip) ------------------------------------------------------------------------
  * The Crank-Nicolson system of a group of 1..OX_MAXC scalars (same diffusivity kappa, same Dirichlet rows) from the
  * matrices of the velocity step, in ONE pass over the shared SELL-64 pattern -- no element loop:

@@ -14,6 +14,7 @@ from .function import Projector
 from .geometry import Probes, WallDistance  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
+from .particles import DEPOSITED, InertialParticles
 from .scalar import ScalarFlux, ScalarTransport
 from .tracers import Tracers
 from .viscosity import (CarreauYasuda, CellViscosity, Cross, DynamicSmagorinsky, PatchFilter, PowerLaw, Smagorinsky, VanDriest,
@@ -48,6 +49,8 @@ __all__ = [
     "Resistance",
     "Windkessel",
     "Tracers",
+    "InertialParticles",
+    "DEPOSITED",
     "FlowDiagnostics",
     "FlowStatistics",
     "ProfileStatistics",

@@ -277,6 +277,56 @@ class ox_tracer_args(C.Structure):
     ]
 
 
+PARTICLE_SCHEMES = {"exp1": 0, "exp2": 1}  # OX_PARTICLE_EXP1 / _EXP2
+PARTICLE_DRAG = {"stokes": 0, "schiller_naumann": 1}  # OX_PARTICLE_STOKES / _SCHILLER_NAUMANN
+
+
+class ox_particle_args(C.Structure):
+    _fields_ = [
+        ("loc", C.c_void_p),
+        ("walls", C.c_void_p),
+        ("degree", C.c_int),
+        ("gdim", C.c_int),
+        ("nc", C.c_int),
+        ("cell_dofs", C.c_void_p),
+        ("n_cells", C.c_int64),
+        ("n_rows", C.c_int64),
+        ("cell_inv", C.c_void_p),
+        ("n_mesh_cells", C.c_int64),
+        ("u_a", C.c_void_p),
+        ("u_b", C.c_void_p),
+        ("t", C.c_double),
+        ("dt", C.c_double),
+        ("substeps", C.c_int),
+        ("scheme", C.c_int),
+        ("drag", C.c_int),
+        ("use_hint", C.c_int),
+        ("tol", C.c_double),
+        ("nu", C.c_double),
+        ("g", C.c_double * 3),
+        ("periodic", C.c_int * 3),
+        ("lo", C.c_double * 3),
+        ("hi", C.c_double * 3),
+        ("period", C.c_double * 3),
+        ("facet_action", C.c_void_p),
+        ("n_facets", C.c_int64),
+        ("n", C.c_int64),
+        ("x", C.c_void_p),
+        ("v", C.c_void_p),
+        ("cell", C.c_void_p),
+        ("status", C.c_void_p),
+        ("age", C.c_void_p),
+        ("path", C.c_void_p),
+        ("t_exit", C.c_void_p),
+        ("wraps", C.c_void_p),
+        ("facet", C.c_void_p),
+        ("xq", C.c_void_p),
+        ("tau_p", C.c_void_p),
+        ("diam", C.c_void_p),
+        ("beta", C.c_void_p),
+    ]
+
+
 class ox_lagrangian_args(C.Structure):
     _fields_ = [
         ("loc", C.c_void_p),
@@ -424,6 +474,7 @@ SIGNATURES = {
     "ox_eval_points": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _P]),
     "ox_probe_sample": (_I, [_I, _I, _P, _L, _L, _L, _P, _P, _P, _P, _I, _I, _P, _L, _L, _L, _L, _P]),
     "ox_tracer_advance": (_I, [C.POINTER(ox_tracer_args), _P]),
+    "ox_particle_advance": (_I, [C.POINTER(ox_particle_args), _P]),
     "ox_dynamic_lagrangian": (_I, [C.POINTER(ox_lagrangian_args), _P]),
     "ox_walldist_create": (_I, [_I, _P, _L, C.POINTER(_I), _P, C.POINTER(_P)]),
     "ox_walldist_destroy": (_I, [_P]),

@@ -627,6 +627,154 @@ __global__ __launch_bounds__(256) void k_tracer_advance(TracerParams P) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Inertial particles: dx/dt = v, dv/dt = (f / tau_p)(u(x, t) - v) + beta g, one lane per particle,
+// all substeps and both stages in registers, the tracers' locate / gather / blend.  A substep of h from (x, v) at theta_s
+// freezes the drag factor f (1, or Schiller-Naumann's 1 + 0.15 Re_p^0.687 of the start) and the fluid velocity
+// (exp1: of the start; exp2: of the exponential half step's end at theta_s + 1 / (2 substeps)) and integrates the linear
+// equation exactly: with tau_e = tau_p / f, w = u + tau_e beta g, E = exp(-h / tau_e), phi = tau_e (1 - E) [as -expm1],
+//   x_new = x + h w + phi (v - w),  v_new = w + E (v - w);   tau_e == 0: E = phi = 0 (the tracers' Euler / midpoint rule).
+// Every predictor and end point is folded into [lo, hi) on the periodic axes before it is located; the image counts go to
+// wraps.  A point in no cell freezes the particle at the substep's start with status 1 exactly as a tracer, and the
+// (folded) point goes to xq with facet = -2: k_particle_classify, the second launch, names its nearest exterior facet.
+// No LDS, no atomics, no cross-lane traffic; every loop is bounded by substeps or a clamped list range.
+#define OX_PARTICLE_PENDING (-2)
+struct ParticleParams {
+  double *v;          // [n][D]
+  int32_t *wraps;     // [n][D]
+  int32_t *facet;     // [n]
+  double *xq;         // [n][D] the point that left, for the classification
+  const double *tau_p, *diam, *beta;  // [n]
+  double g[3], nu;
+  int drag;
+  int periodic[3];
+  double lo[3], hi[3], period[3];
+};
+
+// x folded into [lo, hi) on the periodic axes (the fold of k_dyn_lagrangian); w: the images it went through
+template <int D>
+__device__ __forceinline__ void particle_fold(const ParticleParams &A, double (&x)[D], int (&w)[D]) {
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    w[k] = 0;
+    if (A.periodic[k]) {
+      const double q = floor((x[k] - A.lo[k]) / A.period[k]);
+      double xk = x[k] - A.period[k] * q;
+      int n = (q >= -2147483647.0 && q <= 2147483647.0) ? (int)q : 0;  // (a non-finite x: caught by the caller)
+      if (xk >= A.hi[k]) xk -= A.period[k], n += 1;
+      x[k] = xk, w[k] = n;
+    }
+  }
+}
+
+// E = exp(-h / tau_e), phi = tau_e (1 - E); tau_e == 0: both 0
+__device__ __forceinline__ void particle_coef(double h, double tau_e, double &E, double &phi) {
+  E = 0.0, phi = 0.0;
+  if (tau_e != 0.0) {
+    const double r = h / tau_e;
+    E = exp(-r);
+    phi = tau_e * (-expm1(-r));
+  }
+}
+
+template <int D, int DEG>
+__global__ __launch_bounds__(256) void k_particle_advance(TracerParams P, ParticleParams A) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= P.n) return;
+  if (P.status[i] != 0) return;
+  double x[D], v[D], g[D];
+  int wraps[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = P.x[i * D + k], v[k] = A.v[i * D + k], wraps[k] = A.wraps[i * D + k], g[k] = A.g[k];
+  int64_t cell = P.cell[i];
+  double age = P.age[i], path = P.path[i], t_exit = P.t_exit[i];
+  const double tau_p = A.tau_p[i], diam = A.diam[i], beta = A.beta[i];
+  const double m = (double)P.substeps, h = P.dt / m;
+  int status = 0;
+  double xs[D];  // the point of the last move: the one that left, where the status becomes 1
+#pragma unroll
+  for (int k = 0; k < D; ++k) xs[k] = x[k];
+  const int n_stages = P.scheme == 1 ? 2 : 1;
+  for (int s = 0; s < P.substeps && status == 0; ++s) {
+    // point j: 0 the start (in `cell`), 0 < j < n_stages the exponential half step's end, j == n_stages the end point; every
+    // point but the start is folded and located, every point but the end gives the fluid velocity of the next move
+    double u[D], w[D], xu[D], vn[D], lam[D + 1];
+    int ws[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) w[k] = 0.0, xu[k] = x[k], vn[k] = v[k], ws[k] = 0;
+    double tg = 0.0, tau_e = 0.0;
+    for (int j = 0; j <= n_stages && status == 0; ++j) {
+      if (j == 0) {
+        if (cell < 0 || cell >= P.n_loc) status = 2;
+        else loc_bary<D>(P.x0, P.grad, cell, x, lam);
+      } else {
+        const double hq = j == n_stages ? h : 0.5 * h;
+        double E, phi;
+        particle_coef(hq, tau_e, E, phi);
+        bool finite = true;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+          const double dv = v[k] - w[k];
+          xu[k] = fma(phi, dv, fma(hq, w[k], x[k]));
+          vn[k] = fma(E, dv, w[k]);
+          xs[k] = xu[k];
+          finite = finite && isfinite(xu[k]) && isfinite(vn[k]);
+        }
+        if (!finite) status = 2;
+        else {
+          particle_fold<D>(A, xs, ws);
+          if (!tracer_locate<D>(P, xs, cell, lam)) status = 1;
+        }
+      }
+      if (status == 0 && j < n_stages) {
+        if (!tracer_velocity<D, DEG>(P, cell, lam, ((double)s + (j == 0 ? 0.0 : 0.5)) / m, u)) status = 2;
+        else {
+          if (j == 0) {  // the drag factor of the substep's start, frozen over the substep
+            double f = 1.0;
+            if (A.drag == 1) {
+              double r2 = 0.0;
+#pragma unroll
+              for (int k = 0; k < D; ++k) {
+                const double d = u[k] - v[k];
+                r2 = fma(d, d, r2);
+              }
+              f = fma(0.15, pow(diam * sqrt(r2) / A.nu, 0.687), 1.0);
+            }
+            tau_e = tau_p / f;
+            tg = tau_e * beta;
+          }
+#pragma unroll
+          for (int k = 0; k < D; ++k) w[k] = fma(tg, g[k], u[k]);
+        }
+      }
+    }
+    if (status == 0) {
+      double d2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const double d = xu[k] - x[k];  // (the unfolded step)
+        d2 = fma(d, d, d2);
+        x[k] = xs[k], v[k] = vn[k], wraps[k] += ws[k];
+      }
+      path += sqrt(d2);
+      age += h;
+    } else {
+      t_exit = tracer_exit_time(P.t, (double)s / m, P.dt);
+      cell = -1;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) P.x[i * D + k] = x[k], A.v[i * D + k] = v[k], A.wraps[i * D + k] = wraps[k];
+  P.cell[i] = cell;
+  P.status[i] = status;
+  P.age[i] = age, P.path[i] = path, P.t_exit[i] = t_exit;
+  if (status == 1) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) A.xq[i * D + k] = xs[k];
+    A.facet[i] = OX_PARTICLE_PENDING;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Lagrangian averaging of the dynamic Smagorinsky model: one lane per vertex class traces its path
 // line back over h with the patch-mean velocity, x' = x_v - h u_v (folded into the box on periodic axes), finds the cell
 // of x' by the tracers' rule (tracer_locate with the patch's first cell as the hint), interpolates the OLD pair
@@ -1178,31 +1326,13 @@ __device__ __forceinline__ double wd_facet_d2(const double *__restrict__ f, cons
   return wd_dot3(d, d);
 }
 
+// the ring walk of a finite point x: (best, best_f) = the squared distance to the nearest facet and its position, ties to
+// the lower position; old_d: a distance known already (INFINITY: none) -- the walk may stop once nothing unmet beats it
 template <int D>
-__global__ __launch_bounds__(256) void k_wd_query(int64_t n, const double *__restrict__ xs, WdVec shift, int merge, LocGrid G,
-                                                  WdVec H, int64_t n_f, int64_t n_bins,
-                                                  const int64_t *__restrict__ bin_ptr, const int32_t *__restrict__ list,
-                                                  int64_t n_list, const double *__restrict__ xyz,
-                                                  double *__restrict__ dist, int32_t *__restrict__ nearest) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  double x[D];
-  bool finite = true;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    x[k] = xs[i * D + k] + shift.v[k];
-    finite = finite && isfinite(x[k]);
-  }
-  if (!finite) {  // touches no table
-    dist[i] = NAN, nearest[i] = -1;
-    return;
-  }
-  double old_d = INFINITY;
-  int32_t old_f = -1;
-  if (merge) {
-    old_d = dist[i], old_f = nearest[i];
-    if (!(old_d >= 0.0) || old_f < 0) old_d = INFINITY, old_f = -1;  // (nothing kept yet)
-  }
+__device__ __forceinline__ void wd_nearest(const double (&x)[D], const LocGrid &G, const WdVec &H, int64_t n_f, int64_t n_bins,
+                                           const int64_t *__restrict__ bin_ptr, const int32_t *__restrict__ list,
+                                           int64_t n_list, const double *__restrict__ xyz, double old_d, double &best_out,
+                                           int32_t &best_f_out) {
   // b: the point's bin, clamped; slack: what the roundings of loc_bin and of the edges below can move an edge by
   int b0 = 0, b1 = 0, b2 = 0;
   double slack = 0.0;
@@ -1255,11 +1385,73 @@ __global__ __launch_bounds__(256) void k_wd_query(int64_t n, const double *__res
     bound -= slack;
     if (bound > 0.0 && (best <= bound * bound || old_d < bound)) break;
   }
+  best_out = best, best_f_out = best_f;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_wd_query(int64_t n, const double *__restrict__ xs, WdVec shift, int merge, LocGrid G,
+                                                  WdVec H, int64_t n_f, int64_t n_bins,
+                                                  const int64_t *__restrict__ bin_ptr, const int32_t *__restrict__ list,
+                                                  int64_t n_list, const double *__restrict__ xyz,
+                                                  double *__restrict__ dist, int32_t *__restrict__ nearest) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double x[D];
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    x[k] = xs[i * D + k] + shift.v[k];
+    finite = finite && isfinite(x[k]);
+  }
+  if (!finite) {  // touches no table
+    dist[i] = NAN, nearest[i] = -1;
+    return;
+  }
+  double old_d = INFINITY;
+  int32_t old_f = -1;
+  if (merge) {
+    old_d = dist[i], old_f = nearest[i];
+    if (!(old_d >= 0.0) || old_f < 0) old_d = INFINITY, old_f = -1;  // (nothing kept yet)
+  }
+  double best;
+  int32_t best_f;
+  wd_nearest<D>(x, G, H, n_f, n_bins, bin_ptr, list, n_list, xyz, old_d, best, best_f);
   double d = sqrt(best);
   int32_t f = best_f;
   if (best_f < 0) d = NAN;  // (no facet with a finite distance)
   if (old_f >= 0 && (f < 0 || old_d < d || (old_d == d && old_f < f))) d = old_d, f = old_f;
   dist[i] = d, nearest[i] = f;
+}
+
+// The particles that left the mesh in this advance (facet == OX_PARTICLE_PENDING; every other lane returns at once): the
+// nearest exterior facet of the point that left, by the ring walk above; a facet whose action is 1 deposits the particle
+// (status 3, velocity 0).  facet = -1: no facet with a finite distance.
+template <int D>
+__global__ __launch_bounds__(256) void k_particle_classify(int64_t n, const double *__restrict__ xq, LocGrid G, WdVec H,
+                                                           int64_t n_f, int64_t n_bins, const int64_t *__restrict__ bin_ptr,
+                                                           const int32_t *__restrict__ list, int64_t n_list,
+                                                           const double *__restrict__ xyz, const int32_t *__restrict__ action,
+                                                           int32_t *__restrict__ facet, int32_t *__restrict__ status,
+                                                           double *__restrict__ v) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (facet[i] != OX_PARTICLE_PENDING) return;
+  double x[D];
+  bool finite = true;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    x[k] = xq[i * D + k];
+    finite = finite && isfinite(x[k]);
+  }
+  double best = INFINITY;
+  int32_t f = -1;
+  if (finite) wd_nearest<D>(x, G, H, n_f, n_bins, bin_ptr, list, n_list, xyz, (double)INFINITY, best, f);
+  facet[i] = f;
+  if (f >= 0 && (int64_t)f < n_f && action[f] == 1) {
+    status[i] = 3;
+#pragma unroll
+    for (int k = 0; k < D; ++k) v[i * D + k] = 0.0;
+  }
 }
 
 static void wd_free(ox_walldist *W) {
@@ -1356,6 +1548,87 @@ extern "C" int ox_walldist_query(const ox_walldist *W, int64_t n_points, const d
   else
     hipLaunchKernelGGL(k_wd_query<3>, grid, dim3(256), 0, st, n_points, x, s, merge ? 1 : 0, W->grid, H, W->n_f, W->n_bins,
                        W->bin_ptr, W->list, W->n_list, W->xyz, dist, nearest);
+  OX_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Inertial particles: the advance (k_particle_advance) and, behind it on the same stream, the classification of the
+// particles that left in it (k_particle_classify).
+extern "C" int ox_particle_advance(const ox_particle_args *a, void *stream) {
+  if (!a) OX_FAIL("ox_particle_advance: null argument (args)");
+  if (!a->loc || !a->walls) OX_FAIL("ox_particle_advance: null argument (loc, walls)");
+  if (a->gdim != 2 && a->gdim != 3) OX_FAIL("ox_particle_advance: gdim=%d", a->gdim);
+  if (a->degree < 1 || a->degree > 3) OX_FAIL("ox_particle_advance: degree %d (1..3)", a->degree);
+  if (a->nc < a->gdim || a->nc > OX_MAXC) OX_FAIL("ox_particle_advance: nc=%d (gdim=%d..%d)", a->nc, a->gdim, OX_MAXC);
+  if (a->substeps < 1 || a->substeps > OX_TRACER_MAX_SUBSTEPS)
+    OX_FAIL("ox_particle_advance: substeps=%d (1..%d)", a->substeps, OX_TRACER_MAX_SUBSTEPS);
+  if (a->scheme != OX_PARTICLE_EXP1 && a->scheme != OX_PARTICLE_EXP2) OX_FAIL("ox_particle_advance: scheme=%d", a->scheme);
+  if (a->drag != OX_PARTICLE_STOKES && a->drag != OX_PARTICLE_SCHILLER_NAUMANN) OX_FAIL("ox_particle_advance: drag=%d", a->drag);
+  if (!std::isfinite(a->dt) || !std::isfinite(a->t)) OX_FAIL("ox_particle_advance: dt=%g at t=%g is not finite", a->dt, a->t);
+  if (!std::isfinite(a->nu) || a->nu < 0.0) OX_FAIL("ox_particle_advance: nu=%g (finite, >= 0)", a->nu);
+  if (a->drag == OX_PARTICLE_SCHILLER_NAUMANN && !(a->nu > 0.0))
+    OX_FAIL("ox_particle_advance: the Schiller-Naumann law needs nu > 0 (nu=%g)", a->nu);
+  for (int k = 0; k < a->gdim; ++k) {
+    if (!std::isfinite(a->g[k])) OX_FAIL("ox_particle_advance: g[%d] is not finite", k);
+    if (a->periodic[k] && (!std::isfinite(a->lo[k]) || !std::isfinite(a->hi[k]) || !(a->period[k] > 0.0) ||
+                           !std::isfinite(a->period[k]) || !(a->hi[k] > a->lo[k])))
+      OX_FAIL("ox_particle_advance: periodic axis %d with box %g .. %g, period %g", k, a->lo[k], a->hi[k], a->period[k]);
+  }
+  const ox_locator *L = a->loc;
+  const ox_walldist *W = a->walls;
+  if (L->ids) OX_FAIL("ox_particle_advance: a locator over a selection of cells; particles take the whole-mesh locator");
+  if (L->gdim != a->gdim || W->gdim != a->gdim)
+    OX_FAIL("ox_particle_advance: loc->gdim=%d, walls->gdim=%d, gdim=%d", L->gdim, W->gdim, a->gdim);
+  if (a->n_mesh_cells != L->n_cells)
+    OX_FAIL("ox_particle_advance: n_mesh_cells=%lld, the locator holds %lld", (long long)a->n_mesh_cells, (long long)L->n_cells);
+  if (a->n_facets != W->n_f)
+    OX_FAIL("ox_particle_advance: n_facets=%lld, the wall structure holds %lld", (long long)a->n_facets, (long long)W->n_f);
+  if (!(a->tol >= 0.0) || a->tol > L->tol) OX_FAIL("ox_particle_advance: tol=%g, the grid was built for tol <= %g", a->tol, L->tol);
+  if (a->n < 0) OX_FAIL("ox_particle_advance: n=%lld", (long long)a->n);
+  if (a->n == 0) return 0;
+  if (!a->cell_dofs || !a->cell_inv || !a->u_a || !a->u_b || a->n_cells < 1 || a->n_rows < 1)
+    OX_FAIL("ox_particle_advance: null argument (cell_dofs, cell_inv, u_a, u_b)");
+  if (!a->x || !a->v || !a->cell || !a->status || !a->age || !a->path || !a->t_exit)
+    OX_FAIL("ox_particle_advance: null argument (x, v, cell, status, age, path, t_exit)");
+  if (!a->wraps || !a->facet || !a->xq || !a->tau_p || !a->diam || !a->beta || !a->facet_action)
+    OX_FAIL("ox_particle_advance: null argument (wraps, facet, xq, tau_p, diam, beta, facet_action)");
+  TracerParams P;
+  P.G = L->grid;
+  P.n_loc = L->n_cells, P.n_bins = L->n_bins, P.n_list = L->n_list;
+  P.bin_ptr = L->bin_ptr, P.list = L->list, P.x0 = L->x0, P.grad = L->grad;
+  P.cell_dofs = a->cell_dofs, P.n_cells = a->n_cells, P.n_rows = a->n_rows, P.cell_inv = a->cell_inv;
+  P.u_a = a->u_a, P.u_b = a->u_b, P.nc = a->nc;
+  P.t = a->t, P.dt = a->dt, P.tol = a->tol;
+  P.substeps = a->substeps, P.scheme = a->scheme, P.use_hint = a->use_hint ? 1 : 0;
+  P.n = a->n, P.x = a->x, P.cell = a->cell, P.status = a->status, P.age = a->age, P.path = a->path, P.t_exit = a->t_exit;
+  ParticleParams A;
+  memset(&A, 0, sizeof(A));
+  A.v = a->v, A.wraps = a->wraps, A.facet = a->facet, A.xq = a->xq;
+  A.tau_p = a->tau_p, A.diam = a->diam, A.beta = a->beta;
+  A.nu = a->nu, A.drag = a->drag;
+  for (int k = 0; k < a->gdim; ++k) {
+    A.g[k] = a->g[k];
+    A.periodic[k] = a->periodic[k] ? 1 : 0, A.lo[k] = a->lo[k], A.hi[k] = a->hi[k], A.period[k] = a->period[k];
+  }
+  hipStream_t st = ox_stream(stream);
+  const dim3 grid((unsigned)((a->n + 255) / 256)), blk(256);
+  switch (a->gdim * 10 + a->degree) {
+    case 21: hipLaunchKernelGGL((k_particle_advance<2, 1>), grid, blk, 0, st, P, A); break;
+    case 22: hipLaunchKernelGGL((k_particle_advance<2, 2>), grid, blk, 0, st, P, A); break;
+    case 23: hipLaunchKernelGGL((k_particle_advance<2, 3>), grid, blk, 0, st, P, A); break;
+    case 31: hipLaunchKernelGGL((k_particle_advance<3, 1>), grid, blk, 0, st, P, A); break;
+    case 32: hipLaunchKernelGGL((k_particle_advance<3, 2>), grid, blk, 0, st, P, A); break;
+    default: hipLaunchKernelGGL((k_particle_advance<3, 3>), grid, blk, 0, st, P, A); break;
+  }
+  OX_LAUNCH_CHECK();
+  const WdVec H{{W->h[0], W->h[1], W->h[2]}};
+  if (a->gdim == 2)
+    hipLaunchKernelGGL(k_particle_classify<2>, grid, blk, 0, st, a->n, a->xq, W->grid, H, W->n_f, W->n_bins, W->bin_ptr, W->list,
+                       W->n_list, W->xyz, a->facet_action, a->facet, a->status, a->v);
+  else
+    hipLaunchKernelGGL(k_particle_classify<3>, grid, blk, 0, st, a->n, a->xq, W->grid, H, W->n_f, W->n_bins, W->bin_ptr, W->list,
+                       W->n_list, W->xyz, a->facet_action, a->facet, a->status, a->v);
   OX_LAUNCH_CHECK();
   return 0;
 }

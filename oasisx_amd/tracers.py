@@ -55,7 +55,8 @@ class Tracers:
     of the measured combinations.  One GPU.
 
     On a periodic mesh (``mesh.make_periodic``) particles do NOT wrap: a particle that leaves through an identified face
-    leaves the geometric mesh and freezes with status 1, as at any other boundary."""
+    leaves the geometric mesh and freezes with status 1, as at any other boundary (``InertialParticles`` fold and count
+    the images; with ``response_time=0`` they are tracers that wrap)."""
 
     def __init__(self, velocity, points, scheme: str = "rk4", substeps: int = 1, tol: float = G.DEFAULT_TOL,
                  hint: bool = True, sort_every: int = 8, allow_missing: bool = False):
