@@ -1068,6 +1068,41 @@ int ox_outlet_backflow(int u_degree, const ox_cells *cells, const int32_t *cell_
                        int64_t n_facets, const int32_t *facet_rec, const double *beta, const double *uab, const double *u1,
                        double *a_vals, int64_t a_size, double *b_first, void *stream);
 
+/* ---- Flux and Robin conditions of a scalar group (ox_scalar.hip) ---------------------------------
+ * With n outward and kappa_eff whatever diffuses the scalar:   kappa_eff dc/dn = q   (q > 0 enters the domain) and
+ *   -kappa_eff dc/dn = (h + beta max(-u_ab . n, 0)) (c - c_inf),   Crank-Nicolson in c.
+ * Condition facets: one record per (facet, condition), sorted by facet id and then by the order of the conditions;
+ * facet_rec as for ox_outlet_backflow; q, c_inf: device [n_facets][nfd][nc], h: device [n_facets][nfd] -- nodal values at
+ * the facet's dofs (the cell's dofs that live on the facet, ascending), interpolated on the facet; beta: device
+ * [n_facets].  For row rows[i], over its pairs row_ptr[i] <= k < row_ptr[i+1] (condition facet pair_facet[k], on which the
+ * row is dof number pair_loc[k]; pairs in ascending record order), the facet's dofs s and the facet rule (w_q, x_q) of
+ * ox_outlet_backflow:   hq = h(x_q) + beta max(-u_ab(x_q) . n, 0),   e = (1/2) |f| sum_q w_q hq phi_r phi_s,
+ *   a_vals[pair_off[k * nfd + s]] += e  (a slot outside [0, a_size) is skipped),
+ *   b[rows[i]][col] += |f| sum_q w_q (q_col(x_q) + hq c_inf,col(x_q)) phi_r(x_q) - sum_s e c1[dof_s][col].
+ * robin == 0: h = beta = 0; pair_off, h, c_inf, beta, uab, c1 and a_vals are not read.  adv == 0: beta = 0; beta and uab
+ * are not read.  A pair or a record outside the tables adds nothing; a row outside [0, n_dofs) is not written.  One lane
+ * per row, which owns that row of the matrix and of b (device [n_dofs][nc], nc <= 3): no atomics, a fixed order of sums,
+ * equal bits for equal inputs. */
+typedef struct ox_scalar_bc_args {
+  int degree, nc, robin, adv;
+  int64_t n_rows;
+  const int32_t *rows;       /* [n_rows]                                        */
+  const int64_t *row_ptr;    /* [n_rows + 1]                                    */
+  const int32_t *pair_facet; /* [n_pairs]                                       */
+  const int32_t *pair_loc;   /* [n_pairs]                                       */
+  const int64_t *pair_off;   /* [n_pairs][nfd]                                  */
+  int64_t n_facets;
+  const int32_t *facet_rec;  /* [n_facets][2]                                   */
+  const double *q, *h, *c_inf, *beta;
+  const double *uab;         /* [n_dofs][gdim]                                  */
+  const double *c1;          /* [n_dofs][nc]                                    */
+  double *a_vals;
+  int64_t a_size;
+  double *b;                 /* [n_dofs][nc]                                    */
+  int64_t n_dofs;
+} ox_scalar_bc_args;
+int ox_scalar_boundary(const ox_cells *cells, const int32_t *cell_dofs, const ox_scalar_bc_args *args, void *stream);
+
 /* ---- Drag zones: -sigma(x, |u|) (u - u_t) in the momentum equation (ox_drag.hip) ---------------
  * Porous media (Darcy-Forchheimer), sponge layers that relax to a target field, solids by Brinkman penalisation.  With
  * M_e the mass matrix of cell e on the velocity component space (|e| times the compile-time table of means of

@@ -15,7 +15,7 @@ from .geometry import Probes, WallDistance  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
 from .particles import DEPOSITED, InertialParticles
-from .scalar import ScalarFlux, ScalarTransport
+from .scalar import FluxBC, RobinBC, ScalarFlux, ScalarTransport
 from .tracers import Tracers
 from .viscosity import (CarreauYasuda, CellViscosity, Cross, DynamicSmagorinsky, PatchFilter, PowerLaw, Smagorinsky, VanDriest,
                         Wale)
@@ -33,6 +33,8 @@ __all__ = [
     "PressureBC",
     "ScalarTransport",
     "ScalarFlux",
+    "FluxBC",
+    "RobinBC",
     "Smagorinsky",
     "DynamicSmagorinsky",
     "PatchFilter",

@@ -371,8 +371,36 @@ class ox_buoy_term(C.Structure):
     ]
 
 
+class ox_scalar_bc_args(C.Structure):
+    _fields_ = [
+        ("degree", C.c_int),
+        ("nc", C.c_int),
+        ("robin", C.c_int),
+        ("adv", C.c_int),
+        ("n_rows", C.c_int64),
+        ("rows", C.c_void_p),
+        ("row_ptr", C.c_void_p),
+        ("pair_facet", C.c_void_p),
+        ("pair_loc", C.c_void_p),
+        ("pair_off", C.c_void_p),
+        ("n_facets", C.c_int64),
+        ("facet_rec", C.c_void_p),
+        ("q", C.c_void_p),
+        ("h", C.c_void_p),
+        ("c_inf", C.c_void_p),
+        ("beta", C.c_void_p),
+        ("uab", C.c_void_p),
+        ("c1", C.c_void_p),
+        ("a_vals", C.c_void_p),
+        ("a_size", C.c_int64),
+        ("b", C.c_void_p),
+        ("n_dofs", C.c_int64),
+    ]
+
+
 PROF_TAG_BUOYANCY_ROWS = 190  # OX_TAG_BUOYANCY_ROWS of csrc/ox_kernels.h (ox_profile_get: key = 2 x terms + dictionary)
 PROF_TAG_SCALAR_ROWS_CELLVISC = 192  # OX_TAG_SCALAR_ROWS_CELLVISC (ox_profile_get: key = columns)
+PROF_TAG_SCALAR_BOUNDARY = 183  # OX_TAG_SCALAR_BOUNDARY, beside OX_TAG_OUTLET_BACKFLOW = 182 (ox_profile_get: key = rows)
 
 _P = C.c_void_p
 _I = C.c_int
@@ -489,6 +517,7 @@ SIGNATURES = {
     "ox_scalar_flux_cells": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _P, _D, _D, _P, _P, _P, _P, _P]),
     "ox_wall_stress": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _L, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P]),
     "ox_wall_forces": (_I, [_I, _I, _P, _P, _D, _P, _L, _L, _P]),
+    "ox_scalar_boundary": (_I, [C.POINTER(ox_cells), _P, C.POINTER(ox_scalar_bc_args), _P]),
     "ox_outlet_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P]),
     "ox_outlet_update": (_I, [_I, _P, _P, _P, _L, _L, _P, _D, _P, _P, _P, _P, _P, _L, _P]),
     "ox_outlet_backflow": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P]),

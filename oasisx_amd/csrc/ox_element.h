@@ -164,6 +164,38 @@ __device__ __forceinline__ void ox_facet_normal(const double (&Ga)[GDIM], double
   area = adet * ga * (GDIM == 3 ? 0.5 : 1.0);
 }
 
+// The facet rule of the backflow term and of the scalars' flux / Robin conditions: its size and tables, indexed at run
+// time (constant memory).  The facet basis at the rule's points is the same on every local facet (facet dofs and points
+// both in ascending local vertex order).
+template <int GDIM, int DU>
+struct ox_facet_rule {
+  static constexpr int NP = DU == 1 ? 2 : (DU == 2 ? 4 : 5);
+  static constexpr int NQ = GDIM == 2 ? NP : NP * NP;
+  static constexpr int NFD = GDIM == 2 ? DU + 1 : (DU + 1) * (DU + 2) / 2;
+  __device__ static double w(int q) { OX_FE_PICK(GDIM, DU, OX_OW, [q]); }
+  __device__ static double phi(int q, int j) { OX_FE_PICK(GDIM, DU, OX_OPHI, [q][j]); }
+  __device__ static int fd(int a, int j) { OX_FE_PICK(GDIM, DU, OX_OFD, [a][j]); }
+};
+
+// outward unit normal and measure of local facet a (0 <= a <= GDIM) from the cell's geometry record: the one row
+// grad lambda_a is selected as the rows are read, no G[GDIM + 1][GDIM] is kept
+template <int GDIM>
+__device__ __forceinline__ void ox_facet_geometry(const double *__restrict__ gp, int a, double (&n)[GDIM], double &area) {
+  double Ga[GDIM];
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) {
+    double g0 = 0.0, ga = 0.0;
+#pragma unroll
+    for (int b = 1; b <= GDIM; ++b) {
+      const double g = gp[(b - 1) * GDIM + d];
+      g0 -= g;
+      if (b == a) ga = g;
+    }
+    Ga[d] = a == 0 ? g0 : ga;
+  }
+  ox_facet_normal<GDIM>(Ga, ox_geom_adet<GDIM>(gp), n, area);
+}
+
 // f(std::integral_constant<int, a>) for the run-time local facet 0 <= a <= GDIM: one instantiation of f per facet
 template <int GDIM, class F>
 __device__ __forceinline__ void ox_facet_dispatch(int a, F &&f) {

@@ -148,6 +148,7 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_OUTLET_FLUX 180     // ox_outlet_flux (key = facets)
 #define OX_TAG_OUTLET_UPDATE 181   // ox_outlet_update (key = tags)
 #define OX_TAG_OUTLET_BACKFLOW 182 // ox_outlet_backflow (key = rows)
+#define OX_TAG_SCALAR_BOUNDARY 183 // ox_scalar_boundary (key = rows)
 #define OX_TAG_DRAG_SIGMA 185       // ox_drag_sigma (key = zone cells)
 #define OX_TAG_DRAG_ROWS 186        // ox_drag_rows (key = touched slices)
 #define OX_TAG_DRAG_FORCE_CELLS 187 // ox_drag_force_cells (key = zone cells)

@@ -20,37 +20,6 @@
 
 namespace {
 
-// The facet rule of the backflow term: its size and tables, indexed at run time (constant memory).  The facet basis at
-// the rule's points is the same on every local facet (facet dofs and points both in ascending local vertex order).
-template <int GDIM, int DU>
-struct Outlet {
-  static constexpr int NP = DU == 1 ? 2 : (DU == 2 ? 4 : 5);
-  static constexpr int NQ = GDIM == 2 ? NP : NP * NP;
-  static constexpr int NFD = GDIM == 2 ? DU + 1 : (DU + 1) * (DU + 2) / 2;
-  __device__ static double w(int q) { OX_FE_PICK(GDIM, DU, OX_OW, [q]); }
-  __device__ static double phi(int q, int j) { OX_FE_PICK(GDIM, DU, OX_OPHI, [q][j]); }
-  __device__ static int fd(int a, int j) { OX_FE_PICK(GDIM, DU, OX_OFD, [a][j]); }
-};
-
-// outward unit normal and measure of local facet a (0 <= a <= GDIM) from the cell's geometry record: the one row
-// grad lambda_a is selected as the rows are read, no G[GDIM + 1][GDIM] is kept
-template <int GDIM>
-__device__ __forceinline__ void facet_geometry(const double *__restrict__ gp, int a, double (&n)[GDIM], double &area) {
-  double Ga[GDIM];
-#pragma unroll
-  for (int d = 0; d < GDIM; ++d) {
-    double g0 = 0.0, ga = 0.0;
-#pragma unroll
-    for (int b = 1; b <= GDIM; ++b) {
-      const double g = gp[(b - 1) * GDIM + d];
-      g0 -= g;
-      if (b == a) ga = g;
-    }
-    Ga[d] = a == 0 ? g0 : ga;
-  }
-  ox_facet_normal<GDIM>(Ga, ox_geom_adet<GDIM>(gp), n, area);
-}
-
 template <int GDIM, int DU>
 __global__ __launch_bounds__(256) void k_outlet_flux(ox_cells cells, const int32_t *__restrict__ vdofs, int64_t n_facets,
                                                      const int2 *__restrict__ rec, const double *__restrict__ u,
@@ -67,7 +36,7 @@ __global__ __launch_bounds__(256) void k_outlet_flux(ox_cells cells, const int32
   const int64_t e = r.x;
   const int32_t *__restrict__ dv = vdofs + (size_t)e * ND;
   double n[GDIM], area, ub[GDIM] = {};
-  facet_geometry<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), r.y, n, area);
+  ox_facet_geometry<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), r.y, n, area);
   // ub[d] = sum_i u[dof_i][d] mean_f(phi_i) on the local facet, in dof order; dofs with a zero mean are not read
   ox_facet_dispatch<GDIM>(r.y, [&](auto facet) {
     constexpr int A = decltype(facet)::value;
@@ -142,7 +111,7 @@ __global__ __launch_bounds__(256) void k_outlet_backflow(ox_cells cells, const i
                                                          const double *__restrict__ uab, const double *__restrict__ u1,
                                                          double *__restrict__ avals, int64_t a_size,
                                                          double *__restrict__ b_first) {
-  using O = Outlet<GDIM, DU>;
+  using O = ox_facet_rule<GDIM, DU>;
   constexpr int ND = ox_nd(GDIM, DU), NFD = O::NFD;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n_rows) return;
@@ -158,7 +127,7 @@ __global__ __launch_bounds__(256) void k_outlet_backflow(ox_cells cells, const i
     const int64_t e = r.x;
     const int a = r.y;
     double n[GDIM], area;
-    facet_geometry<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), a, n, area);
+    ox_facet_geometry<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), a, n, area);
     const double c = 0.5 * beta[fi] * area;
     size_t dvf[NFD];
     double un[NFD], ent[NFD];

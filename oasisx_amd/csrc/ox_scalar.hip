@@ -17,6 +17,14 @@
 //   k_buoyancy_rows   b_first[r][i] += sum_t coef_t[i] (M d_t)[r],  d_t = (c1 + 0.5 (c1 - c2)) - ref of up to OX_MAXC
 //                     coupled scalars, in one pass over M in the launch shape of k_scalar_rows
 //   k_scalar_flux     q = -kappa n . gbar(c) on tagged exterior facets, one lane per facet as k_wall_stress
+//
+// Flux and Robin conditions of a scalar group, after k_scalar_rows and before the Dirichlet rows:
+//   k_scalar_boundary one lane per touched row, shaped on k_outlet_backflow: the row's (condition facet, position among
+//                     the facet's dofs) pairs in ascending order, the slots of A_c's value array from set-up.  With the
+//                     facet rule (w_k, x_k), the nodal data interpolated on the facet and hq = h + beta max(-u_ab . n, 0):
+//                       e_rs = (1/2) |f| sum_k w_k hq phi_r phi_s,   A_c[r][s] += e_rs,
+//                       b_c[r][col] += |f| sum_k w_k (q_col + hq c_inf,col) phi_r - sum_s e_rs c_1[s][col]
+//                     The lane owns its row of A_c and of b_c: no atomics, no LDS, a fixed order of sums.
 #include "ox_element.h"
 
 namespace {
@@ -298,6 +306,124 @@ __global__ __launch_bounds__(256) void k_scalar_flux(ox_cells cells, const int32
   if (weight > 0.0) acc_q[f] = __dadd_rn(acc_q[f], __dmul_rn(weight, qv));
 }
 
+// ---- flux and Robin conditions ------------------------------------------------------------------------------------------
+// One lane per touched row.  Streamed per pair: 8 B of (facet, position) and, with ROBIN, NFD slots; gathered: the
+// facet's record and geometry, its nodal data (q, and with ROBIN h and c_inf: rows of NFD x nc doubles, read once per
+// pair) and, with ROBIN, the facet's dofs and c_1 there; with ADV u_ab at those dofs.  Live over the rule loop: hn, un,
+// ent, dvf (NFD each, ROBIN / ADV only), one column's qn and cn (NFD doubles each) and acc (OX_MAXC doubles): nothing
+// spills in any instance (profiles/scalar_bc_kernel_resources.txt).  A first form re-read the nodal data per rule point
+// to save registers and paid a round of loads per point: 0.155 against 0.076 ms for the backflow kernel on one face.
+// ROBIN = false reads neither A_c, c_1 nor u_ab; only ADV = true reads u_ab.
+template <int GDIM, int DU, bool ROBIN, bool ADV>
+__global__ __launch_bounds__(256) void k_scalar_boundary(ox_cells cells, const int32_t *__restrict__ dofs,
+                                                         ox_scalar_bc_args P) {
+  static_assert(ROBIN || !ADV, "the advective part belongs to a Robin condition");
+  using O = ox_facet_rule<GDIM, DU>;
+  constexpr int ND = ox_nd(GDIM, DU), NFD = O::NFD;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= P.n_rows) return;
+  const int nc = P.nc;
+  double acc[OX_MAXC];
+#pragma unroll
+  for (int c = 0; c < OX_MAXC; ++c) acc[c] = 0.0;
+  for (int64_t k = P.row_ptr[i]; k < P.row_ptr[i + 1]; ++k) {
+    const int64_t fi = P.pair_facet[k];
+    const int jr = P.pair_loc[k];
+    if (fi < 0 || fi >= P.n_facets || jr < 0 || jr >= NFD) continue;  // a pair outside the tables adds nothing
+    const int2 r = reinterpret_cast<const int2 *>(P.facet_rec)[fi];
+    if (!(r.x >= 0 && (int64_t)r.x < cells.n_cells && r.y >= 0 && r.y <= GDIM)) continue;
+    const int64_t e = r.x;
+    const int a = r.y;
+    double n[GDIM], area;
+    ox_facet_geometry<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), a, n, area);
+    const double *__restrict__ qf = P.q + (size_t)fi * NFD * nc;
+    const double *__restrict__ hf = ROBIN ? P.h + (size_t)fi * NFD : nullptr;
+    const double *__restrict__ cf = ROBIN ? P.c_inf + (size_t)fi * NFD * nc : nullptr;
+    size_t dvf[NFD];
+    double un[NFD], ent[NFD], hn[NFD];
+    double beta = 0.0;
+    if constexpr (ROBIN) {
+#pragma unroll
+      for (int j = 0; j < NFD; ++j) {
+        dvf[j] = (size_t)dofs[(size_t)e * ND + O::fd(a, j)];
+        hn[j] = hf[j];
+        ent[j] = 0.0;
+      }
+    }
+    if constexpr (ADV) {
+      beta = P.beta[fi];
+#pragma unroll
+      for (int j = 0; j < NFD; ++j) {
+        double s = 0.0;
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) s = fma(P.uab[dvf[j] * GDIM + d], n[d], s);
+        un[j] = s;
+      }
+    }
+    // column by column: the column's nodal q and c_inf are loaded once and stay in registers over the rule loop (no load
+    // inside it); hq is formed again per column -- 2 NFD multiply-adds per point, against a round of gathers -- by the same
+    // operations, so every column sees the same bits; the entries e_rs are summed in the first column's loop
+#pragma unroll
+    for (int c = 0; c < OX_MAXC; ++c)
+      if (c < nc) {
+        double qn[NFD], cn[NFD];
+#pragma unroll
+        for (int j = 0; j < NFD; ++j) {
+          qn[j] = qf[j * nc + c];
+          if constexpr (ROBIN) cn[j] = cf[j * nc + c];
+        }
+        double load = 0.0;
+        for (int q = 0; q < O::NQ; ++q) {
+          const double gr = O::w(q) * O::phi(q, jr);
+          double hq = 0.0;
+          if constexpr (ROBIN) {
+#pragma unroll
+            for (int j = 0; j < NFD; ++j) hq = fma(hn[j], O::phi(q, j), hq);
+          }
+          if constexpr (ADV) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < NFD; ++j) s = fma(O::phi(q, j), un[j], s);
+            hq = fma(beta, fmax(-s, 0.0), hq);
+          }
+          double v = 0.0;
+#pragma unroll
+          for (int j = 0; j < NFD; ++j) v = fma(qn[j], O::phi(q, j), v);
+          if constexpr (ROBIN) {
+            double ci = 0.0;
+#pragma unroll
+            for (int j = 0; j < NFD; ++j) ci = fma(cn[j], O::phi(q, j), ci);
+            v = fma(hq, ci, v);
+          }
+          load = fma(gr, v, load);
+          if (ROBIN && c == 0) {
+            const double g2 = gr * hq;
+#pragma unroll
+            for (int j = 0; j < NFD; ++j) ent[j] = fma(g2, O::phi(q, j), ent[j]);
+          }
+        }
+        acc[c] = fma(area, load, acc[c]);
+      }
+    if constexpr (ROBIN) {
+      const double hc = 0.5 * area;
+#pragma unroll
+      for (int j = 0; j < NFD; ++j) {
+        const double v = hc * ent[j];
+        const int64_t off = P.pair_off[(size_t)k * NFD + j];
+        if (off >= 0 && off < P.a_size) P.a_vals[off] += v;
+#pragma unroll
+        for (int c = 0; c < OX_MAXC; ++c)
+          if (c < nc) acc[c] = fma(-v, P.c1[dvf[j] * nc + c], acc[c]);
+      }
+    }
+  }
+  const int64_t row = P.rows[i];
+  if (row < 0 || row >= P.n_dofs) return;
+#pragma unroll
+  for (int c = 0; c < OX_MAXC; ++c)
+    if (c < nc) P.b[(size_t)row * nc + c] += acc[c];
+}
+
 }  // namespace
 
 extern "C" int ox_scalar_rows(const ox_sell *A, const ox_sell *M, const ox_sell *K, const ox_sell *Ac, double s, double dt,
@@ -394,4 +520,40 @@ extern "C" int ox_scalar_flux_cells(int degree, const ox_cells *cells, const int
   OX_FOR_GDIM_DEG(OX_SCALAR_FLUXC_CASE)
 #undef OX_SCALAR_FLUXC_CASE
   OX_FAIL("ox_scalar_flux_cells: unsupported gdim=%d, P%d", g, degree);
+}
+
+extern "C" int ox_scalar_boundary(const ox_cells *cells, const int32_t *cell_dofs, const ox_scalar_bc_args *args,
+                                  void *stream) {
+  if (!cells || !cells->geom || !cell_dofs || !args) OX_FAIL("ox_scalar_boundary: null argument");
+  const ox_scalar_bc_args &P = *args;
+  if (!P.rows || !P.row_ptr || !P.pair_facet || !P.pair_loc || !P.facet_rec || !P.q || !P.b)
+    OX_FAIL("ox_scalar_boundary: null argument");
+  if (P.adv && !P.robin) OX_FAIL("ox_scalar_boundary: adv without robin");
+  if (P.robin && (!P.pair_off || !P.h || !P.c_inf || !P.c1 || !P.a_vals || P.a_size <= 0))
+    OX_FAIL("ox_scalar_boundary: a Robin pass without its arrays");
+  if (P.adv && (!P.beta || !P.uab)) OX_FAIL("ox_scalar_boundary: an advective pass without beta or u_ab");
+  if (P.nc < 1 || P.nc > OX_MAXC) OX_FAIL("ox_scalar_boundary: nc=%d", P.nc);
+  if (P.n_rows <= 0) return 0;
+  if (P.n_rows > (int64_t)0x7fffffff || P.n_facets > (int64_t)0x7fffffff || cells->n_cells > (int64_t)0x7fffffff)
+    OX_FAIL("ox_scalar_boundary: %lld rows, %lld facets, %lld cells", (long long)P.n_rows, (long long)P.n_facets,
+            (long long)cells->n_cells);
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const unsigned nblk = (unsigned)((P.n_rows + 255) / 256);
+#define OX_SCALAR_BC_CASE(GD, DG)                                                                                      \
+  if (g == GD && P.degree == DG) {                                                                                     \
+    if (ox_prof_on) ox_prof_start(OX_TAG_SCALAR_BOUNDARY, st, P.n_rows);                                               \
+    if (P.adv) hipLaunchKernelGGL((k_scalar_boundary<GD, DG, true, true>), dim3(nblk), dim3(256), 0, st, *cells,       \
+                                  cell_dofs, P);                                                                       \
+    else if (P.robin) hipLaunchKernelGGL((k_scalar_boundary<GD, DG, true, false>), dim3(nblk), dim3(256), 0, st,       \
+                                         *cells, cell_dofs, P);                                                        \
+    else hipLaunchKernelGGL((k_scalar_boundary<GD, DG, false, false>), dim3(nblk), dim3(256), 0, st, *cells,           \
+                            cell_dofs, P);                                                                             \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                  \
+    OX_LAUNCH_CHECK();                                                                                                 \
+    return 0;                                                                                                          \
+  }
+  OX_FOR_GDIM_DEG(OX_SCALAR_BC_CASE)
+#undef OX_SCALAR_BC_CASE
+  OX_FAIL("ox_scalar_boundary: unsupported gdim=%d, P%d", g, P.degree);
 }

@@ -103,7 +103,9 @@ class FractionalStep_AB_CN:
             :class:`oasisx_amd.function.Expression` of fields (assembled once, as in the reference)
         scalars: list of :class:`oasisx_amd.ScalarTransport`: scalars on the velocity component space, advected by
             the extrapolated velocity and solved once per step after the velocity update (:mod:`oasisx_amd.scalar`);
-            ``None`` / ``[]``: no scalar phase runs.  A scalar is passive unless it is given ``buoyancy=b``: then
+            ``None`` / ``[]``: no scalar phase runs.  ``ScalarTransport(flux_bcs=[FluxBC, RobinBC])``: prescribed fluxes,
+            film and open-boundary conditions on exterior facets (``scalar_boundary_assemble``).
+            A scalar is passive unless it is given ``buoyancy=b``: then
             component ``i`` of the momentum equation gains the Boussinesq force ``b_i (c* - reference)``, with ``c*`` the
             scalar extrapolated to the step's midpoint, added to ``b_first`` inside ``assemble_first`` in one pass over the
             mass matrix (``buoyancy_assemble``); the coupling is explicit in ``c`` and conditionally stable.
@@ -320,6 +322,7 @@ class FractionalStep_AB_CN:
         self._scalar_groups, self._scalar_index = [], {}
         self._buoyancy = []
         self._A_pre_bc = False
+        self._scalar_rows_open = None  # the scalar group between its row kernel and its Dirichlet rows
         self._b_first_open = False  # inside assemble_first, between the fused kernel and the boundary terms of b_first
         if scalars:
             from . import scalar as _sc
@@ -761,6 +764,18 @@ class FractionalStep_AB_CN:
             _sc.assemble(self, g, dt, nu)
 
     @_phase
+    def scalar_boundary_assemble(self):
+        """The flux and Robin conditions of a scalar group (``flux_bcs=``): ``A_c += H/2``, ``b_c += load - (H/2) c_1``
+        (``ox_scalar_boundary``, with the ``u_ab`` block ``assemble_first`` has just formed).  Runs INSIDE
+        ``scalar_assemble``, per group, after its row kernel has written ``A_c`` and ``b_c`` and before its Dirichlet rows;
+        a group without such conditions never calls it."""
+        g = self._scalar_rows_open
+        if g is None or g.boundary is None:
+            raise RuntimeError("scalar_boundary_assemble runs inside assemble_first (whose scalar_assemble calls it): it "
+                               "adds to the A_c and b_c that the row kernel has just written, once per step")
+        g.boundary.add()
+
+    @_phase
     def buoyancy_assemble(self):
         """The Boussinesq forces of the coupled scalars: ``b_first_i += b_i M (c* - reference)``, ``c* = c_1 + 0.5 (c_1 -
         c_2)`` (``c_1`` without extrapolation), summed over the scalars with ``buoyancy=`` in one pass over the mass matrix
@@ -816,6 +831,8 @@ class FractionalStep_AB_CN:
             for m in g.members:
                 for bc in m.bcs:
                     bc.update_bc()
+                for bc in m.flux_bcs:
+                    bc.update()
         self.assemble_first(dt, nu)
         while inner_it < max_iter and diff > max_error:
             inner_it += 1

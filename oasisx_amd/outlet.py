@@ -288,39 +288,44 @@ def facet_dofs(d: int, degree: int, a: int) -> np.ndarray:
     return np.nonzero(np.abs(lagrange_basis(d, degree, p)).max(axis=0) > 1e-12)[0]
 
 
-class Backflow:
-    """The backflow pass of one solver: the facets of every ``PressureBC`` with ``backflow > 0`` in ascending facet id,
-    ``beta`` per facet; per touched velocity row its (facet, position among the facet's dofs) pairs and the slots of
-    ``A``'s value array, computed once from the velocity pattern."""
+class RowPairs:
+    """The row-centric set-up of a facet pass over the velocity component space (shared by :class:`Backflow` and the
+    scalars' flux / Robin pass, :mod:`oasisx_amd.scalar`): per touched owned row its (record, position among the record's
+    facet dofs) pairs, by row and then by record, and -- with ``slots`` -- per pair the slots of (row, facet dof s) in the
+    SELL value array of the space's pattern.  ``kpos`` / ``local_facets``: kernel cell and local facet per record (a facet
+    may occur in several records)."""
 
-    def __init__(self, solver, bcs):
+    def __init__(self, Vi, kpos, local_facets, dev, who: str, slots: bool = True):
         from .fem import KV, SLICE
 
-        mesh = solver._mesh
-        dev = mesh.device
-        d = mesh.gdim
-        ids = np.concatenate([np.asarray(b._facets, dtype=np.int64) for b in bcs])
-        beta = np.concatenate([np.full(b._facets.shape[0], b.backflow, dtype=np.float64) for b in bcs])
-        order = np.argsort(ids, kind="stable")
-        ids, beta = ids[order], beta[order]
-        self._set = _FacetSet(solver, ids, np.zeros(ids.shape[0], dtype=np.int64), 1, "PressureBC with backflow")
-        self._solver = solver
-        Vi = solver._Vi[0][0]
-        nf = ids.shape[0]
+        d = int(Vi.mesh.gdim)
+        nf = int(np.asarray(kpos).shape[0])
         table = np.stack([facet_dofs(d, Vi.degree, a) for a in range(d + 1)])  # (d + 1, nfd)
         nfd = table.shape[1]
-        cd = Vi.cell_dofs.cpu().numpy()[self._set.kpos]  # (nf, nd)
-        fd = np.take_along_axis(cd, table[self._set.local_facets], axis=1).astype(np.int64)  # (nf, nfd)
+        cd = Vi.cell_dofs.cpu().numpy()[kpos]  # (nf, nd)
+        fd = np.take_along_axis(cd, table[local_facets], axis=1).astype(np.int64)  # (nf, nfd)
         row = fd.reshape(-1)
         fi = np.repeat(np.arange(nf, dtype=np.int64), nfd)
         loc = np.tile(np.arange(nfd, dtype=np.int64), nf)
         keep = row < Vi.n_owned
         row, fi, loc = row[keep], fi[keep], loc[keep]
-        order = np.lexsort((fi, row))  # by row, then by facet (= ascending facet id)
+        order = np.lexsort((fi, row))  # by row, then by record (= ascending facet id)
         row, fi, loc = row[order], fi[order], loc[order]
         rows, counts = np.unique(row, return_counts=True)
         row_ptr = np.zeros(rows.shape[0] + 1, dtype=np.int64)
         row_ptr[1:] = np.cumsum(counts)
+        self.facet_dofs = fd
+        self.n_rows, self.nfd, self.n_pairs = int(rows.shape[0]), int(nfd), int(row.shape[0])
+        self.rows = torch.from_numpy(rows.astype(np.int32) if rows.size else np.zeros(1, dtype=np.int32)).to(dev)
+        self.row_ptr = torch.from_numpy(row_ptr).to(dev)
+        self.pair_facet = torch.from_numpy(fi.astype(np.int32) if fi.size else np.zeros(1, dtype=np.int32)).to(dev)
+        self.pair_loc = torch.from_numpy(loc.astype(np.int32) if loc.size else np.zeros(1, dtype=np.int32)).to(dev)
+        self.pair_off = None
+        if not slots:
+            return
+        if not row.size:  # an empty facet set: nothing is looked up
+            self.pair_off = torch.zeros(1, dtype=torch.int64, device=dev)
+            return
         # slots of (row, facet dof s) in the SELL value array of the velocity pattern
         P = Vi.pattern
         r = torch.from_numpy(row).to(dev)
@@ -336,14 +341,29 @@ class Backflow:
         for s in range(nfd):
             hit = (cols == want[:, s].unsqueeze(1)) & valid
             if not bool(hit.any(dim=1).all()):
-                raise RuntimeError("backflow: an entry of the facet mass matrix is not in the velocity pattern")
+                raise RuntimeError(f"{who}: an entry of the facet mass matrix is not in the velocity pattern")
             off[:, s] = torch.gather(slots, 1, hit.to(torch.int8).argmax(dim=1, keepdim=True)).squeeze(1)
-        self.n_rows, self.nfd = int(rows.shape[0]), int(nfd)
-        self.rows = torch.from_numpy(rows.astype(np.int32) if rows.size else np.zeros(1, dtype=np.int32)).to(dev)
-        self.row_ptr = torch.from_numpy(row_ptr).to(dev)
-        self.pair_facet = torch.from_numpy(fi.astype(np.int32) if fi.size else np.zeros(1, dtype=np.int32)).to(dev)
-        self.pair_loc = torch.from_numpy(loc.astype(np.int32) if loc.size else np.zeros(1, dtype=np.int32)).to(dev)
         self.pair_off = off.contiguous() if off.numel() else torch.zeros(1, dtype=torch.int64, device=dev)
+
+
+class Backflow:
+    """The backflow pass of one solver: the facets of every ``PressureBC`` with ``backflow > 0`` in ascending facet id,
+    ``beta`` per facet; per touched velocity row its (facet, position among the facet's dofs) pairs and the slots of
+    ``A``'s value array, computed once from the velocity pattern (:class:`RowPairs`)."""
+
+    def __init__(self, solver, bcs):
+        mesh = solver._mesh
+        dev = mesh.device
+        ids = np.concatenate([np.asarray(b._facets, dtype=np.int64) for b in bcs])
+        beta = np.concatenate([np.full(b._facets.shape[0], b.backflow, dtype=np.float64) for b in bcs])
+        order = np.argsort(ids, kind="stable")
+        ids, beta = ids[order], beta[order]
+        self._set = _FacetSet(solver, ids, np.zeros(ids.shape[0], dtype=np.int64), 1, "PressureBC with backflow")
+        self._solver = solver
+        rp = RowPairs(solver._Vi[0][0], self._set.kpos, self._set.local_facets, dev, "backflow")
+        self.n_rows, self.nfd = rp.n_rows, rp.nfd
+        self.rows, self.row_ptr, self.pair_facet, self.pair_loc, self.pair_off = (rp.rows, rp.row_ptr, rp.pair_facet,
+                                                                                  rp.pair_loc, rp.pair_off)
         self.beta = torch.from_numpy(beta if beta.size else np.zeros(1)).to(dev)
 
     def add(self) -> None:

@@ -20,8 +20,8 @@ scalar with ``turbulent_schmidt=Sc_t`` has the diffusivity ``kappa + nut_c / Sc_
 fused kernel without its convection turns and gathers) and streams the slices as ``ox_scalar_rows`` does.  ``Sc_t = 1``
 (``t = 0``) and a solver without a model run ``ox_scalar_rows``.
 
-Scalars with the same diffusivity specification (``turbulent_schmidt`` included) and the same set of Dirichlet rows form a GROUP: one matrix, solved in
-lock-step as the columns of one block solve (at most 3 columns; more open further groups).  One group costs one f64
+Scalars with the same diffusivity specification (``turbulent_schmidt`` included), the same set of Dirichlet rows and the same
+matrix-changing part of their ``flux_bcs`` (below) form a GROUP: one matrix, solved in lock-step as the columns of one block solve (at most 3 columns; more open further groups).  One group costs one f64
 value array of the velocity pattern in device memory.
 
 A scalar with ``buoyancy=b`` drives the flow (Boussinesq): component ``i`` of the momentum equation
@@ -32,6 +32,16 @@ gains ``b_i (c* - reference)`` with ``c* = c_1 + 0.5 (c_1 - c_2)``, the scalar a
 
 in one pass over ``M`` (``ox_buoyancy_rows``); ``A`` is not touched.  The coupling is explicit in ``c``.
 :class:`ScalarFlux` evaluates the diffusive flux ``-kappa n . grad c`` through tagged exterior facets on the device.
+
+Natural boundary conditions other than the insulated wall, ``flux_bcs=[FluxBC, RobinBC, ...]``: with
+``n`` outward and ``kappa_eff`` whatever diffuses the scalar::
+
+    FluxBC(q, facets):                  kappa_eff dc/dn = q                                   q > 0 ENTERS the domain
+    RobinBC(h, c_inf, facets, beta):   -kappa_eff dc/dn = (h + beta max(-u_ab . n, 0)) (c - c_inf)
+
+Crank-Nicolson in ``c``: ``A_c += H/2``, ``b_c += load - (H/2) c_1`` with ``H_rs = int hq phi_r phi_s ds`` and
+``load_r = int (q + hq c_inf) phi_r ds``, by ``ox_scalar_boundary`` after ``ox_scalar_rows`` and before the group's Dirichlet
+rows (which win on rim dofs): one lane per touched row, no atomics.
 """
 from __future__ import annotations
 
@@ -45,7 +55,7 @@ from .fem import FieldStorage, Function, Vector
 from .ksp import KSPSolver
 from .la import SellMatrix
 
-__all__ = ["ScalarTransport", "ScalarFlux"]
+__all__ = ["ScalarTransport", "ScalarFlux", "FluxBC", "RobinBC"]
 
 MAX_COLUMNS = 3  # OX_MAXC: the columns ox_ksp_solve / ox_spmv take in lock-step
 
@@ -74,10 +84,13 @@ class ScalarTransport:
             a finite float > 0 -- the scalar's diffusivity is ``kappa + nut_c / Sc_t`` per cell -- or ``float("inf")``: no
             turbulent diffusivity.  With a generalised-Newtonian law (whose ``nut`` belongs to the momentum alone) only
             ``inf`` is accepted.  Without a ``viscosity_model`` it has no effect
+        flux_bcs: list of :class:`FluxBC` / :class:`RobinBC`: prescribed fluxes, film and open-boundary conditions on
+            exterior facets (one GPU).  Several conditions may share a facet: their ``q`` and ``h`` add.  Without them
+            the natural condition is the insulated wall, and none of their calls is made
     """
 
     def __init__(self, name, diffusivity=None, schmidt=None, bcs=(), source=0.0, initial=None, buoyancy=None,
-                 reference=0.0, extrapolate=True, turbulent_schmidt=None):
+                 reference=0.0, extrapolate=True, turbulent_schmidt=None, flux_bcs=()):
         if not isinstance(name, str) or not name:
             raise ValueError("ScalarTransport: name must be a non-empty string")
         if (diffusivity is None) == (schmidt is None):
@@ -94,6 +107,11 @@ class ScalarTransport:
         for bc in self.bcs:
             if not isinstance(bc, DirichletBC):
                 raise TypeError(f"ScalarTransport {name!r}: bcs holds DirichletBC objects (got {type(bc).__name__})")
+        self.flux_bcs = list(flux_bcs)
+        for bc in self.flux_bcs:
+            if not isinstance(bc, (FluxBC, RobinBC)):
+                raise TypeError(f"ScalarTransport {name!r}: flux_bcs holds FluxBC and RobinBC objects (got "
+                                f"{type(bc).__name__})")
         from .function import Expression
 
         if not (callable(source) or isinstance(source, (Function, Expression))):
@@ -132,6 +150,246 @@ class ScalarTransport:
     def _spec(self):
         spec = ("kappa", self.diffusivity) if self.schmidt is None else ("schmidt", self.schmidt)
         return spec + (("turbulent_schmidt", self.turbulent_schmidt),)
+
+
+# ---- flux and Robin conditions -----------------------------------------------------------------------------------------
+def _datum(who, what, f):
+    """A float (checked finite) or a callable ``f(x)``, as given."""
+    if callable(f):
+        return f
+    v = float(f)
+    if not np.isfinite(v):
+        raise ValueError(f"{who}: {what} = {v}: a finite number is expected")
+    return v
+
+
+def _nodal(who, what, f, X, nonneg=False):
+    """The datum at the points ``X: (3, npts)``: (npts,) float64; non-finite (and, with ``nonneg``, negative) values raise
+    ``ValueError``."""
+    npts = X.shape[1]
+    v = np.broadcast_to(np.asarray(f(X) if callable(f) else f, dtype=np.float64), (npts,)).copy()
+    if not np.isfinite(v).all():
+        raise ValueError(f"{who}: {what} is not finite at {int((~np.isfinite(v)).sum())} of {npts} facet dofs")
+    if nonneg and (v < 0.0).any():
+        raise ValueError(f"{who}: {what} must be >= 0 (min {v.min()})")
+    return v
+
+
+class _FacetCondition:
+    """Common part of :class:`FluxBC` and :class:`RobinBC`: the facet selection and the link to the group's pass."""
+
+    def __init__(self, facets):
+        self.facets = facets
+        self._bound = []  # (pass of a scalar group, block): set when a solver takes the scalar
+
+    def facet_ids(self, mesh) -> np.ndarray:
+        """The exterior facets of the selection on ``mesh``, ascending; interior facets and facets on an identified
+        (periodic) face raise ``ValueError``."""
+        from .wall import facet_table, select_facets
+
+        who = type(self).__name__
+        ids, _, _ = select_facets(mesh, self.facets, who)
+        ids = np.sort(ids)
+        facet_table(mesh, ids, who, "flux and Robin conditions")
+        return ids
+
+    def update(self) -> None:
+        """Re-evaluate the condition's callables at the facet dofs (time-dependent data: ``FractionalStep_AB_CN.solve``
+        calls it where it calls ``update_bc`` of the Dirichlet conditions).  The values are used as they are: for second
+        order in time return the value at the step's midpoint."""
+        for bp, block in self._bound:
+            bp.evaluate(block)
+
+
+class FluxBC(_FacetCondition):
+    """A prescribed diffusive flux on exterior facets: ``kappa_eff dc/dn = q`` with ``n`` outward, so a positive ``q``
+    ENTERS the domain -- the opposite sign to :class:`ScalarFlux`, which reports the flux that leaves.  Independent of
+    ``kappa`` (neither ``schmidt=`` nor ``turbulent_schmidt=`` changes it).
+
+    Args:
+        q: a float or a callable ``f(x)`` on ``x: (3, npts)``, evaluated at the facets' dofs of the scalar's space and
+            interpolated on the facet
+        facets: what :func:`oasisx_amd.wall.select_facets` takes: ``(meshtags, id | ids)``, an array of exterior facet
+            ids (``None``: all exterior facets).  Interior facets and identified (periodic) facets raise ``ValueError``
+    """
+
+    def __init__(self, q, facets):
+        super().__init__(facets)
+        self.q = _datum("FluxBC", "q", q)
+
+
+class RobinBC(_FacetCondition):
+    """``-kappa_eff dc/dn = (h + advective max(-u_ab . n, 0)) (c - c_inf)`` on exterior facets, ``n`` outward.  ``h > 0``:
+    a film (Biot) condition or first-order surface uptake; ``h = 0, advective = 1``: the open-boundary condition -- nothing
+    on outflow, inflow carries ``c_inf`` (the scalar's counterpart of ``PressureBC(..., backflow=)``).  Crank-Nicolson in
+    ``c``; the advective part takes the step's extrapolated velocity ``u_ab`` (explicit).  Independent of ``kappa``.
+
+    Args:
+        h: the film coefficient, a float or a callable ``f(x)``; ``>= 0`` wherever it is evaluated
+        c_inf: the ambient value, a float or a callable ``f(x)``
+        facets: as for :class:`FluxBC`
+        advective: ``beta`` in ``[0, 1]``
+    """
+
+    def __init__(self, h, c_inf, facets, advective: float = 0.0):
+        super().__init__(facets)
+        self.h = _datum("RobinBC", "h", h)
+        if not callable(self.h) and self.h < 0.0:
+            raise ValueError(f"RobinBC: h = {self.h}: the film coefficient must be >= 0")
+        self.c_inf = _datum("RobinBC", "c_inf", c_inf)
+        self.advective = _datum("RobinBC", "advective", advective)
+        if callable(self.advective) or not 0.0 <= self.advective <= 1.0:
+            raise ValueError(f"RobinBC: advective = {advective!r}: a float in [0, 1] is expected")
+
+    def _matrix_key(self, ids):
+        """What of the condition changes the group's matrix: facets, ``h`` (a float, or the identity of the callable) and
+        ``advective``."""
+        return (ids.tobytes(), ("callable", id(self.h)) if callable(self.h) else ("float", self.h), self.advective)
+
+
+def flux_key(scalar, mesh):
+    """The matrix-changing part of a scalar's ``flux_bcs`` on ``mesh`` (its Robin conditions in list order) and the facet
+    ids of every condition; a scalar with only ``FluxBC`` has the key of one with none."""
+    ids = [bc.facet_ids(mesh) for bc in scalar.flux_bcs]
+    return tuple(bc._matrix_key(i) for bc, i in zip(scalar.flux_bcs, ids) if isinstance(bc, RobinBC)), ids
+
+
+def group_key(scalar, rows, mesh):
+    """(key of the scalar's group, facet ids per condition): the diffusivity specification, the Dirichlet rows and -- only
+    where the scalar has Robin conditions -- their matrix-changing part.  ``FluxBC`` changes no matrix and no key."""
+    key, ids = (scalar._spec(), np.asarray(rows, dtype=np.int64).tobytes()), []
+    if scalar.flux_bcs:
+        robin, ids = flux_key(scalar, mesh)
+        if robin:
+            key += (robin,)
+    return key, ids
+
+
+def group_scalars(keyed_scalars, max_columns=None):
+    """``[(key, rows, scalar), ...]`` -> ``[(rows, members), ...]``: scalars of equal key in lock-step, at most
+    ``MAX_COLUMNS`` per group, in the order of first appearance."""
+    max_columns = MAX_COLUMNS if max_columns is None else max_columns
+    keyed = {}
+    for key, rows, s in keyed_scalars:
+        keyed.setdefault(key, (rows, []))[1].append(s)
+    out = []
+    for rows, members in keyed.values():
+        for i in range(0, len(members), max_columns):
+            out.append((rows, members[i:i + max_columns]))
+    return out
+
+
+class BoundaryPass:
+    """The flux / Robin pass of one scalar group: one record per (facet, condition), sorted by facet id, then by the
+    condition's place in its scalar's list (then by column); the Robin conditions, equal across the members but for
+    ``c_inf``, give one record per facet.  Nodal data per record: ``q`` and ``c_inf`` per column, ``h`` and ``beta`` for
+    the group.  The row-centric tables are :class:`oasisx_amd.outlet.RowPairs`."""
+
+    def __init__(self, solver, group, facet_ids):
+        from .outlet import RowPairs, _single_gpu
+        from .wall import FacetSet
+
+        mesh = solver._mesh
+        _single_gpu(mesh, "ScalarTransport with flux_bcs")
+        dev = mesh.device
+        Vi = solver._Vi[0][0]
+        members = group.members
+        self._solver, self._group, self.nc = solver, group, len(members)
+        # blocks: (kind, the RobinBC of every column | the FluxBC, facet ids, place in the scalar's list, column | -1)
+        self.blocks = []
+        robin = [[(p, bc) for p, bc in enumerate(m.flux_bcs) if isinstance(bc, RobinBC)] for m in members]
+        for k, (p, _) in enumerate(robin[0]):
+            self.blocks.append(("robin", [r[k][1] for r in robin], facet_ids[0][p], p, -1))
+        for j, m in enumerate(members):
+            for p, bc in enumerate(m.flux_bcs):
+                if isinstance(bc, FluxBC):
+                    self.blocks.append(("flux", bc, facet_ids[j][p], p, j))
+        ids = np.concatenate([b[2] for b in self.blocks] + [np.zeros(0, np.int64)])
+        place = np.concatenate([np.full(b[2].shape[0], b[3], np.int64) for b in self.blocks] + [np.zeros(0, np.int64)])
+        col = np.concatenate([np.full(b[2].shape[0], b[4], np.int64) for b in self.blocks] + [np.zeros(0, np.int64)])
+        blk = np.concatenate([np.full(b[2].shape[0], k, np.int64) for k, b in enumerate(self.blocks)] + [np.zeros(0, np.int64)])
+        order = np.lexsort((col, place, ids))  # by facet id, then by the order of the list, then by column
+        self.record_facets, blk = ids[order], blk[order]
+        self._records_of = [np.nonzero(blk == k)[0] for k in range(len(self.blocks))]  # (ascending facet id inside a block)
+        uniq, inv = np.unique(self.record_facets, return_inverse=True)
+        fs = FacetSet(solver, uniq, np.zeros(uniq.shape[0], dtype=np.int64), 1, "ScalarTransport flux_bcs",
+                      "flux and Robin conditions")
+        ne = int(self.record_facets.shape[0])
+        self.n_records = ne
+        kpos, lf = fs.kpos[inv], fs.local_facets[inv]
+        self.robin = bool(robin[0])
+        self.adv = any(bc.advective > 0.0 for _, bc in robin[0])
+        rp = RowPairs(Vi, kpos, lf, dev, "ScalarTransport flux_bcs", slots=self.robin)
+        self.pairs, self.nfd = rp, rp.nfd
+        rec = np.stack([kpos, lf], axis=1).astype(np.int32) if ne else np.zeros((1, 2), dtype=np.int32)
+        self.rec = torch.from_numpy(np.ascontiguousarray(rec)).to(dev)
+        # the coordinates of the records' facet dofs, (3, ne * nfd)
+        x = Vi.x.cpu().numpy()[rp.facet_dofs.reshape(-1)]
+        self._X = np.zeros((3, x.shape[0]))
+        self._X[: x.shape[1]] = x.T
+        n1 = max(ne, 1)
+        self._q, self._c = np.zeros((n1, self.nfd, self.nc)), np.zeros((n1, self.nfd, self.nc))
+        self._h, self._beta = np.zeros((n1, self.nfd)), np.zeros(n1)
+        self.q, self.c_inf = torch.from_numpy(self._q).to(dev), torch.from_numpy(self._c).to(dev)
+        self.h, self.beta = torch.from_numpy(self._h).to(dev), torch.from_numpy(self._beta).to(dev)
+        self._dirty = False
+        for k, b in enumerate(self.blocks):
+            for bc in (b[1] if b[0] == "robin" else [b[1]]):
+                bc._bound.append((self, k))
+            self.evaluate(k, first=True)
+
+    def evaluate(self, k: int, first: bool = False) -> None:
+        """The nodal data of block k on the host (``first``: the constants too); they go to the device with the next
+        pass."""
+        kind, bcs, _, _, col = self.blocks[k]
+        recs = self._records_of[k]
+        nfd = self.nfd
+        if not recs.size:  # an empty facet set
+            return
+        X = self._X.reshape(3, -1, nfd)[:, recs].reshape(3, -1)
+        if kind == "flux":
+            if first or callable(bcs.q):
+                self._q[recs, :, col] = _nodal("FluxBC", "q", bcs.q, X).reshape(-1, nfd)
+                self._dirty = True
+            return
+        for j, bc in enumerate(bcs):
+            if first or callable(bc.c_inf):
+                self._c[recs, :, j] = _nodal("RobinBC", "c_inf", bc.c_inf, X).reshape(-1, nfd)
+                self._dirty = True
+        if first or callable(bcs[0].h):
+            self._h[recs] = _nodal("RobinBC", "h", bcs[0].h, X, nonneg=True).reshape(-1, nfd)
+            self._dirty = True
+        if first:
+            self._beta[recs] = bcs[0].advective
+
+    def add(self) -> None:
+        """``A_c += H/2``, ``b_c += load - (H/2) c_1`` with the ``u_ab`` block of this step (``ox_scalar_boundary``)."""
+        S, g = self._solver, self._group
+        if self._dirty:
+            for dst, src in ((self.q, self._q), (self.c_inf, self._c), (self.h, self._h), (self.beta, self._beta)):
+                dst.copy_(torch.from_numpy(src))
+            self._dirty = False
+        if not self.n_records:
+            return
+        Vi = S._Vi[0][0]
+        rp = self.pairs
+        a = _lib.ox_scalar_bc_args()
+        a.degree, a.nc, a.robin, a.adv = Vi.degree, self.nc, int(self.robin), int(self.adv)
+        a.n_rows = rp.n_rows
+        a.rows, a.row_ptr = rp.rows.data_ptr(), rp.row_ptr.data_ptr()
+        a.pair_facet, a.pair_loc = rp.pair_facet.data_ptr(), rp.pair_loc.data_ptr()
+        a.n_facets, a.facet_rec, a.q = self.n_records, self.rec.data_ptr(), self.q.data_ptr()
+        if self.robin:
+            a.pair_off, a.h, a.c_inf = rp.pair_off.data_ptr(), self.h.data_ptr(), self.c_inf.data_ptr()
+            a.c1 = g.C1.rdev().data_ptr()
+            a.a_vals, a.a_size = g.Ac.vals.data_ptr(), int(g.Ac.vals.shape[0])
+        if self.adv:
+            a.beta, a.uab = self.beta.data_ptr(), S._UAB.rdev().data_ptr()
+        a.b, a.n_dofs = g.B.dev().data_ptr(), int(S._n_u)
+        _lib.check(S._lib.ox_scalar_boundary(C.byref(S._cells), _lib.ptr(Vi.cell_dofs), C.byref(a), _lib.current_stream()),
+                   "ox_scalar_boundary")
+        if self.robin:
+            g.Ac.version += 1
 
 
 def check_turbulent_schmidt(model, scalars) -> None:
@@ -184,6 +442,7 @@ class ScalarGroup:
         self.ksp.setOptions(self.Ac)
         self.reasons = None
         self.ax0_valid = False  # AC1 holds A_c c_1 of the last assembly and has not been used yet
+        self.boundary = None  # the flux / Robin pass (BoundaryPass), where a member has flux_bcs
 
     def wants_ax0(self) -> bool:
         o = self.ksp._options
@@ -218,15 +477,18 @@ def build_groups(solver, scalars, options):
         for s in scalars:
             for bc in s.bcs:
                 bc.create_bc(Vi)
-    keyed = {}
+    keyed, facet_ids = [], {}
     for s in scalars:
         rows = np.unique(np.concatenate([np.asarray(bc._dofs, dtype=np.int64) for bc in s.bcs] + [np.zeros(0, np.int64)]))
         rows = rows[rows < Vi.n_owned]
-        keyed.setdefault((s._spec(), rows.tobytes()), (rows, []))[1].append(s)
+        key, facet_ids[s.name] = group_key(s, rows, solver._mesh)
+        keyed.append((key, rows, s))
     groups = []
-    for rows, members in keyed.values():
-        for i in range(0, len(members), MAX_COLUMNS):
-            groups.append(ScalarGroup(solver, members[i:i + MAX_COLUMNS], rows, options))
+    for rows, members in group_scalars(keyed):
+        g = ScalarGroup(solver, members, rows, options)
+        if any(m.flux_bcs for m in members):
+            g.boundary = BoundaryPass(solver, g, [facet_ids[m.name] for m in members])
+        groups.append(g)
     return groups
 
 
@@ -286,6 +548,8 @@ def assemble(solver, group: ScalarGroup, dt: float, nu: float):
     lib, st = solver._lib, _lib.current_stream()
     kappa = group.members[0].kappa(nu)
     au = group.AC1.ptr() if group.wants_ax0() else None
+    if group.boundary is not None and group.boundary.robin:
+        au = None  # A_c changes after the row kernel: its A_c c_1 by-product is not asked for
     t = 0.0 if solver._viscosity_model is None else turbulent_factor(solver, group.members[0])
     if t == 0.0:  # no model, or Sc_t = 1: the scalar's operator differs from A by a multiple of K alone
         _lib.check(lib.ox_scalar_rows(solver._A.ref(), solver._M.ref(), solver._K.ref(), group.Ac.ref(),
@@ -300,6 +564,12 @@ def assemble(solver, group: ScalarGroup, dt: float, nu: float):
                                                int(solver._row_blocks and Vi.pattern.n_row_blocks > 0), st),
                    "ox_scalar_rows_cellvisc")
     group.Ac.version += 1
+    if group.boundary is not None:  # before the identity rows: Dirichlet rows win on rim dofs
+        solver._scalar_rows_open = group
+        try:
+            solver.scalar_boundary_assemble()
+        finally:
+            solver._scalar_rows_open = None
     if group.rows_dev.shape[0] > 0:  # identity rows; (A_c c_1)[row] = c_1[row] there, in the same launch
         group.Ac.zero_rows(group.rows_dev, 1.0, au, group.C1.rptr() if au is not None else None, group.nc)
     for j, s in enumerate(group.members):
