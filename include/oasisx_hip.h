@@ -986,6 +986,29 @@ int ox_scalar_rows_cellvisc(const ox_cells *cells, const ox_space_info *space, c
                             const ox_sell *K, const ox_sell *Ac, const double *nut, double s, double t, double dt,
                             int ncomp, const double *c1, const double *b0, double *b, double *a_c1, int row_blocks,
                             void *stream);
+/* SUPG stabilisation of a scalar group (streamline-upwind Petrov-Galerkin).  Per cell c, with
+ * G[a] = grad lambda_a and k = degree:
+ *   w_c   = u_ab at the centroid                                     (the frozen advecting velocity of the stabilising terms)
+ *   tau_c = scale ([time_term] (2/dt)^2 + (k q_c)^2 + (2 k^2 kappa_c g_c)^2)^(-1/2),   q_c = sum_a |w_c . G[a]|,
+ *           g_c = sum_a |G[a]|^2,   kappa_c = kappa + inv_sct nut[c]  (nut == NULL: kappa)
+ * ox_supg_cells: one lane per cell; rec: device [(gdim + 1) n_cells], a structure of arrays in kernel cell order,
+ * rec[d n_cells + c] = w_c[d], rec[gdim n_cells + c] = tau_c.  w_c = 0 gives a finite tau_c; a w_c that is not finite
+ * gives tau_c = NaN.  cell_dofs, uab: those of ox_cell_viscosity. */
+int ox_supg_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab, const double *nut,
+                  double kappa, double inv_sct, double dt, double scale, int time_term, double *rec, void *stream);
+/* ox_scalar_rows_supg: the sibling of ox_scalar_rows_cellvisc (same launches, same LDS accumulators, row_blocks as there):
+ *   N_ij = sum_c tau_c int_c (w_c . grad phi_i) phi_j,   S_ij = sum_c tau_c int_c (w_c . grad phi_i)(w_c . grad phi_j)
+ *   A_c  = A + s K + t K_t + N/dt + S/2      per entry v = acc + fma(s, k, a), acc = the rows of t K_t + N/dt + S/2 from LDS
+ *   b    = (2/dt) M c1 - A_c c1 + b0 + N ((2/dt) c1 + fh)          (the last term per lane in registers, from the cells' dofs)
+ *   a_c1 = A_c c1                             (optional; bit-identical to ox_spmv(Ac, c1))
+ * rec: what ox_supg_cells wrote.  nut may be NULL (no model, or t = 0): then t is not read.  fh: the nodal interpolant of
+ * the source, an interleaved (n, ncomp) block as c1.  The second-derivative term tau (w . grad phi_i) kappa lap c is
+ * dropped (zero for P1).  w = 0 everywhere and nut == NULL give the bits of ox_scalar_rows.  No atomics to global memory,
+ * fixed order of sums, no scratch. */
+int ox_scalar_rows_supg(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
+                        const ox_sell *K, const ox_sell *Ac, const double *nut, const double *rec, double s, double t,
+                        double dt, int ncomp, const double *c1, const double *b0, const double *fh, double *b, double *a_c1,
+                        int row_blocks, void *stream);
 
 /* ---- Scalars that drive the flow, scalar fluxes through walls (ox_scalar.hip) ------------------
  * Boussinesq force of 1..OX_MAXC coupled scalars onto the interleaved (n, gdim) block b (b_first of the velocity step), in

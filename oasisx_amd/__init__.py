@@ -15,7 +15,7 @@ from .geometry import Probes, WallDistance  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
 from .particles import DEPOSITED, InertialParticles
-from .scalar import FluxBC, RobinBC, ScalarFlux, ScalarTransport
+from .scalar import SUPG, FluxBC, RobinBC, ScalarFlux, ScalarTransport
 from .tracers import Tracers
 from .viscosity import (CarreauYasuda, CellViscosity, Cross, DynamicSmagorinsky, PatchFilter, PowerLaw, Smagorinsky, VanDriest,
                         Wale)
@@ -32,6 +32,7 @@ __all__ = [
     "LocatorMethod",
     "PressureBC",
     "ScalarTransport",
+    "SUPG",
     "ScalarFlux",
     "FluxBC",
     "RobinBC",

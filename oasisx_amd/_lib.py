@@ -400,6 +400,8 @@ class ox_scalar_bc_args(C.Structure):
 
 PROF_TAG_BUOYANCY_ROWS = 190  # OX_TAG_BUOYANCY_ROWS of csrc/ox_kernels.h (ox_profile_get: key = 2 x terms + dictionary)
 PROF_TAG_SCALAR_ROWS_CELLVISC = 192  # OX_TAG_SCALAR_ROWS_CELLVISC (ox_profile_get: key = columns)
+PROF_TAG_SCALAR_ROWS_SUPG = 193  # OX_TAG_SCALAR_ROWS_SUPG (ox_profile_get: key = columns)
+PROF_TAG_SUPG_CELLS = 194  # OX_TAG_SUPG_CELLS (ox_profile_get: key = cells)
 PROF_TAG_SCALAR_BOUNDARY = 183  # OX_TAG_SCALAR_BOUNDARY, beside OX_TAG_OUTLET_BACKFLOW = 182 (ox_profile_get: key = rows)
 
 _P = C.c_void_p
@@ -512,6 +514,9 @@ SIGNATURES = {
                             _P, _P, _P, _P, _P]),
     "ox_scalar_rows_cellvisc": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), C.POINTER(ox_sell),
                                      C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _D, _D, _D, _I, _P, _P, _P, _P, _I, _P]),
+    "ox_supg_cells": (_I, [_I, C.POINTER(ox_cells), _P, _P, _P, _D, _D, _D, _D, _I, _P, _P]),
+    "ox_scalar_rows_supg": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), C.POINTER(ox_sell),
+                                 C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _P, _D, _D, _D, _I, _P, _P, _P, _P, _P, _I, _P]),
     "ox_buoyancy_rows": (_I, [C.POINTER(ox_sell), _I, _I, C.POINTER(ox_buoy_term), _P, _P]),
     "ox_scalar_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
     "ox_scalar_flux_cells": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _P, _D, _D, _P, _P, _P, _P, _P]),

@@ -216,6 +216,42 @@ __device__ __forceinline__ const StiffTab<GDIM, DEG> &st_tab() {
   else return ST32;
 }
 
+// The Petrov-Galerkin time term of SUPG: with the cell's frozen velocity w,
+//   int (w . grad phi_i) phi_j = |J| sum_a (w . G[a]) NT[i][a][j],   NT[i][a][j] = sum_q w_q dphi_i(q, a) phi_j(q)
+// on the rule of the other tables (exact: degree (DEG - 1) + DEG).  Read from an LDS copy with the lane's row dof i.
+template <int GDIM, int DEG>
+struct SupgTab {
+  using E = Elem<GDIM, DEG>;
+  double t[E::ND][GDIM + 1][E::ND];
+};
+template <int GDIM, int DEG>
+constexpr SupgTab<GDIM, DEG> make_supg() {
+  using E = Elem<GDIM, DEG>;
+  SupgTab<GDIM, DEG> T{};
+  for (int i = 0; i < E::ND; ++i)
+    for (int a = 0; a <= GDIM; ++a)
+      for (int j = 0; j < E::ND; ++j) {
+        double s = 0.0;
+        for (int q = 0; q < E::NQ; ++q) s += E::w(q) * E::dphi(q, i, a) * E::phi(q, j);
+        T.t[i][a][j] = s;
+      }
+  return T;
+}
+__device__ const SupgTab<2, 1> NT21 = make_supg<2, 1>();
+__device__ const SupgTab<2, 2> NT22 = make_supg<2, 2>();
+__device__ const SupgTab<3, 1> NT31 = make_supg<3, 1>();
+__device__ const SupgTab<3, 2> NT32 = make_supg<3, 2>();
+__device__ const SupgTab<2, 3> NT23 = make_supg<2, 3>();
+template <int GDIM, int DEG>
+__device__ __forceinline__ const SupgTab<GDIM, DEG> &nt_tab() {
+  static_assert(!(GDIM == 3 && DEG == 3), "P3 tetrahedra: the time term by quadrature, at the points of the stiffness rows");
+  if constexpr (DEG == 3) return NT23;
+  else if constexpr (GDIM == 2 && DEG == 1) return NT21;
+  else if constexpr (GDIM == 2 && DEG == 2) return NT22;
+  else if constexpr (GDIM == 3 && DEG == 1) return NT31;
+  else return NT32;
+}
+
 // P3 on tetrahedra: the tensor T[i][k][(j, b)] the kernels above read from LDS would be 20 x 20 x 60 doubles = 192 KB --
 // it does not fit.  The convection rows of that element are formed by QUADRATURE at run time instead: the values and
 // derivatives of all 20 basis functions at the 70 points sit in device memory and are read with wave-uniform indices
@@ -829,17 +865,40 @@ struct ScalarVisArgs {
   const double *Md, *Kd;
   int nMd, nKd;
 };
+// SUPG (streamline-upwind Petrov-Galerkin stabilisation): per cell a frozen velocity w_c and a
+// parameter tau_c (ox_supg_cells: rec[d][e] = w_d, rec[GDIM][e] = tau, kernel cell order), and
+//   A_c = A + s K + t K_t + N/dt + S/2,   b_c = (2/dt) M c_1 - A_c c_1 + b0 + N ((2/dt) c_1 + f_h)
+//   N_ij = sum_c tau_c int_c (w_c . grad phi_i) phi_j,   S_ij = sum_c tau_c int_c (w_c . grad phi_i)(w_c . grad phi_j).
+// The pair loop makes the ONE StiffTab contraction with gg[a][b] = t nut G[a].G[b] + (tau/2)(w.G[a])(w.G[b]), adds
+// (tau/dt) sum_a (w.G[a]) NT[i][a][j] (SupgTab, from LDS with the lane's row dof) and sums the lane's entry of
+// N ((2/dt) c_1 + f_h) in registers from the cell's dofs; the epilogue adds the accumulator as it is, v = acc + fma(s, k, a).
+// The fields exist in the SUPG instantiations only (as FirstArgsT<NUT>): the others keep their argument block and code.
+template <bool SUPG>
+struct ScalarVisArgsT : ScalarVisArgs {};
+template <>
+struct ScalarVisArgsT<true> : ScalarVisArgs {
+  const double *rec, *fh;
+  const int32_t *cell_dofs;
+  int64_t n_cells;
+};
 
-template <int GDIM, int DEG, int PW, int NC, bool DICT>
+template <int GDIM, int DEG, int PW, int NC, bool DICT, bool SUPG = false>
 __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, const ox_adj &adj,
                                                       const uint8_t *__restrict__ adj_pos, const ox_sell &A,
-                                                      const ScalarVisArgs &F, const int slice, double *acc, const int lane,
-                                                      const double *tst, const double *dM, const double *dK) {
+                                                      const ScalarVisArgsT<SUPG> &F, const int slice, double *acc,
+                                                      const int lane, const double *tst, const double *dM, const double *dK,
+                                                      const double *tnt = nullptr) {
   using E = Elem<GDIM, DEG>;
   constexpr int ND = E::ND, GS = E::GS;
   constexpr bool QUAD = OX_CONV_BY_QUADRATURE<GDIM, DEG>;
   constexpr int NCB = QUAD ? 1 : COMBOS<GDIM, DEG>.n;
   constexpr int SS = NCB * (GDIM + 1) + 2;
+  constexpr int NS = (GDIM + 1) * ND + 2;  // doubles per row dof of the LDS copy of SupgTab, padded as SS
+  [[maybe_unused]] double rs[NC];          // SUPG: the lane's entry of N ((2/dt) c_1 + f_h), per column
+  if constexpr (SUPG) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) rs[c] = 0.0;
+  }
   const int64_t base = A.slice_ptr[slice];
   const int width = (int)((A.slice_ptr[slice + 1] - base) >> 6);
   for (int k = 0; k < width; ++k) acc[k * 64 + lane] = 0.0;
@@ -862,13 +921,65 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
     } else {
       *reinterpret_cast<uint32_t *>(pos) = *reinterpret_cast<const uint32_t *>(adj_pos + pidx * 4);
     }
-    const double nutv = F.nut[e];
+    double nutv;
+    if constexpr (SUPG) nutv = F.nut ? F.t * F.nut[e] : 0.0;  // (t nut_c: the accumulator is added as it is)
+    else nutv = F.nut[e];
     double G[GDIM + 1][GDIM], adet;
     ox_load_geom<GDIM>(cells.geom + (size_t)e * GS, G, adet);
     double c[ND];
 #pragma unroll
     for (int j = 0; j < ND; ++j) c[j] = 0.0;
-    if constexpr (QUAD) {
+    // SUPG: wa[a] = w_c . G[a], th = tau_c / 2, nr[j] = int (w_c . grad phi_i) phi_j / |J|
+    [[maybe_unused]] double wa[GDIM + 1], th = 0.0, tau = 0.0, nr[ND];
+    if constexpr (SUPG) {
+      double w[GDIM];
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d) w[d] = F.rec[(size_t)d * F.n_cells + e];
+      tau = F.rec[(size_t)GDIM * F.n_cells + e];
+      th = 0.5 * tau;
+#pragma unroll
+      for (int a = 0; a <= GDIM; ++a) {
+        double v = 0.0;
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) v = fma(w[d], G[a][d], v);
+        wa[a] = v;
+      }
+#pragma unroll
+      for (int j = 0; j < ND; ++j) nr[j] = 0.0;
+    }
+    if constexpr (QUAD && SUPG) {
+      // the NUT lines below with the rank-one part beside nut G[b] . grad(phi_i), and the time term at the same points:
+      // nr[j] = sum_q w_q (w . grad phi_i)(x_q) phi_j(x_q)
+      const auto &R = rt<GDIM, DEG>();
+      for (int q = 0; q < E::NQ; ++q) {
+        double gi[GDIM];
+#pragma unroll
+        for (int d = 0; d < GDIM; ++d) {
+          gi[d] = 0.0;
+#pragma unroll
+          for (int b = 1; b <= GDIM; ++b) gi[d] = fma(R.dphi[i][q][b], G[b][d], gi[d]);
+        }
+        double wg = 0.0;  // w . grad phi_i = sum_b (w . G[b]) dphi_i / dlambda_b
+#pragma unroll
+        for (int b = 1; b <= GDIM; ++b) wg = fma(R.dphi[i][q][b], wa[b], wg);
+        const double wq = QW33.w[q];
+        const double wn = wq * nutv, ws = wq * th * wg, wt = wq * wg;
+        double sb[GDIM];
+#pragma unroll
+        for (int b = 1; b <= GDIM; ++b) {
+          double h = 0.0;
+#pragma unroll
+          for (int d = 0; d < GDIM; ++d) h = fma(G[b][d], gi[d], h);
+          sb[b - 1] = fma(ws, wa[b], wn * h);
+        }
+#pragma unroll
+        for (int j = 0; j < ND; ++j) {
+#pragma unroll
+          for (int b = 0; b < GDIM; ++b) c[j] = fma(QT33.dphi[q][j][b], sb[b], c[j]);
+          nr[j] = fma(QT33.phi[q][j], wt, nr[j]);
+        }
+      }
+    } else if constexpr (QUAD) {
       // nut K_e[i][j] / |J| = nut sum_q w_q grad(phi_i) . grad(phi_j) (the lambda_0 column of the tabulation is zero)
       const auto &R = rt<GDIM, DEG>();
       for (int q = 0; q < E::NQ; ++q) {
@@ -906,7 +1017,8 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
           double v = 0.0;
 #pragma unroll
           for (int d = 0; d < GDIM; ++d) v = fma(G[a][d], G[b][d], v);
-          gg[a][b] = gg[b][a] = nutv * v;
+          if constexpr (SUPG) gg[a][b] = gg[b][a] = fma(th * wa[a], wa[b], nutv * v);
+          else gg[a][b] = gg[b][a] = nutv * v;
         }
       double cm[NCB];
 #pragma unroll
@@ -917,6 +1029,35 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
         for (int m = 0; m < NCB; ++m) cm[m] = fma(si[a * NCB + m], gg[a][CB.b[m]], cm[m]);
 #pragma unroll
       for (int m = 0; m < NCB; ++m) c[CB.j[m]] += cm[m];
+      if constexpr (SUPG) {
+        const double *__restrict__ ni = tnt + i * NS;
+#pragma unroll
+        for (int a = 0; a <= GDIM; ++a)
+#pragma unroll
+          for (int j = 0; j < ND; ++j) nr[j] = fma(ni[a * ND + j], wa[a], nr[j]);
+      }
+    }
+    if constexpr (SUPG) {
+      // the time term into the row, (tau/dt) nr[j], and the lane's share of N ((2/dt) c_1 + f_h) from the cell's dofs
+      const double tdt = tau * (0.5 * F.two_idt);
+      int32_t dd[ND];
+      ox_load_dofs<ND>(F.cell_dofs, e, dd);
+      double r[NC];
+#pragma unroll
+      for (int cc = 0; cc < NC; ++cc) r[cc] = 0.0;
+#pragma unroll
+      for (int j = 0; j < ND; ++j) {
+        c[j] = fma(tdt, nr[j], c[j]);
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc) {
+          const size_t k = (size_t)dd[j] * NC + cc;
+          r[cc] = fma(nr[j], fma(F.two_idt, F.c1[k], F.fh[k]), r[cc]);
+        }
+      }
+      if (ok) {
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc) rs[cc] = fma(adet * tau, r[cc], rs[cc]);
+      }
     }
     if (ok) {
 #pragma unroll
@@ -936,7 +1077,8 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
   v2d *__restrict__ ov = reinterpret_cast<v2d *>(F.Acv + base) + lane;
   const unsigned short *__restrict__ mc = DICT ? reinterpret_cast<const unsigned short *>(F.Mc + base) + lane : nullptr;
   const unsigned short *__restrict__ kc = DICT ? reinterpret_cast<const unsigned short *>(F.Kc + base) + lane : nullptr;
-  const double s = F.s, tt = F.t;
+  const double s = F.s;
+  [[maybe_unused]] const double tt = F.t;
   double sa[NC], sm[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) sa[c] = sm[c] = 0.0;
@@ -971,8 +1113,13 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
       const int k = k0 + q;
       if (k < npair) {
         v2d v;
-        v.x = fma(tt, acc[(2 * k) * 64 + lane], fma(s, kk[q].x, a[q].x));
-        v.y = fma(tt, acc[(2 * k + 1) * 64 + lane], fma(s, kk[q].y, a[q].y));
+        if constexpr (SUPG) {
+          v.x = acc[(2 * k) * 64 + lane] + fma(s, kk[q].x, a[q].x);
+          v.y = acc[(2 * k + 1) * 64 + lane] + fma(s, kk[q].y, a[q].y);
+        } else {
+          v.x = fma(tt, acc[(2 * k) * 64 + lane], fma(s, kk[q].x, a[q].x));
+          v.y = fma(tt, acc[(2 * k + 1) * 64 + lane], fma(s, kk[q].y, a[q].y));
+        }
         __builtin_nontemporal_store(v, ov + (size_t)k * 64);
 #pragma unroll
         for (int c = 0; c < NC; ++c) sa[c] = fma(v.x, x0[q][c], sa[c]);  // entry order and operations of k_spmv
@@ -985,7 +1132,11 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
   }
   if (row < A.n_rows) {
 #pragma unroll
-    for (int c = 0; c < NC; ++c) F.b[row * NC + c] = fma(F.two_idt, sm[c], -sa[c]) + F.b0[row * NC + c];
+    for (int c = 0; c < NC; ++c) {
+      const double bc = fma(F.two_idt, sm[c], -sa[c]) + F.b0[row * NC + c];
+      if constexpr (SUPG) F.b[row * NC + c] = bc + rs[c];
+      else F.b[row * NC + c] = bc;
+    }
     if (F.a_c1) {
 #pragma unroll
       for (int c = 0; c < NC; ++c) F.a_c1[row * NC + c] = sa[c];
@@ -993,10 +1144,10 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
   }
 }
 
-template <int GDIM, int DEG, int PW, int NC, bool DICT, bool BLK>
+template <int GDIM, int DEG, int PW, int NC, bool DICT, bool BLK, bool SUPG = false>
 __global__ __launch_bounds__(BLK ? 512 : 256) void k_scalar_rows_cellvisc(ox_cells cells, ox_adj adj,
                                                                           const uint8_t *__restrict__ adj_pos, ox_sell A,
-                                                                          ScalarVisArgs F,
+                                                                          ScalarVisArgsT<SUPG> F,
                                                                           const int32_t *__restrict__ slice_list, int n_list,
                                                                           int bin_width) {
   using E = Elem<GDIM, DEG>;
@@ -1007,6 +1158,8 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_scalar_rows_cellvisc(ox_cel
   extern __shared__ double acc_all[];       // [waves][bin_width][64]  (BLK: the row block's slices back to back)
   __shared__ double dM[DICT ? 256 : 1], dK[DICT ? 256 : 1];
   __shared__ __attribute__((aligned(16))) double tst[QUAD ? 2 : ND * SS];
+  constexpr int NS = (GDIM + 1) * ND + 2;  // SUPG: doubles per row dof of SupgTab, padded as SS
+  __shared__ __attribute__((aligned(16))) double tnt[SUPG && !QUAD ? ND * NS : 2];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int nthr = blockDim.x, nwave = blockDim.x >> 6;
   if constexpr (DICT) {
@@ -1020,6 +1173,14 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_scalar_rows_cellvisc(ox_cel
       const int i = idx / PER_I;
       tst[i * SS + (idx - i * PER_I)] = src[idx];
     }
+    if constexpr (SUPG) {
+      const double *nsrc = &nt_tab<GDIM, DEG>().t[0][0][0];
+      constexpr int PER_N = (GDIM + 1) * ND;
+      for (int idx = threadIdx.x; idx < ND * PER_N; idx += nthr) {
+        const int i = idx / PER_N;
+        tnt[i * NS + (idx - i * PER_N)] = nsrc[idx];
+      }
+    }
   }
   if constexpr (DICT || !QUAD) __syncthreads();
   if constexpr (BLK) {
@@ -1027,18 +1188,19 @@ __global__ __launch_bounds__(BLK ? 512 : 256) void k_scalar_rows_cellvisc(ox_cel
     const int s0 = slice_list[b];
     const int slice = s0 + wave;
     if (slice >= slice_list[b + 1]) return;
-    scalar_cellvisc_slice<GDIM, DEG, PW, NC, DICT>(cells, adj, adj_pos, A, F, slice,
-                                                   acc_all + (A.slice_ptr[slice] - A.slice_ptr[s0]), lane, tst, dM, dK);
+    scalar_cellvisc_slice<GDIM, DEG, PW, NC, DICT, SUPG>(cells, adj, adj_pos, A, F, slice,
+                                                         acc_all + (A.slice_ptr[slice] - A.slice_ptr[s0]), lane, tst, dM, dK,
+                                                         tnt);
   } else {
     const int li = ox_xcd_remap(blockIdx.x, gridDim.x) * nwave + wave;
     if (li >= n_list) return;
-    scalar_cellvisc_slice<GDIM, DEG, PW, NC, DICT>(cells, adj, adj_pos, A, F, slice_list[li],
-                                                   acc_all + (size_t)wave * bin_width * 64, lane, tst, dM, dK);
+    scalar_cellvisc_slice<GDIM, DEG, PW, NC, DICT, SUPG>(cells, adj, adj_pos, A, F, slice_list[li],
+                                                         acc_all + (size_t)wave * bin_width * 64, lane, tst, dM, dK, tnt);
   }
 }
 
-template <int GDIM, int DEG, int PW, int NC, bool DICT>
-static int launch_scalar_cellvisc_t(const RowLaunch &L, const ox_sell *A, const ScalarVisArgs &F) {
+template <int GDIM, int DEG, int PW, int NC, bool DICT, bool SUPG>
+static int launch_scalar_cellvisc_t(const char *who, const RowLaunch &L, const ox_sell *A, const ScalarVisArgsT<SUPG> &F) {
   const ox_space_info &V = *L.V;
   const ox_pattern_info &P = V.pattern;
   auto go = [&](auto kern, unsigned grid, unsigned block, size_t lds, const int32_t *list, int n_list, int width) -> int {
@@ -1053,12 +1215,14 @@ static int launch_scalar_cellvisc_t(const RowLaunch &L, const ox_sell *A, const 
       const int64_t cnt = P.bin_ptr_host[b + 1] - P.bin_ptr_host[b];
       if (cnt <= 0) continue;
       const int width = P.bin_width_host[b];
-      constexpr size_t CAP = OX_ROW_BLOCK_LDS;  // (as the NUT launches of ox_assemble_first: tables of up to 11 KB beside it)
+      // as the NUT launches of ox_assemble_first.  Static tables beside it: up to 9.4 KB, with SUPG up to 12.7 KB (P2
+      // tetrahedra with dictionaries: 4 KB + the stiffness tensor 5.3 KB + the time-term table 3.4 KB): 134 + 12.7 < 160 KB
+      constexpr size_t CAP = OX_ROW_BLOCK_LDS;
       int nw = 4;
       while (nw > 1 && (size_t)nw * width * 64 * sizeof(double) > CAP) nw >>= 1;
       const size_t lds = (size_t)nw * width * 64 * sizeof(double);
-      if (lds > CAP) OX_FAIL("ox_scalar_rows_cellvisc: row width %d needs %zu B of LDS", width, lds);
-      const int rc = go(k_scalar_rows_cellvisc<GDIM, DEG, PW, NC, DICT, false>, (unsigned)((cnt + nw - 1) / nw), 64u * nw, lds,
+      if (lds > CAP) OX_FAIL("%s: row width %d needs %zu B of LDS", who, width, lds);
+      const int rc = go(k_scalar_rows_cellvisc<GDIM, DEG, PW, NC, DICT, false, SUPG>, (unsigned)((cnt + nw - 1) / nw), 64u * nw, lds,
                         P.bin_slices + P.bin_ptr_host[b], (int)cnt, width);
       if (rc) return rc;
     }
@@ -1066,18 +1230,19 @@ static int launch_scalar_cellvisc_t(const RowLaunch &L, const ox_sell *A, const 
   }
   const size_t lds = (size_t)P.row_blk_entries * sizeof(double);
   if (lds > OX_ROW_BLOCK_LDS)
-    OX_FAIL("ox_scalar_rows_cellvisc: a row block needs %zu B of LDS (limit %d)", lds, OX_ROW_BLOCK_LDS);
-  return go(k_scalar_rows_cellvisc<GDIM, DEG, PW, NC, DICT, true>, (unsigned)P.n_row_blocks, 512u, lds, P.row_blk_ptr,
+    OX_FAIL("%s: a row block needs %zu B of LDS (limit %d)", who, lds, OX_ROW_BLOCK_LDS);
+  return go(k_scalar_rows_cellvisc<GDIM, DEG, PW, NC, DICT, true, SUPG>, (unsigned)P.n_row_blocks, 512u, lds, P.row_blk_ptr,
             (int)P.n_row_blocks, 0);
 }
 
-template <int GDIM, int DEG, int PW>
-static int launch_scalar_cellvisc(const RowLaunch &L, const ox_sell *A, const ScalarVisArgs &F, int ncomp) {
+template <int GDIM, int DEG, int PW, bool SUPG>
+static int launch_scalar_cellvisc(const char *who, const RowLaunch &L, const ox_sell *A, const ScalarVisArgsT<SUPG> &F,
+                                  int ncomp) {
   const bool dict = F.Mc && F.Kc && F.Md && F.Kd && F.nMd >= 1 && F.nMd <= 256 && F.nKd >= 1 && F.nKd <= 256;
 #define OX_SCV_NC(N)                                                                        \
   case N:                                                                                   \
-    return dict ? launch_scalar_cellvisc_t<GDIM, DEG, PW, N, true>(L, A, F)                 \
-                : launch_scalar_cellvisc_t<GDIM, DEG, PW, N, false>(L, A, F);
+    return dict ? launch_scalar_cellvisc_t<GDIM, DEG, PW, N, true, SUPG>(who, L, A, F)      \
+                : launch_scalar_cellvisc_t<GDIM, DEG, PW, N, false, SUPG>(who, L, A, F);
   switch (ncomp) {
     OX_SCV_NC(1)
     OX_SCV_NC(2)
@@ -1087,38 +1252,62 @@ static int launch_scalar_cellvisc(const RowLaunch &L, const ox_sell *A, const Sc
 #undef OX_SCV_NC
 }
 
-extern "C" int ox_scalar_rows_cellvisc(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
-                                       const ox_sell *K, const ox_sell *Ac, const double *nut, double s, double t, double dt,
-                                       int ncomp, const double *c1, const double *b0, double *b, double *a_c1, int row_blocks,
-                                       void *stream) {
-  if (!cells || !cells->geom || !space || !A || !M || !K || !Ac || !A->vals || !M->vals || !K->vals || !Ac->vals || !nut ||
-      !c1 || !b0 || !b)
-    OX_FAIL("ox_scalar_rows_cellvisc: null argument");
-  if (row_launch_check("ox_scalar_rows_cellvisc", space, row_blocks)) return -1;
+// the argument checks and the dispatch of the two entries (`who` names the entry in the errors); `extra`: a further
+// pointer argument is missing
+template <bool SUPG>
+static int scalar_rows_cells(const char *who, int tag, const ox_cells *cells, const ox_space_info *space, const ox_sell *A,
+                             const ox_sell *M, const ox_sell *K, const ox_sell *Ac, bool extra, double dt, int ncomp,
+                             int row_blocks, void *stream, ScalarVisArgsT<SUPG> &F) {
+  if (!cells || !cells->geom || !space || !A || !M || !K || !Ac || !A->vals || !M->vals || !K->vals || !Ac->vals || extra ||
+      !F.c1 || !F.b0 || !F.b)
+    OX_FAIL("%s: null argument", who);
+  if (row_launch_check(who, space, row_blocks)) return -1;
   if (M->slice_ptr != A->slice_ptr || K->slice_ptr != A->slice_ptr || Ac->slice_ptr != A->slice_ptr)
-    OX_FAIL("ox_scalar_rows_cellvisc: A, M, K and A_c must share one sparsity pattern");
-  if (Ac->vals == A->vals || Ac->vals == M->vals || Ac->vals == K->vals)
-    OX_FAIL("ox_scalar_rows_cellvisc: A_c needs a value array of its own");
-  if (!(dt > 0.0)) OX_FAIL("ox_scalar_rows_cellvisc: dt=%g", dt);
-  if (ncomp < 1 || ncomp > OX_MAXC) OX_FAIL("ox_scalar_rows_cellvisc: ncomp=%d", ncomp);
+    OX_FAIL("%s: A, M, K and A_c must share one sparsity pattern", who);
+  if (Ac->vals == A->vals || Ac->vals == M->vals || Ac->vals == K->vals) OX_FAIL("%s: A_c needs a value array of its own", who);
+  if (!(dt > 0.0)) OX_FAIL("%s: dt=%g", who, dt);
+  if (ncomp < 1 || ncomp > OX_MAXC) OX_FAIL("%s: ncomp=%d", who, ncomp);
   if (A->n_slices <= 0) return 0;
   const RowLaunch L{cells, space, row_blocks == 1, ox_stream(stream)};
-  const ScalarVisArgs F{M->vals, K->vals, nut, c1, b0, Ac->vals, b, a_c1, s, t, 2.0 / dt,
-                        M->vcode, K->vcode, M->vdict, K->vdict, M->n_dict, K->n_dict};
+  F.Mv = M->vals, F.Kv = K->vals, F.Acv = Ac->vals, F.two_idt = 2.0 / dt;
+  F.Mc = M->vcode, F.Kc = K->vcode, F.Md = M->vdict, F.Kd = K->vdict, F.nMd = M->n_dict, F.nKd = K->n_dict;
   const int g = cells->gdim, degree = space->degree, pw = space->pw;
   int rc = -1;
   bool found = false;
-  if (ox_prof_on) ox_prof_start(OX_TAG_SCALAR_ROWS_CELLVISC, L.st, ncomp);
-#define OX_SCV_CASE(GD, DG, P)                                 \
-  if (!found && g == GD && degree == DG && pw == P) {          \
-    found = true;                                              \
-    rc = launch_scalar_cellvisc<GD, DG, P>(L, A, F, ncomp);    \
+  if (ox_prof_on) ox_prof_start(tag, L.st, ncomp);
+#define OX_SCV_CASE(GD, DG, P)                                            \
+  if (!found && g == GD && degree == DG && pw == P) {                     \
+    found = true;                                                         \
+    rc = launch_scalar_cellvisc<GD, DG, P, SUPG>(who, L, A, F, ncomp);    \
   }
   OX_SCV_CASE(2, 1, 4) OX_SCV_CASE(2, 2, 8) OX_SCV_CASE(3, 1, 4) OX_SCV_CASE(3, 2, 16) OX_SCV_CASE(2, 3, 16) OX_SCV_CASE(3, 3, 32)
 #undef OX_SCV_CASE
   if (ox_prof_on) ox_prof_stop(L.st);
-  if (!found) OX_FAIL("ox_scalar_rows_cellvisc: unsupported gdim=%d degree=%d (adj_pos stride %d)", g, degree, pw);
+  if (!found) OX_FAIL("%s: unsupported gdim=%d degree=%d (adj_pos stride %d)", who, g, degree, pw);
   return rc;
+}
+
+extern "C" int ox_scalar_rows_cellvisc(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
+                                       const ox_sell *K, const ox_sell *Ac, const double *nut, double s, double t, double dt,
+                                       int ncomp, const double *c1, const double *b0, double *b, double *a_c1, int row_blocks,
+                                       void *stream) {
+  ScalarVisArgsT<false> F{};
+  F.nut = nut, F.c1 = c1, F.b0 = b0, F.b = b, F.a_c1 = a_c1, F.s = s, F.t = t;
+  return scalar_rows_cells<false>("ox_scalar_rows_cellvisc", OX_TAG_SCALAR_ROWS_CELLVISC, cells, space, A, M, K, Ac, !nut, dt,
+                                  ncomp, row_blocks, stream, F);
+}
+
+extern "C" int ox_scalar_rows_supg(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
+                                   const ox_sell *K, const ox_sell *Ac, const double *nut, const double *rec, double s,
+                                   double t, double dt, int ncomp, const double *c1, const double *b0, const double *fh,
+                                   double *b, double *a_c1, int row_blocks, void *stream) {
+  ScalarVisArgsT<true> F{};
+  F.nut = nut, F.c1 = c1, F.b0 = b0, F.b = b, F.a_c1 = a_c1, F.s = s, F.t = t;
+  F.rec = rec, F.fh = fh;
+  F.cell_dofs = space ? space->cell_dofs : nullptr;
+  F.n_cells = cells ? cells->n_cells : 0;
+  return scalar_rows_cells<true>("ox_scalar_rows_supg", OX_TAG_SCALAR_ROWS_SUPG, cells, space, A, M, K, Ac,
+                                 !rec || !fh || !F.cell_dofs, dt, ncomp, row_blocks, stream, F);
 }
 
 // ---------------------------------------------------------------------------------------

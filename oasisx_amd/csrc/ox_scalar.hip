@@ -25,6 +25,7 @@
 //                       e_rs = (1/2) |f| sum_k w_k hq phi_r phi_s,   A_c[r][s] += e_rs,
 //                       b_c[r][col] += |f| sum_k w_k (q_col + hq c_inf,col) phi_r - sum_s e_rs c_1[s][col]
 //                     The lane owns its row of A_c and of b_c: no atomics, no LDS, a fixed order of sums.
+#include "fe_tables_d.h"
 #include "ox_element.h"
 
 namespace {
@@ -556,4 +557,84 @@ extern "C" int ox_scalar_boundary(const ox_cells *cells, const int32_t *cell_dof
   OX_FOR_GDIM_DEG(OX_SCALAR_BC_CASE)
 #undef OX_SCALAR_BC_CASE
   OX_FAIL("ox_scalar_boundary: unsupported gdim=%d, P%d", g, P.degree);
+}
+
+// ---- SUPG stabilisation ----------------------------------------------------------------------------
+// Per cell c, one lane, no LDS, no atomics: the frozen velocity w_c = u_ab at the centroid (the centroid values of the basis,
+// fe_tables_d.h, in the dof order of k_drag_sigma) and Shakib's parameter
+//   tau_c = scale ([time_term] (2/dt)^2 + (k q_c)^2 + (2 k^2 kappa_c g_c)^2)^(-1/2),
+//   q_c = sum_a |w_c . G[a]|,  g_c = sum_a |G[a]|^2,  kappa_c = kappa + inv_sct nut_c,  k = the element's degree.
+// Nothing is divided by |w|: w = 0 gives a finite tau (0 where every term under the root is 0); a velocity that is not finite
+// is shown, not clipped: NaN.  rec is a structure of arrays in kernel cell order: rec[d][c] = w_c[d], rec[GDIM][c] = tau_c.
+namespace {
+
+template <int GDIM, int DEG>
+__global__ __launch_bounds__(256) void k_supg_cells(ox_cells cells, const int32_t *__restrict__ cell_dofs,
+                                                    const double *__restrict__ uab, const double *__restrict__ nut,
+                                                    double kappa, double inv_sct, double t2, double scale,
+                                                    double *__restrict__ rec) {
+  constexpr int ND = ox_nd(GDIM, DEG);
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= cells.n_cells) return;
+  int32_t dd[ND];
+  ox_load_dofs<ND>(cell_dofs, e, dd);
+  double G[GDIM + 1][GDIM], adet;
+  ox_load_geom<GDIM>(cells.geom + (size_t)e * ox_gs(GDIM), G, adet);
+  double uc[ND][GDIM];
+  ox_gather<ND, GDIM>(dd, uab, uc);
+  const auto phic = [](int i) -> double { OX_FE_PICK(GDIM, DEG, OX_PHIC, [i]); };
+  double w[GDIM] = {};
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+    if (phic(i) != 0.0) {
+#pragma unroll
+      for (int d = 0; d < GDIM; ++d) w[d] = fma(uc[i][d], phic(i), w[d]);
+    }
+  double q = 0.0, g = 0.0;
+#pragma unroll
+  for (int a = 0; a <= GDIM; ++a) {
+    double wa = 0.0;
+#pragma unroll
+    for (int d = 0; d < GDIM; ++d) {
+      wa = fma(w[d], G[a][d], wa);
+      g = fma(G[a][d], G[a][d], g);
+    }
+    q += fabs(wa);
+  }
+  const double kap = nut ? fma(inv_sct, nut[e], kappa) : kappa;
+  const double cq = DEG * q, cd = (2.0 * DEG * DEG) * kap * g;
+  const double r = fma(cd, cd, fma(cq, cq, t2));
+  double tau = r > 0.0 ? scale / sqrt(r) : 0.0;
+  if (!isfinite(r)) tau = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+  for (int d = 0; d < GDIM; ++d) rec[(size_t)d * cells.n_cells + e] = w[d];
+  rec[(size_t)GDIM * cells.n_cells + e] = tau;
+}
+
+}  // namespace
+
+extern "C" int ox_supg_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, const double *uab,
+                             const double *nut, double kappa, double inv_sct, double dt, double scale, int time_term,
+                             double *rec, void *stream) {
+  if (!cells || !cells->geom || !cell_dofs || !uab || !rec) OX_FAIL("ox_supg_cells: null argument");
+  if (!(dt > 0.0)) OX_FAIL("ox_supg_cells: dt=%g", dt);
+  if (!(scale > 0.0) || !(kappa >= 0.0) || !(inv_sct >= 0.0))
+    OX_FAIL("ox_supg_cells: scale=%g, kappa=%g, 1/Sc_t=%g", scale, kappa, inv_sct);
+  const int64_t nblk = ox_cell_blocks("ox_supg_cells", cells);
+  if (nblk <= 0) return (int)nblk;
+  hipStream_t st = ox_stream(stream);
+  const int g = cells->gdim;
+  const double t2 = time_term ? (2.0 / dt) * (2.0 / dt) : 0.0;
+#define OX_SUPG_CELLS_CASE(GD, DG)                                                                                   \
+  if (g == GD && degree == DG) {                                                                                     \
+    if (ox_prof_on) ox_prof_start(OX_TAG_SUPG_CELLS, st, cells->n_cells);                                            \
+    hipLaunchKernelGGL((k_supg_cells<GD, DG>), dim3((unsigned)nblk), dim3(256), 0, st, *cells, cell_dofs, uab, nut,  \
+                       kappa, inv_sct, t2, scale, rec);                                                              \
+    if (ox_prof_on) ox_prof_stop(st);                                                                                \
+    OX_LAUNCH_CHECK();                                                                                               \
+    return 0;                                                                                                        \
+  }
+  OX_FOR_GDIM_DEG(OX_SUPG_CELLS_CASE)
+#undef OX_SUPG_CELLS_CASE
+  OX_FAIL("ox_supg_cells: unsupported gdim=%d, P%d", g, degree);
 }

@@ -105,6 +105,8 @@ class FractionalStep_AB_CN:
             the extrapolated velocity and solved once per step after the velocity update (:mod:`oasisx_amd.scalar`);
             ``None`` / ``[]``: no scalar phase runs.  ``ScalarTransport(flux_bcs=[FluxBC, RobinBC])``: prescribed fluxes,
             film and open-boundary conditions on exterior facets (``scalar_boundary_assemble``).
+            ``ScalarTransport(stabilization=SUPG(...))``: streamline-upwind Petrov-Galerkin stabilisation for
+            convection-dominated scalars (``scalar_stabilization_assemble``, ``supg_parameter``).
             A scalar is passive unless it is given ``buoyancy=b``: then
             component ``i`` of the momentum equation gains the Boussinesq force ``b_i (c* - reference)``, with ``c*`` the
             scalar extrapolated to the step's midpoint, added to ``b_first`` inside ``assemble_first`` in one pass over the
@@ -752,8 +754,9 @@ class FractionalStep_AB_CN:
     def scalar_assemble(self, dt: float, nu: float):
         """Per scalar group: A_c = A + (kappa - nu)/2 K, b_c = (2/dt) M c_1 - A_c c_1 + b0_c and, for a solver with a nonzero
         initial guess, A_c c_1 -- one pass over the values of the shared pattern (``ox_scalar_rows``; with a
-        ``viscosity_model`` and ``Sc_t != 1``: A_c = A + s K + t K_t, ``ox_scalar_rows_cellvisc``); then the group's own
-        Dirichlet rows.  Runs INSIDE ``assemble_first``, between the fused kernel and the velocity's boundary rows:
+        ``viscosity_model`` and ``Sc_t != 1``: A_c = A + s K + t K_t, ``ox_scalar_rows_cellvisc``; with
+        ``stabilization=SUPG(...)``: + N/dt + S/2 and the stabilised right-hand side, ``ox_scalar_rows_supg``); then the
+        group's own Dirichlet rows.  Runs INSIDE ``assemble_first``, between the fused kernel and the velocity's boundary rows:
         afterwards those rows of ``A`` are gone."""
         if not self._A_pre_bc:
             raise RuntimeError("scalar_assemble runs inside assemble_first (which calls it): afterwards the velocity's "
@@ -774,6 +777,31 @@ class FractionalStep_AB_CN:
             raise RuntimeError("scalar_boundary_assemble runs inside assemble_first (whose scalar_assemble calls it): it "
                                "adds to the A_c and b_c that the row kernel has just written, once per step")
         g.boundary.add()
+
+    @_phase
+    def scalar_stabilization_assemble(self, dt: float, nu: float):
+        """``w_c`` and ``tau_c`` per cell of a scalar group with ``stabilization=SUPG(...)`` (``ox_supg_cells``, from the
+        ``u_ab`` block -- and the ``nut`` -- ``assemble_first`` has just formed).  Runs INSIDE ``scalar_assemble``, per
+        stabilised group, before its row kernel (``ox_scalar_rows_supg``); a group without stabilisation never calls it."""
+        g = self._scalar_rows_open
+        if g is None or g.stabilization is None:
+            raise RuntimeError("scalar_stabilization_assemble runs inside assemble_first (whose scalar_assemble calls it) "
+                               "for a scalar group with stabilization=")
+        from . import scalar as _sc
+
+        _sc.stabilization_cells(self, g, dt, nu)
+
+    def supg_parameter(self, name: str) -> torch.Tensor:
+        """``tau_c`` per cell of the stabilised scalar ``name`` as the last ``assemble_first`` used it: a device tensor
+        ``(num_cells,)`` in the MESH's cell order, as ``eddy_viscosity()`` gives ``nut``."""
+        if name not in self._scalar_index:
+            raise KeyError(f"no scalar named {name!r} (have: {sorted(self._scalar_index)})")
+        g, _ = self._scalar_index[name]
+        if g.stabilization is None:
+            raise RuntimeError(f"supg_parameter: the scalar {name!r} has no stabilization=")
+        out = torch.zeros(int(self._mesh.num_cells), dtype=torch.float64, device=g.supg_rec.device)
+        out[self._Vi[0][0].local_cells.to(torch.int64)] = g.supg_rec[self._gdim]
+        return out
 
     @_phase
     def buoyancy_assemble(self):

@@ -7,7 +7,7 @@ pressure iteration and is solved once)::
     b_c = (M/dt - C/2 - kappa K/2) c_1 + b0_c  =  (2/dt) M c_1 - A_c c_1 + b0_c
     the scalar's own Dirichlet rows -> identity in A_c, boundary value in b_c;  solve A_c c = b_c;  c_1 <- c
 
-Plain Galerkin.  ``C(u_ab)`` is what the velocity step assembles anyway:
+Plain Galerkin unless the scalar states ``stabilization=`` (SUPG, below).  ``C(u_ab)`` is what the velocity step assembles anyway:
 ``A_c = A + (kappa - nu)/2 K`` with the velocity matrix ``A`` before its boundary rows, one streaming pass over the
 values of the shared SELL-64 pattern (``ox_scalar_rows``, csrc/ox_scalar.hip) instead of a second element loop.
 
@@ -42,6 +42,30 @@ Natural boundary conditions other than the insulated wall
 Crank-Nicolson in ``c``: ``A_c += H/2``, ``b_c += load - (H/2) c_1`` with ``H_rs = int hq phi_r phi_s ds`` and
 ``load_r = int (q + hq c_inf) phi_r ds``, by ``ox_scalar_boundary`` after ``ox_scalar_rows`` and before the group's Dirichlet
 rows (which win on rim dofs): one lane per touched row, no atomics.
+
+Convection-dominated scalars (cell Peclet number >> 1), ``stabilization=SUPG(scale, time_term)`` (streamline-upwind
+Petrov-Galerkin, DESIGN.md section 32).  Per cell ``c``, with ``k`` the element degree and ``G[a] = grad lambda_a``::
+
+    w_c     = u_ab(x_c)                     the extrapolated velocity at the centroid
+    q_c     = sum_a |w_c . G[a]|,   g_c = sum_a |G[a]|^2
+    kappa_c = kappa + nut_c / Sc_t          (kappa without a viscosity model, with Sc_t = inf and with a law)
+    tau_c   = scale ([time_term] (2/dt)^2 + (k q_c)^2 + (2 k^2 kappa_c g_c)^2)^(-1/2)         (Shakib)
+
+(1-D P1: ``((2/dt)^2 + (2|w|/h)^2 + (4 kappa/h^2)^2)^(-1/2)``; nothing is divided by ``|w|``: ``w = 0`` gives a finite
+``tau`` and no stabilising term, a ``w`` that is not finite gives NaN.)  The test function ``phi_i + tau_c w_c . grad phi_i``
+is applied to the Crank-Nicolson residual, with the advecting velocity INSIDE the stabilising terms frozen at ``w_c`` and
+the second-derivative term ``tau (w . grad phi_i) kappa lap c`` dropped (exactly zero for P1; for P2 / P3 a stated limit:
+the scheme stays consistent to the order of that term).  With::
+
+    N_ij = sum_c tau_c int_c (w_c . grad phi_i) phi_j,      S_ij = sum_c tau_c int_c (w_c . grad phi_i)(w_c . grad phi_j)
+    A_c  = A + s K + t K_t + N/dt + S/2
+    b_c  = (2/dt) M c_1 - A_c c_1 + b0_c + N ((2/dt) c_1 + f_h)          f_h: the nodal interpolant of ``source``
+
+One per-cell launch (``ox_supg_cells``: ``w_c``, ``tau_c``) and ONE fused row launch per group (``ox_scalar_rows_supg``,
+the sibling of ``ox_scalar_rows_cellvisc``: the same LDS accumulator and ``StiffTab`` contraction with
+``t nut_c G[a].G[b] + (tau_c/2)(w_c.G[a])(w_c.G[b])``, the time term from one more compile-time table, the right-hand side
+term per lane in registers).  Flux / Robin pass, Dirichlet rows, solve and time levels are unchanged.  A scalar without
+``stabilization=`` makes neither call.
 """
 from __future__ import annotations
 
@@ -55,9 +79,37 @@ from .fem import FieldStorage, Function, Vector
 from .ksp import KSPSolver
 from .la import SellMatrix
 
-__all__ = ["ScalarTransport", "ScalarFlux", "FluxBC", "RobinBC"]
+__all__ = ["ScalarTransport", "ScalarFlux", "FluxBC", "RobinBC", "SUPG"]
 
 MAX_COLUMNS = 3  # OX_MAXC: the columns ox_ksp_solve / ox_spmv take in lock-step
+
+
+class SUPG:
+    """Streamline-upwind Petrov-Galerkin stabilisation of a :class:`ScalarTransport` (module docstring, DESIGN.md
+    section 32).
+
+    Args:
+        scale: a finite float > 0 that multiplies Shakib's ``tau`` (1: the standard parameter)
+        time_term: ``True`` (default): ``(2/dt)^2`` stands under the root of ``tau``, so ``tau <= dt/2``; ``False``: the
+            steady-state parameter
+    """
+
+    def __init__(self, scale: float = 1.0, time_term: bool = True):
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"SUPG: scale = {scale!r}: a finite float > 0 is expected") from None
+        if not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError(f"SUPG: scale = {scale}: a finite float > 0 is expected")
+        if not isinstance(time_term, (bool, np.bool_)):
+            raise TypeError(f"SUPG: time_term = {time_term!r}: a bool is expected")
+        self.scale, self.time_term = scale, bool(time_term)
+
+    def key(self):
+        return (self.scale, self.time_term)
+
+    def __repr__(self):
+        return f"SUPG(scale={self.scale}, time_term={self.time_term})"
 
 
 class ScalarTransport:
@@ -87,10 +139,13 @@ class ScalarTransport:
         flux_bcs: list of :class:`FluxBC` / :class:`RobinBC`: prescribed fluxes, film and open-boundary conditions on
             exterior facets (one GPU).  Several conditions may share a facet: their ``q`` and ``h`` add.  Without them
             the natural condition is the insulated wall, and none of their calls is made
+        stabilization: ``None`` (default): plain Galerkin.  :class:`SUPG`: the streamline-upwind Petrov-Galerkin scheme of
+            the module docstring, for cell Peclet numbers far above 1 (``source`` is then interpolated at the dofs for
+            the stabilised source term: an ``Expression`` source raises ``NotImplementedError``).  One GPU
     """
 
     def __init__(self, name, diffusivity=None, schmidt=None, bcs=(), source=0.0, initial=None, buoyancy=None,
-                 reference=0.0, extrapolate=True, turbulent_schmidt=None, flux_bcs=()):
+                 reference=0.0, extrapolate=True, turbulent_schmidt=None, flux_bcs=(), stabilization=None):
         if not isinstance(name, str) or not name:
             raise ValueError("ScalarTransport: name must be a non-empty string")
         if (diffusivity is None) == (schmidt is None):
@@ -139,6 +194,13 @@ class ScalarTransport:
                 raise ValueError(f"ScalarTransport {name!r}: turbulent_schmidt = {turbulent_schmidt}: a float > 0 or "
                                  "float('inf') is expected")
         self.turbulent_schmidt = turbulent_schmidt
+        if stabilization is not None and not isinstance(stabilization, SUPG):
+            raise TypeError(f"ScalarTransport {name!r}: stabilization is None or a SUPG object (got "
+                            f"{type(stabilization).__name__})")
+        if stabilization is not None and isinstance(self.source, Expression):
+            raise NotImplementedError(f"ScalarTransport {name!r}: stabilization= with an Expression source: the stabilised "
+                                      "source term needs a nodal interpolant (a float, a callable f(x) or a Function)")
+        self.stabilization = stabilization
 
     def inverse_turbulent_schmidt(self) -> float:
         """``1 / Sc_t``; 0 for ``inf`` (and where none was given)."""
@@ -149,7 +211,10 @@ class ScalarTransport:
 
     def _spec(self):
         spec = ("kappa", self.diffusivity) if self.schmidt is None else ("schmidt", self.schmidt)
-        return spec + (("turbulent_schmidt", self.turbulent_schmidt),)
+        spec += (("turbulent_schmidt", self.turbulent_schmidt),)
+        if self.stabilization is not None:  # (a scalar without it keeps the key it had)
+            spec += (("supg",) + self.stabilization.key(),)
+        return spec
 
 
 # ---- flux and Robin conditions -----------------------------------------------------------------------------------------
@@ -443,6 +508,13 @@ class ScalarGroup:
         self.reasons = None
         self.ax0_valid = False  # AC1 holds A_c c_1 of the last assembly and has not been used yet
         self.boundary = None  # the flux / Robin pass (BoundaryPass), where a member has flux_bcs
+        # SUPG (equal across the members: it is part of the group's key): the nodal source f_h and the per-cell record
+        # of ox_supg_cells, a structure of arrays in kernel cell order: w_c (gdim rows), then tau_c
+        self.stabilization = members[0].stabilization
+        self.FH = self.supg_rec = None
+        if self.stabilization is not None:
+            self.FH = FieldStorage(n, nc, dev)
+            self.supg_rec = torch.zeros((solver._gdim + 1, int(solver._geom.shape[0])), dtype=torch.float64, device=dev)
 
     def wants_ax0(self) -> bool:
         o = self.ksp._options
@@ -504,6 +576,14 @@ def set_initial(solver, group: ScalarGroup):
         elif f is not None and f != 0.0:
             group.C1.dev()[: Vi.n_local, j] = float(f)
         group.B0.dev()[: Vi.n_owned, j] = solver._source_vector(s.source, f"ScalarTransport {s.name!r}: source")
+        if group.FH is not None:  # f_h, the nodal interpolant of the source
+            f = s.source
+            if isinstance(f, Function):
+                group.FH.dev()[:, j] = f._storage.rdev()[:, 0 if f._comp is None else f._comp]
+            elif callable(f):
+                Function(Vi, s.name + "_source", group.FH, j).interpolate(f)
+            else:
+                group.FH.dev()[: Vi.n_local, j] = float(f)
     group.C.dev().copy_(group.C1.rdev())
     if group.C2 is not None:
         group.C2.dev().copy_(group.C1.rdev())
@@ -551,7 +631,21 @@ def assemble(solver, group: ScalarGroup, dt: float, nu: float):
     if group.boundary is not None and group.boundary.robin:
         au = None  # A_c changes after the row kernel: its A_c c_1 by-product is not asked for
     t = 0.0 if solver._viscosity_model is None else turbulent_factor(solver, group.members[0])
-    if t == 0.0:  # no model, or Sc_t = 1: the scalar's operator differs from A by a multiple of K alone
+    if group.stabilization is not None:  # SUPG: tau_c and w_c per cell, then the sibling of the cell-viscosity rows
+        Vi = solver._Vi[0][0]
+        solver._scalar_rows_open = group
+        try:
+            solver.scalar_stabilization_assemble(dt, nu)
+        finally:
+            solver._scalar_rows_open = None
+        _lib.check(lib.ox_scalar_rows_supg(C.byref(solver._cells), C.byref(Vi.assembly_info()), solver._A.ref(),
+                                           solver._M.ref(), solver._K.ref(), group.Ac.ref(),
+                                           _lib.ptr(solver._nut) if t != 0.0 else None, _lib.ptr(group.supg_rec),
+                                           0.5 * (kappa - float(nu)), t, float(dt), group.nc, group.C1.rptr(),
+                                           group.B0.rptr(), group.FH.rptr(), group.B.ptr(), au,
+                                           int(solver._row_blocks and Vi.pattern.n_row_blocks > 0), st),
+                   "ox_scalar_rows_supg")
+    elif t == 0.0:  # no model, or Sc_t = 1: the scalar's operator differs from A by a multiple of K alone
         _lib.check(lib.ox_scalar_rows(solver._A.ref(), solver._M.ref(), solver._K.ref(), group.Ac.ref(),
                                       0.5 * (kappa - float(nu)), float(dt), group.nc, group.C1.rptr(), group.B0.rptr(),
                                       group.B.ptr(), au, st), "ox_scalar_rows")
@@ -576,6 +670,19 @@ def assemble(solver, group: ScalarGroup, dt: float, nu: float):
         for bc in s.bcs:
             bc.apply(group.bc_vector(j))
     group.ax0_valid = au is not None
+
+
+def stabilization_cells(solver, group: ScalarGroup, dt: float, nu: float):
+    """``w_c`` and ``tau_c`` of a stabilised group from the ``u_ab`` block (and the ``nut``) of this step
+    (``ox_supg_cells``)."""
+    Vi = solver._Vi[0][0]
+    m, sp = group.members[0], group.stabilization
+    model = solver._viscosity_model
+    inv = m.inverse_turbulent_schmidt() if model is not None and model.diffuses_scalars else 0.0
+    _lib.check(solver._lib.ox_supg_cells(Vi.degree, C.byref(solver._cells), _lib.ptr(Vi.cell_dofs), solver._UAB.rptr(),
+                                         _lib.ptr(solver._nut) if inv != 0.0 else None, float(m.kappa(nu)), inv, float(dt),
+                                         sp.scale, int(sp.time_term), _lib.ptr(group.supg_rec), _lib.current_stream()),
+               "ox_supg_cells")
 
 
 def solve(solver, group: ScalarGroup):
