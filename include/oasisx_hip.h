@@ -998,13 +998,14 @@ int ox_supg_cells(int degree, const ox_cells *cells, const int32_t *cell_dofs, c
                   double kappa, double inv_sct, double dt, double scale, int time_term, double *rec, void *stream);
 /* ox_scalar_rows_supg: the sibling of ox_scalar_rows_cellvisc (same launches, same LDS accumulators, row_blocks as there):
  *   N_ij = sum_c tau_c int_c (w_c . grad phi_i) phi_j,   S_ij = sum_c tau_c int_c (w_c . grad phi_i)(w_c . grad phi_j)
- *   A_c  = A + s K + t K_t + N/dt + S/2      per entry v = acc + fma(s, k, a), acc = the rows of t K_t + N/dt + S/2 from LDS
+ *   A_c  = A + s K + t K_t + N/dt + S/2      per entry v = fma(t, acc, fma(s, k, a)), acc = the rows of K_t + (N/dt + S/2)/t from LDS
  *   b    = (2/dt) M c1 - A_c c1 + b0 + N ((2/dt) c1 + fh)          (the last term per lane in registers, from the cells' dofs)
  *   a_c1 = A_c c1                             (optional; bit-identical to ox_spmv(Ac, c1))
- * rec: what ox_supg_cells wrote.  nut may be NULL (no model, or t = 0): then t is not read.  fh: the nodal interpolant of
+ * rec: what ox_supg_cells wrote.  nut may be NULL (no model, or t = 0): then t is not read (t = 1 in the lines above).  fh: the nodal interpolant of
  * the source, an interleaved (n, ncomp) block as c1.  The second-derivative term tau (w . grad phi_i) kappa lap c is
- * dropped (zero for P1).  w = 0 everywhere and nut == NULL give the bits of ox_scalar_rows.  No atomics to global memory,
- * fixed order of sums, no scratch. */
+ * dropped (zero for P1).  w = 0 everywhere gives the bits of ox_scalar_rows_cellvisc with the same nut and t (the accumulator
+ * rows are formed by the sibling's operations), and with nut == NULL those of ox_scalar_rows.  No atomics to global
+ * memory, fixed order of sums, no scratch. */
 int ox_scalar_rows_supg(const ox_cells *cells, const ox_space_info *space, const ox_sell *A, const ox_sell *M,
                         const ox_sell *K, const ox_sell *Ac, const double *nut, const double *rec, double s, double t,
                         double dt, int ncomp, const double *c1, const double *b0, const double *fh, double *b, double *a_c1,

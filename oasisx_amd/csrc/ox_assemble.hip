@@ -10,6 +10,7 @@
 #include "ox_element.h"
 #include <stdlib.h>
 #include <algorithm>
+#include <cmath>
 
 #define OX_KIND_MASS 0
 #define OX_KIND_STIFF 1
@@ -869,9 +870,11 @@ struct ScalarVisArgs {
 // parameter tau_c (ox_supg_cells: rec[d][e] = w_d, rec[GDIM][e] = tau, kernel cell order), and
 //   A_c = A + s K + t K_t + N/dt + S/2,   b_c = (2/dt) M c_1 - A_c c_1 + b0 + N ((2/dt) c_1 + f_h)
 //   N_ij = sum_c tau_c int_c (w_c . grad phi_i) phi_j,   S_ij = sum_c tau_c int_c (w_c . grad phi_i)(w_c . grad phi_j).
-// The pair loop makes the ONE StiffTab contraction with gg[a][b] = t nut G[a].G[b] + (tau/2)(w.G[a])(w.G[b]), adds
-// (tau/dt) sum_a (w.G[a]) NT[i][a][j] (SupgTab, from LDS with the lane's row dof) and sums the lane's entry of
-// N ((2/dt) c_1 + f_h) in registers from the cell's dofs; the epilogue adds the accumulator as it is, v = acc + fma(s, k, a).
+// The pair loop makes the ONE StiffTab contraction with gg[a][b] = nut G[a].G[b] + (tau/(2t))(w.G[a])(w.G[b]), adds
+// (tau/(t dt)) sum_a (w.G[a]) NT[i][a][j] (SupgTab, from LDS with the lane's row dof) and sums the lane's entry of
+// N ((2/dt) c_1 + f_h) in registers from the cell's dofs; the accumulator holds K_t + (N/dt + S/2)/t and the epilogue is the
+// sibling's, v = fma(t, acc, fma(s, k, a)): with w = 0 every operation is the sibling's, so the rows are its bits.  Without
+// nut (no model, or t = 0) the entry sets t = 1: the accumulator is N/dt + S/2 and fma(1, acc, x) rounds as acc + x.
 // The fields exist in the SUPG instantiations only (as FirstArgsT<NUT>): the others keep their argument block and code.
 template <bool SUPG>
 struct ScalarVisArgsT : ScalarVisArgs {};
@@ -880,6 +883,7 @@ struct ScalarVisArgsT<true> : ScalarVisArgs {
   const double *rec, *fh;
   const int32_t *cell_dofs;
   int64_t n_cells;
+  double inv_t;  // 1 / t (t = 1 without nut): the stabilising terms enter the accumulator divided by t
 };
 
 template <int GDIM, int DEG, int PW, int NC, bool DICT, bool SUPG = false>
@@ -922,21 +926,21 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
       *reinterpret_cast<uint32_t *>(pos) = *reinterpret_cast<const uint32_t *>(adj_pos + pidx * 4);
     }
     double nutv;
-    if constexpr (SUPG) nutv = F.nut ? F.t * F.nut[e] : 0.0;  // (t nut_c: the accumulator is added as it is)
+    if constexpr (SUPG) nutv = F.nut ? F.nut[e] : 0.0;
     else nutv = F.nut[e];
     double G[GDIM + 1][GDIM], adet;
     ox_load_geom<GDIM>(cells.geom + (size_t)e * GS, G, adet);
     double c[ND];
 #pragma unroll
     for (int j = 0; j < ND; ++j) c[j] = 0.0;
-    // SUPG: wa[a] = w_c . G[a], th = tau_c / 2, nr[j] = int (w_c . grad phi_i) phi_j / |J|
+    // SUPG: wa[a] = w_c . G[a], th = tau_c / (2 t), nr[j] = int (w_c . grad phi_i) phi_j / |J|
     [[maybe_unused]] double wa[GDIM + 1], th = 0.0, tau = 0.0, nr[ND];
     if constexpr (SUPG) {
       double w[GDIM];
 #pragma unroll
       for (int d = 0; d < GDIM; ++d) w[d] = F.rec[(size_t)d * F.n_cells + e];
       tau = F.rec[(size_t)GDIM * F.n_cells + e];
-      th = 0.5 * tau;
+      th = (0.5 * tau) * F.inv_t;
 #pragma unroll
       for (int a = 0; a <= GDIM; ++a) {
         double v = 0.0;
@@ -1038,8 +1042,8 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
       }
     }
     if constexpr (SUPG) {
-      // the time term into the row, (tau/dt) nr[j], and the lane's share of N ((2/dt) c_1 + f_h) from the cell's dofs
-      const double tdt = tau * (0.5 * F.two_idt);
+      // the time term into the row, (tau/(t dt)) nr[j], and the lane's share of N ((2/dt) c_1 + f_h) from the cell's dofs
+      const double tdt = tau * (0.5 * F.two_idt) * F.inv_t;
       int32_t dd[ND];
       ox_load_dofs<ND>(F.cell_dofs, e, dd);
       double r[NC];
@@ -1078,7 +1082,7 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
   const unsigned short *__restrict__ mc = DICT ? reinterpret_cast<const unsigned short *>(F.Mc + base) + lane : nullptr;
   const unsigned short *__restrict__ kc = DICT ? reinterpret_cast<const unsigned short *>(F.Kc + base) + lane : nullptr;
   const double s = F.s;
-  [[maybe_unused]] const double tt = F.t;
+  const double tt = F.t;
   double sa[NC], sm[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) sa[c] = sm[c] = 0.0;
@@ -1113,13 +1117,8 @@ __device__ __forceinline__ void scalar_cellvisc_slice(const ox_cells &cells, con
       const int k = k0 + q;
       if (k < npair) {
         v2d v;
-        if constexpr (SUPG) {
-          v.x = acc[(2 * k) * 64 + lane] + fma(s, kk[q].x, a[q].x);
-          v.y = acc[(2 * k + 1) * 64 + lane] + fma(s, kk[q].y, a[q].y);
-        } else {
-          v.x = fma(tt, acc[(2 * k) * 64 + lane], fma(s, kk[q].x, a[q].x));
-          v.y = fma(tt, acc[(2 * k + 1) * 64 + lane], fma(s, kk[q].y, a[q].y));
-        }
+        v.x = fma(tt, acc[(2 * k) * 64 + lane], fma(s, kk[q].x, a[q].x));
+        v.y = fma(tt, acc[(2 * k + 1) * 64 + lane], fma(s, kk[q].y, a[q].y));
         __builtin_nontemporal_store(v, ov + (size_t)k * 64);
 #pragma unroll
         for (int c = 0; c < NC; ++c) sa[c] = fma(v.x, x0[q][c], sa[c]);  // entry order and operations of k_spmv
@@ -1302,7 +1301,10 @@ extern "C" int ox_scalar_rows_supg(const ox_cells *cells, const ox_space_info *s
                                    double t, double dt, int ncomp, const double *c1, const double *b0, const double *fh,
                                    double *b, double *a_c1, int row_blocks, void *stream) {
   ScalarVisArgsT<true> F{};
-  F.nut = nut, F.c1 = c1, F.b0 = b0, F.b = b, F.a_c1 = a_c1, F.s = s, F.t = t;
+  // nut is read only where t K_t is there and 1 / t is finite; otherwise t = 1 and the accumulator is N/dt + S/2
+  const bool with_nut = nut && t != 0.0 && std::isfinite(1.0 / t);
+  F.nut = with_nut ? nut : nullptr, F.c1 = c1, F.b0 = b0, F.b = b, F.a_c1 = a_c1, F.s = s, F.t = with_nut ? t : 1.0;
+  F.inv_t = 1.0 / F.t;
   F.rec = rec, F.fh = fh;
   F.cell_dofs = space ? space->cell_dofs : nullptr;
   F.n_cells = cells ? cells->n_cells : 0;

@@ -63,7 +63,7 @@ the scheme stays consistent to the order of that term).  With::
 
 One per-cell launch (``ox_supg_cells``: ``w_c``, ``tau_c``) and ONE fused row launch per group (``ox_scalar_rows_supg``,
 the sibling of ``ox_scalar_rows_cellvisc``: the same LDS accumulator and ``StiffTab`` contraction with
-``t nut_c G[a].G[b] + (tau_c/2)(w_c.G[a])(w_c.G[b])``, the time term from one more compile-time table, the right-hand side
+``nut_c G[a].G[b] + (tau_c/(2t))(w_c.G[a])(w_c.G[b])``, the time term from one more compile-time table, the right-hand side
 term per lane in registers).  Flux / Robin pass, Dirichlet rows, solve and time levels are unchanged.  A scalar without
 ``stabilization=`` makes neither call.
 """

@@ -26,7 +26,11 @@ everywhere, so no tolerance exceeds about 1.2e-13 B.
 (``B`` is the running bound of a kernel whose own rule has positive weights.  The P3-tetrahedron kernels tabulate on the
 70-point Grundmann-Moeller rule, sum |w| / sum w = 25.4: their terms are that much larger than ``B``, and their measured
 errors stand out accordingly; family 0 of ox_assemble_rect, which missed the criterion that way, now contracts a tabulated
-tensor instead -- tests/test_gpu_assembly_entries.py)"""
+tensor instead -- tests/test_gpu_assembly_entries.py)
+
+The scalar row kernels (``scalar_rows``, ``scalar_rows_cellvisc``, ``scalar_rows_supg``: DESIGN.md sections 13, 25, 32) take
+the device's own A, M, K and the device's own SUPG records (w_c, tau_c), promoted exactly; ``supg_cells`` models those
+records, tau_c under a propagated absolute bound (tests/test_gpu_scalar_rows_entries.py)."""
 from __future__ import annotations
 
 import itertools
@@ -357,6 +361,34 @@ def chain(form, d, deg, deg2=None, nut=False, n_table=0):
         return nq + 3 + 1
     if form == "load":  # :888-891: n_q fma over the given table, one fma per cell
         return n_table + 1
+    # -- the per-cell chains of scalar_cellvisc_slice (ox_scalar_rows_cellvisc, ox_scalar_rows_supg) -----------------------
+    quad = d == 3 and deg == 3  # the P3 tetrahedron: the quadrature branches
+    tab = nq + 5  # an entry of StiffTab / SupgTab (:191-204, :228-240): NQ sums of w f g: NQ + 2 products + 3 constants
+    if form == "kt":  # K_t alone (SUPG = false)
+        if quad:  # :986-1011: gi (d fma, constant dphi), wn = w nut (2), h (d fma), sb = wn h, c (NQ d fma, constant dphi)
+            return (d + 1) + 2 + d + 1 + nq * d + 1 + last
+        # :1013-1035: gg = nut (G_a . G_b) (d fma, 1 product; G_0 in both factors: 2 g0), cm (d + 1 fma over the table),
+        # c[j] += cm (the (j, b) pairs of one j: d + 1)
+        return 2 * g0 + d + 1 + tab + (d + 1) + (d + 1) + last
+    if form == "kt_s":  # K_t + S/(2t) through the ONE contraction, and the fma of the time term that lands on the same c[j] (:1054)
+        # th = (tau / 2) (1 / t): the quotient (formed by the entry) and the product: 2
+        if quad:
+            # :954-985: wa (d fma), wg (d fma, constant dphi), ws = w th wg (constant, 2 products, th: 2), sb = fma(ws, wa_b,
+            # wn h): the longer branch is ws wa_b = (d + d + 1) + 5 + d against (d + 1) + 2 + d + 1 of (w nut) h; + the fma
+            return (3 * d + 6) + 1 + nq * d + 1 + 1 + last
+        # :945-950 wa (d fma; G_0: g0), :1024 gg = fma(th wa_a, wa_b, nut v): the longer branch th wa_a wa_b carries
+        # 2 (g0 + d) + 3 against 2 g0 + d + 1; + the fma; then the contraction as for "kt"
+        return 2 * (g0 + d) + 4 + tab + (d + 1) + (d + 1) + 1 + last
+    nr = (2 * d + 1 + 2 + nq + 1) if quad else (g0 + d + tab + (d + 1))
+    # nr[j] = int (w . grad phi_i) phi_j / |J|: :968-983 wt = w wg (wa, wg: 2 d + 1; constant, product), NQ fma, constant phi;
+    # :1037-1041: wa (g0 + d), d + 1 fma over the table
+    if form == "n_time":  # :1046 tdt = tau (0.5 two_idt) (1 / t) (2 / dt, 1 / t, two products), :1054 c[j] = fma(tdt, nr[j], c[j])
+        return nr + 4 + 1 + last
+    if form == "supg":  # the accumulator entry K_t + (N/dt + S/2) / t of one (row, cell): its longest chain
+        return max(chain("kt_s", d, deg), chain("n_time", d, deg))
+    if form == "supg_rhs":
+        # :1053-1063: fma(two_idt, c1, fh) (two_idt: 1), ND fma with nr[j], adet tau, rs = fma(adet tau, r, rs)
+        return nr + 2 + nd + 1 + 1
     ndp = O.num_cell_dofs(d, deg2)
     if form == "grad0":  # :1049-1056: pq (ND_p fma, constant phi, * w), S (NQ fma, constant dphi); :1069-1075 (d + 1 fma, fma)
         return g0 + ndp + 3 + nq + 1 + (d + 1) + 1
@@ -625,6 +657,175 @@ class Model:
         assert n_b.max() <= N_MAX
         return {"A": A, "b_first": (C.matvec(x(u1), ar) + x(b0), Bb + np.abs(np.asarray(b0, dtype=np.float64)), n_b),
                 "a_u1": (A.matvec(x(u1)), Ba, n_a)}
+
+
+    # -- the scalar row kernels (DESIGN.md sections 13, 25, 32) -----------------------------------------------------------
+    def _pattern(self):
+        """(rows, cols, cells per entry) of the velocity component space: every pair of dofs that share a cell."""
+        if not hasattr(self, "_pat"):
+            nd = self.vd.shape[1]
+            rows, cols, _, _, cnt = _scatter(np.zeros((self.vd.shape[0], nd, nd)), self.vd, self.vd, (self.nv, self.nv))
+            self._pat = (rows, cols, cnt)
+        return self._pat
+
+    def _supg_e(self, w, tau):
+        """N_e[i][j] = |J| tau sum_a (w . G_a) int phi_j d(phi_i)/d(lambda_a),
+        S_e[i][j] = |J| tau sum_ab (w . G_a)(w . G_b) int d(phi_i)/d(lambda_a) d(phi_j)/d(lambda_b), and their bounds."""
+        g, deg = self.geo, self.u_deg
+        aphi, agrad = self._abs_tab(deg)
+        wa = _einsum("cd,cad->ca", self._e(w), g.G)
+        s = (g.adet * self._e(tau))[:, None, None]
+        T = self._ref("val_grad", deg, deg)  # [j][i][a] = int phi_j d(phi_i) / d(lambda_a)
+        Ne = s * _einsum("ca,jia->cij", wa, T)
+        Se = s * _einsum("ca,cjia->cij", wa, _einsum("cb,iajb->cjia", wa, self._ref("stiff", deg)))
+        awg = np.einsum("cd,cqid->cqi", np.abs(np.asarray(w, dtype=np.float64)), agrad, optimize=True)
+        sa = (g.aadet * np.abs(np.asarray(tau, dtype=np.float64)))[:, None, None]
+        BN = sa * np.einsum("q,cqi,qj->cij", self.w, awg, aphi, optimize=True)
+        BS = sa * np.einsum("q,cqi,cqj->cij", self.w, awg, awg, optimize=True)
+        return Ne, BN, Se, BS
+
+    def _rows(self, Adev, Mdev, Kdev, s, dt, c1, b0, a_c1, acc=None, n_acc=0, rs=None):
+        """The epilogue shared by the three row kernels (k_scalar_rows :97-119, scalar_cellvisc_slice :1116-1142):
+        A_c = A + s K [+ acc],  sa = A_c c_1,  sm = M c_1,  b_c = fma(2/dt, sm, -sa) + b0 [+ rs].
+        ``acc`` (value, B) per entry of the pattern: what the LDS accumulator holds, scaled; ``n_acc`` (nnz,): its chain,
+        the epilogue's operations on it included; ``rs`` (value, B, n) (n_dofs, NC): the register-summed right-hand side."""
+        rows, cols, cnt = self._pattern()
+        x = self._e
+        look = lambda Mat: np.asarray(Mat.tocsr()[rows, cols]).ravel()  # noqa: E731
+        A, M, K = x(look(Adev)), x(look(Mdev)), x(look(Kdev))
+        aA, aM, aK = (np.abs(to_f64(v)) for v in (A, M, K))
+        val, B = A + x(np.float64(s)) * K, aA + abs(float(s)) * aK
+        n = np.ones_like(cnt)  # v = fma(s, k, a)
+        if acc is not None:
+            val, B, n = val + acc[0], B + acc[1], n + n_acc
+        Ac = Entries(rows, cols, val, B, n, (self.nv, self.nv))
+        c1 = np.asarray(c1, dtype=np.float64).reshape(self.nv, -1)
+        b0 = np.asarray(b0, dtype=np.float64).reshape(self.nv, -1)
+        ac1 = np.abs(c1)
+        width = np.bincount(rows, minlength=self.nv)
+        width = (width + 1) // 2 * 2  # the storage width of the row (OX_KV = 2)
+        nrow = np.zeros(self.nv, dtype=np.int64)
+        np.maximum.at(nrow, rows, n)
+        Ba = np.zeros_like(ac1)
+        np.add.at(Ba, rows, B[:, None] * ac1[cols])
+        Bm = np.zeros_like(ac1)
+        np.add.at(Bm, rows, aM[:, None] * ac1[cols])
+        sa, sm = Ac.matvec(x(c1)), Ac.matvec(x(c1), M)
+        two_idt = 2 / x(np.float64(dt))
+        bval, bB = two_idt * sm - sa + x(b0), 2.0 / dt * Bm + Ba + np.abs(b0)
+        # sa: the entry's chain + one fma per stored entry; sm: 2 / dt and one fma per stored entry; the fma, the b0 add
+        n_b = nrow + width + 2
+        if rs is not None:
+            bval, bB, n_b = bval + rs[0], bB + rs[1], np.maximum(n_b, rs[2]) + 1
+        one = np.ones((1, c1.shape[1]), dtype=np.int64)
+        n_b, n_a = n_b[:, None] * one, (nrow + width)[:, None] * one
+        assert n_b.max() <= N_MAX, int(n_b.max())
+        out = {"A_c": Ac, "b_c": (bval, bB, n_b)}
+        if a_c1:
+            out["a_c1"] = (sa, Ba, n_a)
+        return out
+
+    def scalar_rows(self, Adev, Mdev, Kdev, s, dt, c1, b0, a_c1=True):
+        """ox_scalar_rows from the device's own A, M, K (scipy, promoted exactly): A_c = A + s K,
+        b_c = (2/dt) M c_1 - A_c c_1 + b0, a_c1 = A_c c_1; c_1, b0: (n_dofs, NC)."""
+        return self._rows(Adev, Mdev, Kdev, s, dt, c1, b0, a_c1)
+
+    def _acc_entries(self, Ae, Be):
+        _, _, val, (B,), _ = _scatter(Ae, self.vd, self.vd, (self.nv, self.nv), extra=(Be,))
+        return val, B
+
+    def scalar_rows_cellvisc(self, Adev, Mdev, Kdev, s, dt, c1, b0, nut, t, a_c1=True):
+        """ox_scalar_rows_cellvisc: A_c = A + s K + t K_t, K_t = sum_c nut_c K_c (v = fma(t, kt, fma(s, k, a)): + 1)."""
+        Ke, BKe = self._stiff_e(self.u_deg)
+        kt, Bkt = self._acc_entries(self._e(nut)[:, None, None] * Ke, np.abs(np.asarray(nut, dtype=np.float64))[:, None, None] * BKe)
+        tx = self._e(np.float64(t))
+        n_acc = self._pattern()[2] + chain("kt", self.d, self.u_deg) + 1
+        return self._rows(Adev, Mdev, Kdev, s, dt, c1, b0, a_c1, acc=(tx * kt, abs(float(t)) * Bkt), n_acc=n_acc)
+
+    def scalar_rows_supg(self, Adev, Mdev, Kdev, s, dt, c1, b0, nut, t, rec, fh, a_c1=True, mutate=None):
+        """ox_scalar_rows_supg from the device's own records ``rec`` ((d + 1, n_cells): w_c, then tau_c; promoted exactly):
+        A_c = A + s K + t K_t + N/dt + S/2 (the accumulator holds K_t + (N/dt + S/2)/t, v = fma(t, acc, fma(s, k, a)): + 1;
+        without nut t = 1),  b_c += N ((2/dt) c_1 + f_h).  ``nut`` None: no K_t.
+        ``mutate`` (host tests): called with the element tensors {"Kt", "N", "S"} before they are summed."""
+        rec = np.asarray(rec, dtype=np.float64).reshape(self.d + 1, -1)
+        w, tau = rec[: self.d].T, rec[self.d]
+        x = self._e
+        Ne, BN, Se, BS = self._supg_e(w, tau)
+        idt = 1 / x(np.float64(dt))
+        el = {"N": Ne, "S": Se, "Kt": None}
+        Bacc = BN / dt + BS / 2
+        if nut is not None:
+            Ke, BKe = self._stiff_e(self.u_deg)
+            el["Kt"] = x(np.float64(t)) * x(nut)[:, None, None] * Ke
+            Bacc = Bacc + abs(float(t)) * np.abs(np.asarray(nut, dtype=np.float64))[:, None, None] * BKe
+        if mutate is not None:
+            mutate(el)
+        acc_e = idt * el["N"] + el["S"] / 2
+        if el["Kt"] is not None:
+            acc_e = acc_e + el["Kt"]
+        acc = self._acc_entries(acc_e, Bacc)
+        n_acc = self._pattern()[2] + chain("supg", self.d, self.u_deg) + 1
+        c1 = np.asarray(c1, dtype=np.float64).reshape(self.nv, -1)
+        fh = np.asarray(fh, dtype=np.float64).reshape(self.nv, -1)
+        rhs = 2 * idt * x(c1) + x(fh)
+        arhs = 2.0 / dt * np.abs(c1) + np.abs(fh)
+        re = _einsum("cij,cjk->cik", el["N"], rhs[self.vd])
+        Bre = np.einsum("cij,cjk->cik", BN, arhs[self.vd], optimize=True)
+        rval, (rB,), rcnt = _scatter_vec(re, self.vd, self.nv, extra=(Bre,))
+        rs = (rval, rB, rcnt + chain("supg_rhs", self.d, self.u_deg))
+        return self._rows(Adev, Mdev, Kdev, s, dt, c1, b0, a_c1, acc=acc, n_acc=n_acc, rs=rs)
+
+    def supg_cells(self, uab, nut, kappa, inv_sct, dt, scale, time_term):
+        """ox_supg_cells (k_supg_cells, csrc/ox_scalar.hip :572-612): {"w": (value (nc, d), B, n), "tau": (value (nc,), tol)}.
+        w_c = sum_i phic_i u_i (phic: the basis at the centroid, exact): ND fma: n = ND, the criterion (n + 2) u B.
+        tau_c = scale / sqrt(r), r = t2 + (k q)^2 + (2 k^2 kap g)^2: ``tol`` is the ABSOLUTE bound, propagated: q_c = sum_a
+        |w . G_a| holds cancelling sums, so its error is bounded against sum_a sum_d |w_d| |G_ad| (and what the error of
+        w itself does to it), not against q; g, kap, cq, cd, the two fma, the root and the division add one rounding each
+        against their own (positive) terms; t2 = (2/dt)(2/dt) is formed on the host: 3."""
+        d, deg, x = self.d, self.u_deg, self._e
+        frac = Fraction(1, d + 1) if deg < 3 else mpmath.mpf(1) / (d + 1)
+        phic = ext(np.array(basis_at(d, deg, [frac] * (d + 1)), dtype=object), self.x)
+        nd = self.vd.shape[1]
+        au = np.abs(np.asarray(uab, dtype=np.float64))
+        w = _einsum("cid,i->cd", x(uab)[self.vd], phic)
+        Bw = np.einsum("cid,i->cd", au[self.vd], np.abs(to_f64(phic)))
+        # (``tab_err``: what someone else's tabulation of the centroid values adds to w, an absolute error)
+        ew = np.einsum("cid,i->cd", au[self.vd], self.tab_err[deg][0]) if deg in self.tab_err else 0.0 * Bw
+        G, aG = self.geo.G, self.geo.aG
+        wa = _einsum("cd,cad->ca", w, G)
+        q = absx(wa).sum(axis=1)
+        g = (G * G).sum(axis=(1, 2))
+        kap = x(np.float64(kappa)) + (x(np.float64(inv_sct)) * x(nut) if nut is not None else 0)
+        k = deg
+        t2 = (2 / x(np.float64(dt))) ** 2 if time_term else x(np.float64(0.0))
+        cq, cd = k * q, 2 * k * k * kap * g
+        r = t2 + cq * cq + cd * cd
+        rf = to_f64(r)
+        pos = rf > 0
+        root = np.array([mpmath.sqrt(v) for v in r], dtype=object) if r.dtype == object else np.sqrt(r)
+        tau = np.where(pos, x(np.float64(scale)) / np.where(pos, root, 1), 0 * r)
+        # -- the bound, first order with the second-order terms kept on the safe side (float64) --
+        dw = (nd + 2) * U * (Bw + ew) + ew
+        Bwa = np.einsum("cd,cad->ca", np.abs(to_f64(w)) + dw, aG)  # sum_d |w_d| |G_ad|
+        g0 = np.array([d] + [0] * d)  # G_0 = -sum_a G_a: d roundings against |G_0| := sum_a |G_a|
+        dwa = np.einsum("cd,cad->ca", dw, aG) + (d + 1 + g0)[None] * U * Bwa
+        dq = dwa.sum(axis=1) + (d + 1) * U * Bwa.sum(axis=1)
+        Bg = (aG ** 2).sum(axis=(1, 2))
+        dg = ((d + 1) * d + 2 * d + 1) * U * Bg
+        kf, gf, qf = to_f64(kap) * np.ones(self.geo.nc), to_f64(g), to_f64(q)
+        dk = U * kf if nut is not None else 0.0 * kf  # kap = fma(inv_sct, nut, kappa)
+        cqf, dcq = k * qf, k * dq + U * k * (qf + dq)
+        cdf = 2 * k * k * kf * gf
+        dcd = 2 * k * k * ((kf + dk) * dg + dk * gf) + 2 * U * 2 * k * k * (kf + dk) * (gf + dg)
+        dt2 = 3 * U * float(to_f64(t2))
+        dr = (2 * cdf + dcd) * dcd + (2 * cqf + dcq) * dcq + dt2
+        dr = dr + 2 * U * (rf + dr)  # the two fma
+        assert (dr[pos] < 0.5 * rf[pos]).all(), "r has no correct digit: the first-order bound does not hold"
+        tf = to_f64(tau)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            grow = np.where(pos, np.expm1(-0.5 * np.log1p(-np.where(pos, dr / np.where(pos, rf, 1), 0.0))), 0.0)
+        tol = tf * grow + 3 * U * tf * (1 + grow)  # the root, the division, and their second order
+        return {"w": (w, Bw + ew, np.full(Bw.shape, nd, dtype=np.int64)), "tau": (tau, tol), "q": (q, Bwa.sum(axis=1)), "g": g}
 
 
 def spmv_bound(A_csr, x):

@@ -13,7 +13,8 @@ What each one reaches:
 The storage width of a row is its length rounded up to ``OX_KV`` = 2; set-up refuses a width of 256.  ``FAN_K`` /
 ``SPINDLE_K`` list, per element degree, the k whose widest row lands just below and just above every point at which the
 row kernels change their launch (ox_assemble.hip, launch_rows_t: 4 -> 2 waves per block above 70 entries, 2 -> 1 above 140;
-67 and 134 with a per-cell viscosity) and at the last width the position bytes hold (254)."""
+67 and 134 with a per-cell viscosity, and in launch_scalar_cellvisc_t, which sizes the launches of ox_scalar_rows_cellvisc and
+ox_scalar_rows_supg by the same rule) and at the last width the position bytes hold (254)."""
 from __future__ import annotations
 
 import numpy as np
