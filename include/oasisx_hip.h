@@ -1043,6 +1043,49 @@ int ox_scalar_flux_cells(int degree, const ox_cells *cells, const int32_t *cell_
                          const int32_t *facet_rec, const double *c, int nc, int col, double kappa, const double *nut,
                          double inv_sct, double weight, double *q, double *fq, double *cbar, double *acc_q, void *stream);
 
+/* ---- Reacting scalars: mass-action kinetics, split from the transport step (ox_reaction.hip) ----
+ * A network of R <= OX_REACT_MAXR reactions between S <= OX_REACT_MAXS species.  At a dof i with the concentrations c:
+ *   k_j   = kdof[j] ? kdof[j][i] : k[j]
+ *   a_j   = arr[j] >= 0 ? exp(-Ta[j] / c[arr[j]]) : 1          (no guard on c <= 0: a value that is not finite stays in its dof)
+ *   r_j   = ((k_j a_j) p_j0) p_j1 ...,   p_js = c_s^order[j][s] by repeated multiplication (orders 0..3; 1 for order 0)
+ *   f_s   = sum_j nu[s][j] r_j                                 (j ascending, from 0)
+ *   J_st  = sum_j nu[s][j] d_jt,  d_jt = (k_j a_j) prod_s (s == t ? order[j][s] c_s^(order[j][s] - 1) : p_js)
+ *                                        [+ (r_j Ta[j]) / (c_t c_t) where t == arr[j]]       (nothing is divided by c otherwise)
+ * The record is a HOST structure, copied into the kernel arguments: its tables are lane-uniform scalar loads. */
+#define OX_REACT_MAXS 6
+#define OX_REACT_MAXR 12
+typedef struct {
+  int32_t S, R;
+  double nu[OX_REACT_MAXS][OX_REACT_MAXR];     /* products - reactants */
+  int32_t order[OX_REACT_MAXR][OX_REACT_MAXS]; /* 0..3 */
+  double k[OX_REACT_MAXR];
+  const double *kdof[OX_REACT_MAXR];           /* device [n] or NULL: the rate coefficient per dof */
+  int32_t arr[OX_REACT_MAXR];                  /* the species whose value is the Arrhenius temperature, or -1 */
+  double Ta[OX_REACT_MAXR];
+} ox_react_net;
+/* Species s lives in column col of an interleaved (n, nc) block -- the species of one network usually sit in different
+ * blocks of different nc.  src is read once, out (and out2 where not NULL) written once; src, out and out2 may be one
+ * block, and several species may share a block (other columns of it are neither read nor written).  held: device [n]
+ * bytes or NULL; where held[i] != 0 the species' value at i is written back as it was read (its Dirichlet rows) while it
+ * still enters the rates of the others. */
+typedef struct {
+  const double *src;
+  double *out, *out2;
+  const uint8_t *held;
+  int32_t nc, col;
+} ox_react_species;
+/* `substeps` steps h = H / substeps of ROS2 (Verwer, Spee, Blom, Hundsdorfer 1999; second order, L-stable) per dof, all
+ * in registers, with g = 1 + 1/sqrt(2) and W = I - (g h) J(y):
+ *   W k1 = f(y);   W k2 = f(y + h k1) - 2 k1;   y <- (y + (1.5 h) k1) + (0.5 h) k2
+ * W is factorised once per substep with partial pivoting (largest |.| of the column, ties to the lower row), the pivots
+ * kept as reciprocals; rows are exchanged through selects over compile-time indices.  The step count is fixed: equal inputs
+ * give equal bits.  f = 0 and J = 0 (all k_j = 0) leave y bit-unchanged.  One lane per dof, one instantiation per S, no
+ * LDS, no atomics, no scratch, no host synchronisation.  species: HOST array [net->S]. */
+int ox_scalar_react(const ox_react_net *net, const ox_react_species *species, int64_t n, double H, int substeps,
+                    void *stream);
+/* rates[j n + i] = r_j at dof i from the species' src blocks (device [R][n]): the rate function of ox_scalar_react alone. */
+int ox_reaction_rates(const ox_react_net *net, const ox_react_species *species, int64_t n, double *rates, void *stream);
+
 /* ---- Wall shear stress, traction and boundary forces on exterior facets (ox_wall.hip) ----------
  * Facet i -- the caller passes the facets SORTED by tag -- belongs to the cell at kernel position facet_rec[2 i] and lies
  * opposite that cell's local vertex facet_rec[2 i + 1] (a record outside the tables reads nothing and leaves NaN).  With

@@ -15,6 +15,7 @@ from .geometry import Probes, WallDistance  # noqa: F401
 from .ksp import KSPSolver  # noqa: F401
 from .outlet import FlowRate, Resistance, Windkessel
 from .particles import DEPOSITED, InertialParticles
+from .reaction import Reaction, ReactionNetwork
 from .scalar import SUPG, FluxBC, RobinBC, ScalarFlux, ScalarTransport
 from .tracers import Tracers
 from .viscosity import (CarreauYasuda, CellViscosity, Cross, DynamicSmagorinsky, PatchFilter, PowerLaw, Smagorinsky, VanDriest,
@@ -36,6 +37,8 @@ __all__ = [
     "ScalarFlux",
     "FluxBC",
     "RobinBC",
+    "Reaction",
+    "ReactionNetwork",
     "Smagorinsky",
     "DynamicSmagorinsky",
     "PatchFilter",

@@ -371,6 +371,33 @@ class ox_buoy_term(C.Structure):
     ]
 
 
+REACT_MAXS, REACT_MAXR = 6, 12  # OX_REACT_MAXS / OX_REACT_MAXR
+
+
+class ox_react_net(C.Structure):
+    _fields_ = [
+        ("S", C.c_int32),
+        ("R", C.c_int32),
+        ("nu", (C.c_double * REACT_MAXR) * REACT_MAXS),
+        ("order", (C.c_int32 * REACT_MAXS) * REACT_MAXR),
+        ("k", C.c_double * REACT_MAXR),
+        ("kdof", C.c_void_p * REACT_MAXR),
+        ("arr", C.c_int32 * REACT_MAXR),
+        ("Ta", C.c_double * REACT_MAXR),
+    ]
+
+
+class ox_react_species(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("out", C.c_void_p),
+        ("out2", C.c_void_p),
+        ("held", C.c_void_p),
+        ("nc", C.c_int32),
+        ("col", C.c_int32),
+    ]
+
+
 class ox_scalar_bc_args(C.Structure):
     _fields_ = [
         ("degree", C.c_int),
@@ -518,6 +545,8 @@ SIGNATURES = {
     "ox_scalar_rows_supg": (_I, [C.POINTER(ox_cells), C.POINTER(ox_space_info), C.POINTER(ox_sell), C.POINTER(ox_sell),
                                  C.POINTER(ox_sell), C.POINTER(ox_sell), _P, _P, _D, _D, _D, _I, _P, _P, _P, _P, _P, _I, _P]),
     "ox_buoyancy_rows": (_I, [C.POINTER(ox_sell), _I, _I, C.POINTER(ox_buoy_term), _P, _P]),
+    "ox_scalar_react": (_I, [C.POINTER(ox_react_net), C.POINTER(ox_react_species), _L, _D, _I, _P]),
+    "ox_reaction_rates": (_I, [C.POINTER(ox_react_net), C.POINTER(ox_react_species), _L, _P, _P]),
     "ox_scalar_flux": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
     "ox_scalar_flux_cells": (_I, [_I, C.POINTER(ox_cells), _P, _L, _P, _P, _I, _I, _D, _P, _D, _D, _P, _P, _P, _P, _P]),
     "ox_wall_stress": (_I, [_I, _I, C.POINTER(ox_cells), _P, _P, _L, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P]),

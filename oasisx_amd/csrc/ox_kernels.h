@@ -157,6 +157,8 @@ int ox_reduce_partials(const double *partial, int nparts, int nv, double *sums, 
 #define OX_TAG_SCALAR_ROWS_CELLVISC 192 // ox_scalar_rows_cellvisc (key = columns)
 #define OX_TAG_SCALAR_ROWS_SUPG 193 // ox_scalar_rows_supg (key = columns)
 #define OX_TAG_SUPG_CELLS 194      // ox_supg_cells (key = cells)
+#define OX_TAG_SCALAR_REACT 195    // ox_scalar_react (key = 100 x species + reactions)
+#define OX_TAG_REACTION_RATES 196  // ox_reaction_rates (key = 100 x species + reactions)
 #define OX_TAG_DYNAMIC_CELLS 200    // ox_dynamic_cells (key = cells)
 #define OX_TAG_DYNAMIC_VERTICES 201 // ox_dynamic_vertices (key = vertices)
 #define OX_TAG_DYNAMIC_PRODUCTS 202 // ox_dynamic_products (key = cells)

@@ -129,12 +129,23 @@ class FractionalStep_AB_CN:
             ``A`` and ``b_first`` inside ``assemble_first`` (``drag_assemble``, :mod:`oasisx_amd.drag`); ``None``: no drag
             call is made.  One GPU only; not with ``rotational=True``
         drag_theta: implicitness of the drag term in [0.5, 1]: 1 (default) backward Euler, 0.5 Crank-Nicolson
+        reactions: a :class:`oasisx_amd.ReactionNetwork` between scalars of ``scalars=``: stiff mass-action kinetics,
+            integrated per dof by an L-stable Rosenbrock scheme and split from the unchanged transport step
+            (``scalar_react``, ``reaction_rates``, :mod:`oasisx_amd.reaction`); ``None``: no reaction call is made.  One GPU
     """
 
     def __init__(self, mesh, u_element, p_element, bcs_u, bcs_p, rotational: bool = False,
                  solver_options: dict | None = None, jit_options: dict | None = None,
                  body_force=None, options: dict | None = None, scalars=None, viscosity_model=None,
-                 stress_form: str = "laplacian", drag=None, drag_theta: float = 1.0):
+                 stress_form: str = "laplacian", drag=None, drag_theta: float = 1.0, reactions=None):
+        if reactions is not None:  # the scope guards need neither the library nor a GPU
+            from .reaction import ReactionNetwork
+
+            if not isinstance(reactions, ReactionNetwork):
+                raise TypeError(f"reactions: a ReactionNetwork is expected (got {type(reactions).__name__})")
+            if not scalars:
+                raise ValueError("reactions= without scalars=: the species of a network are scalars of the solver")
+            reactions.check_names({getattr(s, "name", None) for s in scalars})
         if stress_form not in ("laplacian", "full"):
             raise ValueError(f'stress_form: "laplacian" or "full" is expected (got {stress_form!r})')
         if stress_form == "full" and viscosity_model is None:
@@ -338,6 +349,9 @@ class FractionalStep_AB_CN:
             # scalars that drive the flow: the kernel's term records, per launch (empty: every scalar is passive)
             self._buoyancy = _sc.buoyancy_terms(self._scalar_groups)
         self.timings = {}
+        self._reactions = reactions
+        if reactions is not None:
+            reactions.bind(self)
 
     # ------------------------------------------------------------------------------------
     def _compile_and_allocate_forms(self):
@@ -828,6 +842,28 @@ class FractionalStep_AB_CN:
                 out[m.name] = int(reasons[j])
         return out
 
+    @_phase
+    def scalar_react(self, h: float):
+        """The kinetics of ``reactions=`` over ``h``: ``network.substeps`` ROS2 steps per dof from ``c_1`` into ``c_1`` AND
+        ``c`` (``ox_scalar_react``: one launch for every species, whatever groups they sit in; no host synchronisation).
+        A species' own Dirichlet rows keep their bits; a scalar in no reaction is neither read nor written.  ``solve`` calls
+        it around the transport step (``splitting=``); callable on its own.  ``timings["scalar_react"]`` sums the host
+        time of the enqueues."""
+        if self._reactions is None:
+            raise RuntimeError("scalar_react: the solver was built without reactions=")
+        import time
+
+        t0 = time.perf_counter()
+        self._reactions.react(h)
+        self.timings["scalar_react"] = self.timings.get("scalar_react", 0.0) + (time.perf_counter() - t0)
+
+    def reaction_rates(self) -> torch.Tensor:
+        """``r_j`` of every reaction at the current level ``c``: a device tensor ``(n_reactions, n_dofs)`` (a rate-only
+        launch, ``ox_reaction_rates``; the tensor is reused by the next call)."""
+        if self._reactions is None:
+            raise RuntimeError("reaction_rates: the solver was built without reactions=")
+        return self._reactions.rates()
+
     def scalar(self, name: str, level: int = 0) -> Function:
         """The scalar ``name``: the current level ``c`` (``level=0``) or the previous one ``c_1`` (``level=1``), from which
         the next step starts -- write initial data there -- or ``c_2`` (``level=2``), which only a group with a coupled
@@ -861,6 +897,11 @@ class FractionalStep_AB_CN:
                     bc.update_bc()
                 for bc in m.flux_bcs:
                     bc.update()
+        rx = self._reactions
+        if rx is not None:
+            rx.update()
+            if rx.splitting == "strang":  # the transport step starts from the reacted c_1
+                self.scalar_react(0.5 * dt)
         self.assemble_first(dt, nu)
         while inner_it < max_iter and diff > max_error:
             inner_it += 1
@@ -875,6 +916,8 @@ class FractionalStep_AB_CN:
         if self._scalar_groups:  # after the velocity update (Oasis' order); u_ab of this step is in the operator already
             reasons = self.scalar_solve()
             assert all(r > 0 for r in reasons.values()), f"scalar transport solve failed: {reasons}"
+            if rx is not None:  # c_1 is a bit copy of c here: the kinetics read c_1 and write both levels
+                self.scalar_react(0.5 * dt if rx.splitting == "strang" else dt)
         # u2 <- u1, u1 <- u, p <- ps (:689-693)
         _lib.check(lib.ox_axpby(n, 1.0, self._U1.ptr(), 0.0, None, self._U2.ptr(), st), "ox_axpby")
         _lib.check(lib.ox_axpby(n, 1.0, self._U.ptr(), 0.0, None, self._U1.ptr(), st), "ox_axpby")
